@@ -1,10 +1,17 @@
 """Benchmark: population env-steps/s (+ learner updates/s) of an 8-agent PPO
 population (config 2: LunarLander-shaped, 128 vec envs per agent, T=16,
-B=128, E=4), plus the GAE + clipped-loss kernel roofline at the SURVEY §8d
-synthetic shape, plus the reference-style CPU baseline.
+B=128, E=4).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the one JSON
+line.  ``--dump-outputs DIR`` also writes what the last timed step computed
+as ``DIR/<name>.npy``.  ``--full`` adds every side measurement: the learner
+kernel alone, the GAE + clipped-loss kernel roofline at the SURVEY §8d
+synthetic shape, the off-policy kernels, configs 3 and 5, the end-to-end
+``train_on_policy`` run, the mutated-shape learner, the weak-scaling leg
+(N > 1) and the reference-style CPU baselines.
 
 A "step" = one PPO iteration of the population: T vector steps of rollout
 for every agent (host env + HBM rollout SoA), bootstrap + GAE, and E x M
@@ -51,6 +58,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pop", type=int, default=8, help="agents in the whole population (sharded over the GPUs)")
     ap.add_argument("--pop-per-gpu", type=int, default=8, help="agents per GPU of the extra weak-scaling leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (learner kernel, roofline, kernels, configs 3 and 5, "
+                         "train_on_policy, mutated-shape learner, weak scaling, CPU baselines); the --no-* "
+                         "options below skip single ones of them")
     ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling leg")
     ap.add_argument("--num-envs", type=int, default=128)
     ap.add_argument("--learn-step", type=int, default=2048)
@@ -141,8 +154,29 @@ def dist_selftest(args, world, rank):
 
 
 # --------------------------------------------------------------------------- #
-def population_leg(args, world, rank, P, steps=None):
-    """P agents on this rank, global agents rank*P .. of a world*P population."""
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``arrays`` (name -> tensor) as ``path/<name>.npy``: float64 stays, every
+    other dtype is written as float32.  An array over its share of the 64 MB
+    budget is written as a fixed sample of its flattened elements (sorted
+    indices drawn by numpy's PCG64 seeded 0, the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def population_leg(args, world, rank, P, steps=None, dump=None, learner_probe=False):
+    """P agents on this rank, global agents rank*P .. of a world*P population.
+    ``dump``: directory for the last timed step's outputs (dump_outputs).
+    ``learner_probe``: time learn() alone after the timed steps."""
     from agilerl_amd.envs import SyntheticVecEnv
     from agilerl_amd.hpo.population_sync import PopulationSync
     from agilerl_amd.population.nets import ActorCriticSpec
@@ -153,6 +187,7 @@ def population_leg(args, world, rank, P, steps=None):
                            actor_hidden=[64], critic_hidden=[64])
     N = args.num_envs
     steps = args.steps if steps is None else steps
+    np.random.seed(0)  # the minibatch orders come from numpy's global stream: the same in every run
     seeds = [rank * P + i for i in range(P)]
     pop = PPOPopulation(spec, P, N, learn_step=args.learn_step, batch_size=args.batch_size, lr=1e-3,
                         update_epochs=args.epochs, seeds=seeds, device="cuda",
@@ -163,9 +198,10 @@ def population_leg(args, world, rank, P, steps=None):
     sync = PopulationSync(pop, runner, world, rank, seed=42) if args.evo_every > 0 else None
 
     def step(i):
-        runner.iteration()
+        loss = runner.iteration()
         if sync is not None and (i + 1) % args.evo_every == 0:
             sync.generation()
+        return loss
 
     for i in range(args.warmup):
         runner.iteration()
@@ -175,8 +211,9 @@ def population_leg(args, world, rank, P, steps=None):
     barrier(world)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    loss = None
     for i in range(steps):
-        step(i)
+        loss = step(i)
     torch.cuda.synchronize()
     barrier(world)
     torch.cuda.synchronize()
@@ -184,8 +221,26 @@ def population_leg(args, world, rank, P, steps=None):
     pop.check_errors()  # a partner timeout in any timed learn() fails the run loudly
     env_steps = world * P * pop.S * steps
     updates = world * P * args.epochs * pop.n_minibatches() * steps
-    # the dominant kernel alone: learn() (gather prologue + fused learner) on the
-    # last rollout, HIP events on the launch stream
+    if dump is not None and loss is not None:
+        # what a caller of the timed step holds after it: the per-agent mean loss
+        # iteration() returned, the parameters and Adam state the learner (and a
+        # generation's parent clone) left, and the rollout with its GAE
+        dump_outputs(dump, {"loss": loss, "params": pop.params.data, "adam_exp_avg": pop.opt.exp_avg,
+                            "adam_exp_avg_sq": pop.opt.exp_avg_sq, "obs": pop.obs, "actions": pop.actions,
+                            "rewards": pop.rewards, "dones": pop.dones, "values": pop.values,
+                            "log_probs": pop.log_probs, "advantages": pop.advantages, "returns": pop.returns})
+    out = dict(dt=dt, env_steps=env_steps, updates=updates, S=pop.S, T=pop.T, learner=None,
+               generations=(steps // args.evo_every) if args.evo_every else 0)
+    if learner_probe:
+        out["learner"] = learner_leg(args, pop, P)
+    del runner, pop, sync
+    torch.cuda.empty_cache()
+    return out
+
+
+def learner_leg(args, pop, P):
+    """The dominant kernel alone: learn() (gather prologue + fused learner) on
+    the last rollout, HIP events on the launch stream."""
     reps = 10
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -203,11 +258,7 @@ def population_leg(args, world, rank, P, steps=None):
                    frac=round(flop / learn_s / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
                    bound="latency: 64 serial minibatch updates per agent, each a chain of barrier-separated "
                          "small GEMM / row phases and a 3-barrier partner hand-off (DESIGN §5)")
-    out = dict(dt=dt, env_steps=env_steps, updates=updates, S=pop.S, T=pop.T, learner=learner,
-               generations=(steps // args.evo_every) if args.evo_every else 0)
-    del runner, pop, sync
-    torch.cuda.empty_cache()
-    return out
+    return learner
 
 
 # --------------------------------------------------------------------------- #
@@ -1150,32 +1201,10 @@ def cpu_config3_learn(seconds: float, B: int = 64):
                 sample=f"{reps} Rainbow updates of one config-3 agent (B={B}) in torch CPU ops on {threads} threads")
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args))
-    world, rank, local = setup_dist(gpu=not args.dist_selftest)
-    if world != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s)")
-    if args.dist_selftest:
-        dist_selftest(args, world, rank)
-        if world > 1:
-            dist.destroy_process_group()
-        return
-    from agilerl_amd import _lib
-
-    _lib.load()
-    if args.pop % world:
-        raise SystemExit(f"bench.py: --pop {args.pop} agents cannot be sharded over {world} GPUs")
-    log("population leg")
-    res = population_leg(args, world, rank, args.pop // world)
-    weak = None
-    if world > 1 and not args.no_weak:
-        w = population_leg(args, world, rank, args.pop_per_gpu)
-        weak = {"value": round(w["env_steps"] / w["dt"], 1), "unit": "env-steps/s",
-                "ms_per_step": round(w["dt"] / args.steps * 1e3, 3),
-                "learner_updates_per_s": round(w["updates"] / w["dt"], 1),
-                "workload": f"{args.pop_per_gpu} agents per GPU ({args.pop_per_gpu * world}-agent population)"}
+def full_legs(args, world, rank, res):
+    """The side measurements of ``--full`` after the population leg ->
+    (roofline, kernels, config5, config3, train_on_policy, mutated_shape_learner,
+    cpu_baseline), each None where it is switched off or does not apply."""
     roof = kern = None
     if not args.no_roofline:
         log("roofline leg")
@@ -1204,6 +1233,39 @@ def main():
         cpu["cpu_model"] = cpu["off_policy"]["cpu_model"]
         if c3 is not None:
             cpu["config3_learn"] = cpu_config3_learn(min(args.cpu_seconds, 10.0))
+    return roof, kern, c5, c3, tp, ml, cpu
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(spawn_ranks(args))
+    world, rank, local = setup_dist(gpu=not args.dist_selftest)
+    if world != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s)")
+    if args.dist_selftest:
+        dist_selftest(args, world, rank)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    from agilerl_amd import _lib
+
+    _lib.load()
+    if args.pop % world:
+        raise SystemExit(f"bench.py: --pop {args.pop} agents cannot be sharded over {world} GPUs")
+    log("population leg")
+    res = population_leg(args, world, rank, args.pop // world, dump=args.dump_outputs if rank == 0 else None,
+                         learner_probe=args.full)
+    weak = None
+    if args.full and world > 1 and not args.no_weak:
+        w = population_leg(args, world, rank, args.pop_per_gpu)
+        weak = {"value": round(w["env_steps"] / w["dt"], 1), "unit": "env-steps/s",
+                "ms_per_step": round(w["dt"] / args.steps * 1e3, 3),
+                "learner_updates_per_s": round(w["updates"] / w["dt"], 1),
+                "workload": f"{args.pop_per_gpu} agents per GPU ({args.pop_per_gpu * world}-agent population)"}
+    roof = kern = c5 = c3 = tp = ml = cpu = None
+    if args.full:
+        roof, kern, c5, c3, tp, ml, cpu = full_legs(args, world, rank, res)
     if rank == 0:
         value = res["env_steps"] / res["dt"]
         line = {

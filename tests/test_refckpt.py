@@ -5,10 +5,13 @@ stand-ins for every class the file names.
 
 * the reference's own DQN checkpoint (tutorials/pettingzoo/models/DQN/
   lesson1_trained_agent.pt, agilerl 2.2.0) loads into the agx DQN with every
-  tensor, the Adam state and the hyper-parameters as stored (skipped where
-  /root/reference is absent);
+  tensor, the Adam state and the hyper-parameters as stored (the file is kept
+  as tests/golden/ref_dqn_lesson1.pt);
 * the tutorial files written by agilerl < 2.0 (no ``network_info``) are
-  refused with a clear error, not misread;
+  refused with a clear error, not misread (lesson3_trained_agent.pt of the
+  same folder, kept as tests/golden/ref_dqn_lesson3_pre2.pt: the same layout
+  and keys as lesson2 / lesson4, and the one of the three under the 1 MiB
+  limit for a committed file);
 * a file in the reference's layout naming classes of a module that is not
   importable at load time, one of which would run a function when unpickled
   the reference's way, loads with nothing run;
@@ -27,7 +30,9 @@ import numpy as np
 import pytest
 import torch
 
-REF_DQN = "/root/reference/tutorials/pettingzoo/models/DQN"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_DQN_2_2 = os.path.join(GOLDEN, "ref_dqn_lesson1.pt")  # written by agilerl 2.2.0
+REF_DQN_PRE_2_0 = os.path.join(GOLDEN, "ref_dqn_lesson3_pre2.pt")  # written by agilerl < 2.0
 TRIPPED = []
 
 
@@ -84,12 +89,11 @@ def _write_reference_file(path, algo, attrs, modules, optimizer_sd, networks):
         del sys.modules[mod.__name__]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DQN), reason="reference checkpoints not present")
 def test_reference_dqn_checkpoint_loads():
     from agilerl_amd.algorithms import refckpt
     from agilerl_amd.algorithms.dqn import DQN
 
-    path = f"{REF_DQN}/lesson1_trained_agent.pt"
+    path = REF_DQN_2_2
     allow_before = list(torch.serialization.get_safe_globals())
     raw = refckpt.read_reference(path)
     assert set(torch.serialization.get_safe_globals()) == set(allow_before)  # nothing stays allow-listed
@@ -112,12 +116,11 @@ def test_reference_dqn_checkpoint_loads():
         assert float(opt["state"][i]["step"]) == float(s["step"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DQN), reason="reference checkpoints not present")
 def test_pre_2_0_reference_checkpoint_refused():
     from agilerl_amd.algorithms.dqn import DQN
 
     with pytest.raises(ValueError, match="network_info"):
-        DQN.load(f"{REF_DQN}/lesson2_trained_agent.pt", device="cpu")
+        DQN.load(REF_DQN_PRE_2_0, device="cpu")
 
 
 def test_reference_layout_loads_with_nothing_run(tmp_path):

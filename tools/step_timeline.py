@@ -3,8 +3,7 @@ envs, T = 16, one group) from a rocprofv3 kernel trace: per iteration the
 persistent rollout kernel, the GAE / gather kernels and the learner, and the
 device-idle gaps between them (diagnostic):
 
-  rocprofv3 --kernel-trace --output-format csv -d DIR -o st -- python bench.py --steps 20 --warmup 3 \\
-      --no-cpu --no-config5 --no-config3 --no-train-on-policy --no-roofline
+  rocprofv3 --kernel-trace --output-format csv -d DIR -o st -- python bench.py --steps 20 --warmup 3
   python tools/step_timeline.py DIR/.../st_kernel_trace.csv"""
 import csv
 import statistics as S
