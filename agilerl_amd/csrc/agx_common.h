@@ -62,6 +62,48 @@ __device__ __forceinline__ T group_sum(T v) {
     return v;
 }
 
+// ---- lane helpers ------------------------------------------------------------
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+template <int C>
+__device__ __forceinline__ float dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), C, 0xf, 0xf, true));
+}
+// sum / max over the 16 lanes of a DPP row; result in every lane of the row
+__device__ __forceinline__ float row_sum(float v) {
+    v += dpp<0xb1>(v);   // quad_perm [1,0,3,2]
+    v += dpp<0x4e>(v);   // quad_perm [2,3,0,1]
+    v += dpp<0x141>(v);  // row_half_mirror
+    v += dpp<0x140>(v);  // row_mirror
+    return v;
+}
+__device__ __forceinline__ float row_max(float v) {
+    v = fmaxf(v, dpp<0xb1>(v));
+    v = fmaxf(v, dpp<0x4e>(v));
+    v = fmaxf(v, dpp<0x141>(v));
+    v = fmaxf(v, dpp<0x140>(v));
+    return v;
+}
+// v of lane `lane`
+__device__ __forceinline__ float bperm(int lane, float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(lane << 2, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the device's CU count, queried once (runtime.hip)
+int cu_count();
+
+// The gather prologue of both fused PPO learners (defined in learner.hip):
+// permuted, advantage-normalised, minibatch-ordered copy of the rollout.
+__global__ void ppo_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
+                                  const float *__restrict__ old_logp, const float *__restrict__ adv,
+                                  const float *__restrict__ ret, const float *__restrict__ old_v,
+                                  const double *__restrict__ adv_stats, const long long *__restrict__ perms,
+                                  const unsigned char *__restrict__ masks, int A, long long S, int D, int P,
+                                  float *__restrict__ gobs, int *__restrict__ gact, unsigned *__restrict__ gmask,
+                                  float *__restrict__ grow, unsigned *__restrict__ counters, int ncounters,
+                                  const int *__restrict__ epochs_p, unsigned *__restrict__ err);
 
 }  // namespace agx

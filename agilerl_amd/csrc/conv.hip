@@ -39,7 +39,6 @@ namespace conv {
 #define AGX_CONV_BK 16
 #endif
 constexpr int BK = AGX_CONV_BK, NT = 256, kTab = 1024, kTapMax = 16;
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct Shape {
     int B, Cin, H, W, Cout, KH, KW, S, OH, OW;

@@ -74,7 +74,6 @@ constexpr int kMaxPT = 32;        // LDS parameter slots per thread: 8 float4 ch
 constexpr int kMaxA = 16;
 constexpr int kMaxBlk = 28;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 struct NetDims {
@@ -293,25 +292,7 @@ struct Shape {
 // ---------------------------------------------------------------------------
 // cross-lane helpers
 // ---------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ float dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), C, 0xf, 0xf, true));
-}
-// sum / max over the 16 lanes of a DPP row; result in every lane of the row
-__device__ __forceinline__ float row_sum(float v) {
-    v += dpp<0xb1>(v);   // quad_perm [1,0,3,2]
-    v += dpp<0x4e>(v);   // quad_perm [2,3,0,1]
-    v += dpp<0x141>(v);  // row_half_mirror
-    v += dpp<0x140>(v);  // row_mirror
-    return v;
-}
-__device__ __forceinline__ float row_max(float v) {
-    v = fmaxf(v, dpp<0xb1>(v));
-    v = fmaxf(v, dpp<0x4e>(v));
-    v = fmaxf(v, dpp<0x141>(v));
-    v = fmaxf(v, dpp<0x140>(v));
-    return v;
-}
+// (dpp<>, row_sum, row_max: agx_common.h)
 __device__ __forceinline__ float readlane_f(float v, int l) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
@@ -435,8 +416,6 @@ __device__ __forceinline__ void block_sum2(float &a, float &b, float *stat, int 
     a = ta;
     b = tb;
 }
-
-__device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
 
 // C[16x16] += A[16 x K] B[K x 16], K % 4 == 0.  Software-pipelined: the
 // operands of k-batch i+1 (KB k values, KB/2 LDS reads per lane) are issued
@@ -1967,30 +1946,12 @@ __device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resid
     }
     const bool prev = g.st_rew && tid < nrow;
     const size_t idx = (size_t)p * g.N + n0 + tid;
-    float rw = 0.f;
-    unsigned char dn = 0;
-    if (prev) {
-        rw = ld_sys(g.st_rew + idx);
-        dn = ld_sys_u8(g.st_done + idx);
-    }
+    const PrevStep ps = load_prev_step(g, idx, prev);
     if (st && tid == 0) {
         __builtin_amdgcn_s_waitcnt(0);
         st[0] = (long long)__builtin_amdgcn_s_memrealtime() + (long long)(obv[0] != obv[0]);
     }
-    if (prev) {  // reward/done of the previous step -> slot t-1, episode accounting
-        const int env = n0 + tid;
-        g.rew_prev[(size_t)p * g.prev_pstride + env] = rw;
-        g.done_prev[(size_t)p * g.prev_pstride + env] = dn;
-        if (g.scores) {
-            float sc = g.scores[idx] + rw;
-            if (dn) {
-                g.ret_sum[idx] += (double)sc;
-                g.episodes[idx] += 1;
-                sc = 0.f;
-            }
-            g.scores[idx] = sc;
-        }
-    }
+    if (prev) store_prev_step(g, p, n0 + tid, idx, ps);  // -> slot t-1, episode accounting
     if (g.obs_copy) {
         float *oc = g.obs_copy + (size_t)p * g.obs_copy_pstride + (size_t)n0 * pl.D;
 #pragma unroll
@@ -2026,14 +1987,8 @@ __device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resid
     const float H = -row_sum(a < pl.A ? pa * logf(pa + 1e-8f) : 0.f);
     float score = lg;
     if (g.sample) {
-        const unsigned long long env =
-            (g.env_base ? (unsigned long long)g.env_base[p] : (unsigned long long)p * g.N) + n0 + r;
-        const uint4 rnd = philox(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)g.counter,
-                                            (unsigned)(g.counter >> 32) ^ ((unsigned)(a >> 2) << 24)),
-                                 make_uint2((unsigned)g.seed, (unsigned)(g.seed >> 32)));
-        const unsigned w = (a & 3) == 0 ? rnd.x : (a & 3) == 1 ? rnd.y : (a & 3) == 2 ? rnd.z : rnd.w;
-        const float u = ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-        score = a < pl.A ? lg - logf(-logf(u)) : -3.0e38f;                  // Gumbel-max
+        const unsigned long long env = stream_env(-1, g.env_base, p, g.N, n0 + r);
+        score = a < pl.A ? gumbel_score(lg, a, env, g.seed, g.counter) : -3.0e38f;
     }
     const float best = row_max(score);
     const unsigned long long ball = __ballot(score == best);
@@ -2089,30 +2044,7 @@ __global__ __launch_bounds__(kNT, 1) void ppo_rollout_persistent_kernel(const Ac
         if (tid < kArgWords)
             reinterpret_cast<unsigned *>(&s_args)[tid] = reinterpret_cast<const unsigned *>(steps + t)[tid];
         if (tid == 0) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            int go = 1;
-            for (;;) {
-                // relaxed: an acquire at system scope would invalidate the
-                // caches on every poll; one invalidate follows the wait
-                const unsigned v = __hip_atomic_load(rel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (v == AGX_ROLLOUT_ABORT) {  // host exception: the rollout is partial
-                    go = 0;
-                    __hip_atomic_store(&ctl->timeout, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                if (v == AGX_ROLLOUT_STOP) {  // clean early end (an evaluation whose episodes all finished)
-                    go = 0;
-                    break;
-                }
-                if (v >= base + (unsigned)(t + 1)) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > timeout_ticks) {
-                    go = 0;
-                    __hip_atomic_store(&ctl->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-            s_go = go;
+            s_go = wait_release(rel, ctl, base, t, timeout_ticks);
             if (st) st[1] = (long long)__builtin_amdgcn_s_memrealtime();
             if (stamps && t == 5 && blk < 64) stamps[256 + blk] = (long long)__builtin_amdgcn_s_memrealtime();
         }
@@ -2120,16 +2052,10 @@ __global__ __launch_bounds__(kNT, 1) void ppo_rollout_persistent_kernel(const Ac
         if (!s_go) return;
         const ActArgs g = s_args;
         act_body<C>(g, sm, t > 0 && pl.param_end > 0, st ? st + 2 : nullptr);
-        // the host-memory stores (actions) are system-scope write-through;
-        // wait for their acknowledgements (no L2 write-back: a release fence
-        // would flush every dirty L2 line per wave)
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
+        step_stores_acked();
         if (st && tid == 0) st[5] = (long long)__builtin_amdgcn_s_memrealtime();
         if (stamps && tid == 0 && t == 5 && blk < 64) stamps[320 + blk] = (long long)__builtin_amdgcn_s_memrealtime();
-        if (tid == 0)
-            __hip_atomic_store(rollout_done_words(ctl) + blk, base + (unsigned)(t + 1), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_done(ctl, blk, base, t);
     }
 }
 
@@ -2282,18 +2208,6 @@ extern "C" size_t agx_ppo_learn_lds_bytes(const agx_ppo_net *net) {
 
 // Workgroups per agent: the learner spreads an agent's sub-batches over up to
 // kMaxK = 16 partner workgroups (one CU each) when the population leaves CUs idle.
-static int cu_count() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                ? prop.multiProcessorCount
-                : 256;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
 // Partner workgroups per agent: all partners must be co-resident (1 block per
 // CU), so K <= CUs / P; AGX_LEARN_SPLIT lowers the cap (tests, diagnostics).
 static int max_partners(int64_t P) {
@@ -2477,37 +2391,9 @@ extern "C" int agx_ppo_act(const agx_ppo_net *net, int64_t P, int64_t N, const f
         set_error("agx_ppo_act: network shape not instantiated");
         return AGX_EUNSUPPORTED;
     }
-    ActArgs a;
-    a.params = params;
-    a.obs = obs;
-    a.obs_pstride = obs_agent_stride;
-    a.N = (int)N;
-    a.P = (int)P;
-    a.sample = sample;
-    a.seed = seed;
-    a.counter = counter;
-    a.act_out = reinterpret_cast<long long *>(actions);
-    a.logp_out = log_probs;
-    a.value_out = values;
-    a.ent_out = entropy;
-    a.out_pstride = out_agent_stride;
-    a.act_flat = reinterpret_cast<long long *>(actions_flat);
-    a.act = 1;
-    a.obs_copy = nullptr;
-    a.obs_copy_pstride = 0;
-    a.st_rew = nullptr;
-    a.st_done = nullptr;
-    a.rew_prev = nullptr;
-    a.done_prev = nullptr;
-    a.prev_pstride = 0;
-    a.scores = nullptr;
-    a.ret_sum = nullptr;
-    a.episodes = nullptr;
-    a.mask = action_mask;
-    a.mask_pstride = mask_agent_stride;
-    a.mask_copy = nullptr;
-    a.mask_copy_pstride = 0;
-    a.env_base = reinterpret_cast<const long long *>(agent_env_base);
+    const ActArgs a = act_step_args(P, N, params, obs, obs_agent_stride, action_mask, mask_agent_stride, sample, seed,
+                                    counter, actions, log_probs, values, entropy, out_agent_stride, actions_flat,
+                                    agent_env_base);
     dim3 grid((unsigned)ceil_div(N, kSB), (unsigned)P);
     L.act(a, grid, (size_t)L.plan->act_floats * sizeof(float), as_stream(stream));
     return check_launch("agx_ppo_act");
@@ -2523,7 +2409,7 @@ extern "C" int agx_ppo_rollout_step(const agx_ppo_net *net, int64_t P, int64_t N
         set_error("agx_ppo_rollout_step: network shape not instantiated");
         return AGX_EUNSUPPORTED;
     }
-    ActArgs a;
+    ActArgs a{};
     fill_rollout_args(a, L.plan->D, L.plan->A, P, N, params, io, act, sample, seed, counter);
     dim3 grid((unsigned)ceil_div(N, kSB), (unsigned)P);
     L.act(a, grid, (size_t)L.plan->act_floats * sizeof(float), as_stream(stream));
@@ -2563,11 +2449,9 @@ extern "C" int agx_ppo_eval_persistent(const agx_ppo_net *net, int64_t P, int64_
                                        const int64_t *agent_env_base, int64_t nsteps, uint32_t base, uint64_t seed,
                                        uint64_t counter0, void *args_host, agx_rollout_ctl *ctl, double timeout_s,
                                        void *stream) {
-    AGX_REQUIRE(net && params && stage_obs && actions_flat && args_host && ctl && P > 0 && N > 0 && P <= 65535 &&
-                    nsteps >= 1,
-                "agx_ppo_eval_persistent: bad arguments");
-    AGX_REQUIRE((uint64_t)base + (uint64_t)nsteps < AGX_ROLLOUT_STOP, "agx_ppo_eval_persistent: base wraps");
-    AGX_REQUIRE(timeout_s > 0 && timeout_s < 3600, "agx_ppo_eval_persistent: timeout_s out of range");
+    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl, P, N, nsteps, base,
+                                  timeout_s, "agx_ppo_eval_persistent"))
+        return rc;
     Launcher L;
     if (!find_launcher(net, L)) {
         set_error("agx_ppo_eval_persistent: network shape not instantiated");
@@ -2576,24 +2460,10 @@ extern "C" int agx_ppo_eval_persistent(const agx_ppo_net *net, int64_t P, int64_
     if (int rc = persistent_fits(L, P, N, "agx_ppo_eval_persistent")) return rc;
     const LearnPlan &pl = *L.plan;
     ActArgs *steps = static_cast<ActArgs *>(args_host);
-    for (int64_t t = 0; t < nsteps; ++t) {
-        ActArgs a{};
-        a.params = params;
-        a.obs = stage_obs;
-        a.obs_pstride = N * (int64_t)pl.D;
-        a.N = (int)N;
-        a.P = (int)P;
-        a.sample = 1;
-        a.seed = seed;
-        a.counter = counter0 + (uint64_t)t;
-        a.act_flat = reinterpret_cast<long long *>(actions_flat);
-        a.act = 1;
-        a.mask = stage_mask;
-        a.mask_pstride = N * (int64_t)pl.A;
-        a.env_base = reinterpret_cast<const long long *>(agent_env_base);
-        steps[t] = a;
-    }
-    const unsigned long long ticks = (unsigned long long)(timeout_s * 1e8);  // s_memrealtime: 100 MHz
+    for (int64_t t = 0; t < nsteps; ++t)
+        steps[t] = eval_step_args(pl.D, pl.A, P, N, params, stage_obs, stage_mask, actions_flat, agent_env_base, seed,
+                                  counter0 + (uint64_t)t);
+    const unsigned long long ticks = seconds_to_ticks(timeout_s);
     ctl->nwg = (uint32_t)agx_rollout_workgroups(P, N);
     dim3 grid((unsigned)ceil_div(N, kSB), (unsigned)P);
     L.persist(steps, (int)nsteps, ctl, ticks, base, nullptr, grid, (size_t)pl.act_floats * sizeof(float),
@@ -2605,10 +2475,9 @@ extern "C" int agx_ppo_rollout_persistent(const agx_ppo_net *net, int64_t P, int
                                           const agx_rollout_io *ios, int64_t nsteps, uint32_t base, uint64_t seed,
                                           uint64_t counter0, void *args_host, agx_rollout_ctl *ctl,
                                           double timeout_s, void *stream) {
-    AGX_REQUIRE(net && ios && params && args_host && ctl && P > 0 && N > 0 && P <= 65535 && nsteps >= 1,
-                "agx_ppo_rollout_persistent: bad arguments");
-    AGX_REQUIRE((uint64_t)base + (uint64_t)nsteps < AGX_ROLLOUT_STOP, "agx_ppo_rollout_persistent: base wraps");
-    AGX_REQUIRE(timeout_s > 0 && timeout_s < 3600, "agx_ppo_rollout_persistent: timeout_s out of range");
+    if (int rc = check_persistent(net && ios && params && args_host && ctl, P, N, nsteps, base, timeout_s,
+                                  "agx_ppo_rollout_persistent"))
+        return rc;
     Launcher L;
     if (!find_launcher(net, L)) {
         set_error("agx_ppo_rollout_persistent: network shape not instantiated");
@@ -2622,7 +2491,7 @@ extern "C" int agx_ppo_rollout_persistent(const agx_ppo_net *net, int64_t P, int
         fill_rollout_args(steps[t], L.plan->D, L.plan->A, P, N, params, ios + t, 1, last ? 0 : 1, seed,
                           last ? 0 : counter0 + 1 + (uint64_t)t);
     }
-    const unsigned long long ticks = (unsigned long long)(timeout_s * 1e8);  // s_memrealtime: 100 MHz
+    const unsigned long long ticks = seconds_to_ticks(timeout_s);
     ctl->nwg = (uint32_t)agx_rollout_workgroups(P, N);
     dim3 grid((unsigned)ceil_div(N, kSB), (unsigned)P);
     L.persist(steps, (int)nsteps, ctl, ticks, base, g_roll_stamps_ptr(), grid, (size_t)L.plan->act_floats * sizeof(float),

@@ -28,7 +28,6 @@ constexpr int kOptPer = 4;  // params per thread per block
 constexpr int kOptChunk = kOptBlock * kOptPer;
 constexpr int kSumChunk = kOptBlock * 4 * 8;  // sum-of-squares block: 8 float4 per thread
 constexpr int kMaxGroups = 8;
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct Groups {
     int64_t off[kMaxGroups + 1];

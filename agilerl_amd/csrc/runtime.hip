@@ -40,6 +40,21 @@ extern "C" int agx_device_info(int *out3) {
     return AGX_OK;
 }
 
+// The co-residency limits of the partnered learners and the persistent
+// launches are CUs x occupancy; 256 when the query fails.
+int agx::cu_count() {
+    static int n = 0;
+    if (!n) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+                ? prop.multiProcessorCount
+                : 256;
+        if (n <= 0) n = 256;
+    }
+    return n;
+}
+
 // STREAM-style kernels used by bench.py to measure the box's achievable HBM
 // bandwidth (the roofline's "measured peak"): 16 B per lane, each block moves
 // one contiguous 16 KiB tile per pass (4 loads in flight per lane).

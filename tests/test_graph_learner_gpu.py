@@ -197,6 +197,53 @@ def test_graph_policy_step_matches_torch_forward(shape):
     torch.testing.assert_close(ent, -(pa * torch.log(pa + 1e-8)).sum(-1), rtol=1e-4, atol=1e-5)
 
 
+def test_graph_policy_step_twenty_masked_actions():
+    """More than 16 actions: each lane of graph_sample holds a second action
+    (16..31).  Two row blocks of 16 (the second partial), a legal-action mask.
+    Greedy: the argmax of the masked torch logits on every row whose top-two
+    gap is at least 1e-4 (all 40 rows with these CPU-drawn parameters and
+    inputs: the smallest gap is 3.2e-4, and 18 of the 40 argmaxes are >= 16),
+    log-prob / value / entropy as the test above.  Sampled: legal actions,
+    a function of the counter."""
+    from agilerl_amd.population.learner import policy_step_graph
+
+    P, N, A = 2, 20, 20
+    pop = _pop("latent_56", P=P, N=N, A=A)
+    g = torch.Generator().manual_seed(1)  # CPU stream: the rows the gap excludes do not depend on the device
+    obs = torch.randn(P, N, 8, generator=g).to(DEV)
+    mask = (torch.rand(P, N, A, generator=g) < 0.7).to(torch.uint8)
+    mask[..., 0] = 1
+    mask = mask.to(DEV)
+    act = torch.empty(P, N, dtype=torch.int64, device=DEV)
+    lp, v, ent = (torch.empty(P, N, device=DEV) for _ in range(3))
+
+    def step(sample, counter, **out):
+        policy_step_graph(pop, pop.learn_descriptor(), obs, N * 8, sample=sample, counter=counter, actions=act,
+                          out_agent_stride=N, action_mask=mask, mask_agent_stride=N * A, **out)
+        return act.clone()
+
+    greedy = step(False, 0, log_probs=lp, values=v, entropy=ent)
+    logits, value = pop.spec.forward(pop.params.data, obs)
+    logits = torch.where(mask.bool(), logits, torch.full_like(logits, -1.0e8))
+    top2 = logits.topk(2, -1).values
+    clear = (top2[..., 0] - top2[..., 1]) >= 1e-4
+    assert clear.float().mean().item() >= 0.95
+    assert torch.equal(greedy[clear], logits.argmax(-1)[clear])
+    assert (greedy >= 16).any()
+    logp_all = torch.log_softmax(logits, -1)
+    torch.testing.assert_close(lp, logp_all.gather(-1, greedy.unsqueeze(-1)).squeeze(-1), rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(v, value.view(P, N), rtol=1e-4, atol=1e-5)
+    pa = logp_all.exp()
+    torch.testing.assert_close(ent, -(pa * torch.log(pa + 1e-8)).sum(-1), rtol=1e-4, atol=1e-5)
+
+    sampled = [step(True, c) for c in range(1, 6)]
+    for a in sampled:
+        assert bool(mask.gather(-1, a.unsqueeze(-1)).all())
+    for c in range(1, 6):
+        assert torch.equal(step(True, c), sampled[c - 1])
+    assert any(not torch.equal(sampled[0], a) for a in sampled[1:])
+
+
 def test_graph_policy_step_samples_the_fused_stream():
     """On a compiled shape both policy steps draw from the same Philox stream:
     the sampled actions agree (up to logits within rounding of a tie)."""
