@@ -89,6 +89,10 @@ SIGNATURES = {
     "agx_td_workspace_bytes": (_SZ, [_I]),
     "agx_td_target": (_INT, [_P] * 6 + [_I, _I, _D, _INT, _P, _P, _P, _P, _P]),
     "agx_maddpg_critic_target": (_INT, [_P] * 4 + [_I, _D, _P, _P, _P, _P, _P]),
+    # include/agx_td3.h: TD3 / DDPG target smoothing and twin-critic target
+    "agx_td3_smooth_actions": (_INT, [_P] * 4 + [_I, _I, _D, _P, _P]),
+    "agx_td3_workspace_bytes": (_SZ, [_I]),
+    "agx_td3_critic_target": (_INT, [_P] * 6 + [_I, _D] + [_P] * 6),
     "agx_c51_project_loss": (_INT, [_P] * 7 + [_I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_c51_project_loss_rows": (_INT, [_P] * 5 + [_I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_adam_workspace_bytes": (_SZ, [_I, _I]),

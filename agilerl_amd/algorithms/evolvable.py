@@ -1,6 +1,6 @@
 """The EvolvableAlgorithm hooks the reference's Mutations call
 (agilerl/algorithms/core/base.py:744-775, hpo/mutation.py:413-453, 515-570)
-for the object-level agents (DQN, RainbowDQN, MADDPG):
+for the object-level agents (DQN, RainbowDQN, DDPG, TD3, MADDPG):
 
 * ``registry``            the agent's HyperparameterConfig (hpo/registry.py);
 * ``get_lr_names``        the attributes that are learning rates;

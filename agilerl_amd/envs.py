@@ -69,16 +69,20 @@ class SyntheticVecEnv:
     """``num_envs`` independent synthetic episodes; data drawn from a ring of
     pre-generated batches (``ring`` steps) so a step is a memcpy.
     ``max_episode_steps`` truncates episodes like gymnasium's TimeLimit
-    (LunarLander: 1000); None never truncates (the bench's default)."""
+    (LunarLander: 1000); None never truncates (the bench's default).
+    ``action_dim`` (None: the Discrete env) makes it a continuous-control
+    stand-in: actions are ``Box(action_low, action_high, (action_dim,))``."""
 
     #: the step never touches the GPU (PopulationRunner may pace a persistent rollout)
     agx_device_free = True
 
     def __init__(self, num_envs: int, obs_dim: int = 8, n_actions: int = 4, p_done: float = 1 / 200,
-                 seed: int = 0, ring: int = 97, max_episode_steps: int | None = None):
+                 seed: int = 0, ring: int = 97, max_episode_steps: int | None = None, action_dim: int | None = None,
+                 action_low: float = -1.0, action_high: float = 1.0):
         self.num_envs = int(num_envs)
         self.single_observation_space = Box(-np.inf, np.inf, (obs_dim,))
-        self.single_action_space = Discrete(n_actions)
+        self.single_action_space = Discrete(n_actions) if action_dim is None else \
+            Box(action_low, action_high, (int(action_dim),))
         self.observation_space = self.single_observation_space
         self.action_space = self.single_action_space
         self._obs_dim, self._p_done, self._ring, self.seed = obs_dim, p_done, ring, seed

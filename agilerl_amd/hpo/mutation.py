@@ -47,6 +47,13 @@ What runs, with the reference's draws from the reference's generators:
   to the Q network with the network's generator, the target network re-made
   from it, fresh optimizers (modules/cnn.py bit-exact per method).
 
+* ``architecture_mutate`` on DDPG / TD3: _architecture_mutate_single
+  (:829-885) in algorithms/ddpg.py — the method from the actor's table applied
+  to the actor, the applied method with its mutation dict to every critic
+  that has it, every target re-made, fresh optimizers; RL-hyperparameter
+  mutations of ``lr_actor`` / ``lr_critic`` re-make the actor's / every
+  critic's optimizer.
+
 * ``architecture_mutate`` on MADDPG (config 4): _architecture_mutate_multi
   (:887-1011) in algorithms/maddpg.py — the actors' ModuleDict table, the
   applied method on every actor that has it, the analogous method on every
@@ -152,6 +159,7 @@ class Mutations:
         mutation_hook and a fresh optimizer; CNN-encoder PPO agents:
         population/image_arch.py; DQN / Rainbow with MLP or CNN encoders:
         algorithms/evolvable.py, the target re-made from the mutated network;
+        DDPG / TD3: algorithms/ddpg.py, the applied method on every critic;
         MADDPG: _architecture_mutate_multi in algorithms/maddpg.py).  Sharded
         object-level populations: not applied."""
         fn = getattr(individual, "architecture_mutation", None)

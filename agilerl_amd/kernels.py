@@ -254,6 +254,52 @@ def maddpg_critic_target(q, q_next, rewards, dones, gamma):
     return y, g_q, loss
 
 
+def td3_smooth_actions(mu, noise, low, high, noise_clip, out=None):
+    """Target-policy smoothing (td3.py:493-501, ddpg.py:448-456) in one
+    launch: max(min(mu + clamp(noise, -c, c), high), low) with per-dimension
+    bounds [A].  -> out [B, A] (``out`` may be ``mu`` itself)."""
+    _need(mu, "mu", _f32)
+    if mu.dim() != 2:
+        raise ValueError(f"mu: expected [B, A], got {tuple(mu.shape)}")
+    B, A = mu.shape
+    _need(noise, "noise", _f32, (B, A))
+    _need(low, "low", _f32, (A,))
+    _need(high, "high", _f32, (A,))
+    if out is None:
+        out = torch.empty_like(mu)
+    _need(out, "out", _f32, (B, A))
+    _lib.call("agx_td3_smooth_actions", mu.data_ptr(), noise.data_ptr(), low.data_ptr(), high.data_ptr(), B, A,
+              float(noise_clip), out.data_ptr(), _lib.stream())
+    return out
+
+
+def td3_critic_target(q1, qn1, rewards, dones, gamma, q2=None, qn2=None):
+    """-> (y (B,1), dloss/dq1 (B,1), dloss/dq2 (B,1) | None, loss (1,)) of
+    TD3.learn's critic step (td3.py:503-515: y from the smaller target
+    critic, the sum of the two MSE losses), or DDPG's with one critic
+    (ddpg.py:457-461), in one launch (+ the fixed-order loss sums)."""
+    if (q2 is None) != (qn2 is None):
+        raise ValueError("q2 and qn2 go together (both None: the single-critic form)")
+    B = q1.shape[0]
+    q1f, qn1f, r, d = (t.reshape(-1) for t in (q1, qn1, rewards, dones))
+    named = [(q1f, "q1"), (qn1f, "qn1"), (r, "rewards"), (d, "dones")]
+    q2f = qn2f = None
+    if q2 is not None:
+        q2f, qn2f = q2.reshape(-1), qn2.reshape(-1)
+        named += [(q2f, "q2"), (qn2f, "qn2")]
+    for t, name in named:
+        _need(t, name, _f32, (B,))
+    y = torch.empty(B, 1, dtype=_f32, device=r.device)
+    g_q1 = torch.empty(B, 1, dtype=_f32, device=r.device)
+    g_q2 = torch.empty(B, 1, dtype=_f32, device=r.device) if q2 is not None else None
+    loss = torch.empty(1, dtype=_f32, device=r.device)
+    ws = _ws(_lib.load().agx_td3_workspace_bytes(B), r.device)
+    _lib.call("agx_td3_critic_target", q1f.data_ptr(), _lib.ptr(q2f), qn1f.data_ptr(), _lib.ptr(qn2f), r.data_ptr(),
+              d.data_ptr(), B, float(gamma), y.data_ptr(), g_q1.data_ptr(), _lib.ptr(g_q2), loss.data_ptr(),
+              ws.data_ptr(), _lib.stream())
+    return y, g_q1, g_q2, loss
+
+
 def c51_project_loss(q_next_online, target_dist, logp_cur, actions, rewards, dones, support, v_min,
                      v_max, gamma, with_proj=False):
     B, A, Z = target_dist.shape

@@ -1,9 +1,12 @@
 """Drop-in ``train_off_policy`` (agilerl/training/train_off_policy.py:41-616)
-for DQN / RainbowDQN populations on the agx HBM replay buffers.
+for DQN / RainbowDQN / DDPG / TD3 populations on the agx HBM replay buffers.
 
 The loop mirrors the reference: agents in turn collect ``evo_steps`` from the
-shared env with epsilon-greedy (DQN, epsilon decayed per step) or noisy-net
-(Rainbow) actions into the SHARED memory (one replay for the population,
+shared env with epsilon-greedy (DQN, epsilon decayed per step), noisy-net
+(Rainbow) or noise-perturbed deterministic (DDPG / TD3: the env gets the
+action rescaled to its bounds, the memory the raw [-1, 1] network output,
+and the exploration noise of every finished env is reset, :276-325) actions
+into the SHARED memory (one replay for the population,
 train_off_policy.py:249, 340-345), learn every ``learn_step`` env steps once
 ``len(memory) >= batch_size`` and ``memory.size > learning_delay`` (PER:
 sample with the agent's annealed beta, update priorities; n-step: the
@@ -26,11 +29,15 @@ order (hpo/shard.py), each rank keeping its slice."""
 from __future__ import annotations
 
 import numpy as np
+import torch
 
+from ..algorithms.ddpg import DDPG
 from ..algorithms.dqn import DQN, RainbowDQN
+from ..algorithms.td3 import TD3
 from ..components.sampler import Sampler
 from ..hpo.shard import all_gather_obj, all_ranks, mutate_population, sync_host_rngs, world_rank
 from ..hpo.sharded import select_population
+from ..networks.actors import DeterministicActor
 
 
 def train_off_policy(env, env_name: str, algo: str, pop, memory, INIT_HP=None, MUT_P=None,
@@ -74,15 +81,27 @@ def train_off_policy(env, env_name: str, algo: str, pop, memory, INIT_HP=None, M
                     epsilon = max(eps_end, epsilon * eps_decay)
                 elif isinstance(agent, RainbowDQN):
                     action = agent.get_action(obs)
+                elif isinstance(agent, (DDPG, TD3)):
+                    raw_action = agent.get_action(obs)
+                    action = DeterministicActor.rescale_action(torch.from_numpy(raw_action), agent.action_low,
+                                                               agent.action_high,
+                                                               agent.actor.output_activation).numpy()
                 else:
                     raise NotImplementedError(f"{type(agent).__name__} is outside the agx off-policy path")
                 next_obs, reward, done, trunc, info = env.step(action)
                 scores += np.asarray(reward)
+                finished = []
                 for i, (d, t) in enumerate(zip(np.atleast_1d(done), np.atleast_1d(trunc))):
                     if d or t:
                         agent.scores.append(scores[i])
                         scores[i] = 0
-                transition = {"obs": obs, "action": np.asarray(action).reshape(num_envs, 1),
+                        finished.append(i)
+                if isinstance(agent, (DDPG, TD3)):
+                    agent.reset_action_noise(finished)
+                    stored = np.asarray(raw_action, dtype=np.float32).reshape(num_envs, agent.action_dim)
+                else:
+                    stored = np.asarray(action).reshape(num_envs, 1)
+                transition = {"obs": obs, "action": stored,
                               "reward": np.asarray(reward, dtype=np.float32).reshape(num_envs, 1),
                               "next_obs": next_obs,
                               "done": np.asarray(done, dtype=np.float32).reshape(num_envs, 1)}

@@ -13,7 +13,9 @@ seeds and sampling streams), so the same script trains the same population
 on 1 or G GPUs.  Object-level agents (DQN / Rainbow / MADDPG) are built for
 the whole population in order and the slice is kept, which leaves the
 torch generators where the unsharded build leaves them.  ``shard=False``
-keeps ``population_size`` agents per rank."""
+keeps ``population_size`` agents per rank.  DDPG / TD3 populations
+(``vect_noise_dim = num_envs``; ``SHARE_ENCODERS`` defaults to False, the
+reference's True being outside this path) are single-process only."""
 
 from __future__ import annotations
 
@@ -88,7 +90,19 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         for a in agents:
             a.sharded = bool(shard and world > 1)
         return agents[lo:lo + P]
-    raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, MADDPG)")
+    if algo in ("DDPG", "TD3"):  # utils/utils.py:466-493, 560-587
+        from ..algorithms import DDPG, TD3
+
+        if actor_network is not None or critic_network is not None:
+            raise NotImplementedError("custom actor/critic modules: use net_config (MLP) networks")
+        if world > 1:
+            raise NotImplementedError(f"{algo} populations under a process group of {world} ranks: the off-policy "
+                                      "loop treats every multi-rank run as one sharded population")
+        cls = DDPG if algo == "DDPG" else TD3
+        return [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, num_envs=num_envs,
+                                 device=device, hp_config=hp_config, **algo_kwargs) for i in range(P)]
+    raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, MADDPG, "
+                              "DDPG, TD3)")
 
 
 __all__ = ["create_population"]

@@ -1,0 +1,270 @@
+"""DDPG / TD3 on the GPU: agx_td3_smooth_actions and agx_td3_critic_target
+against the reference's own outputs (tests/golden/td3_*.npz, ddpg_*.npz) and
+against the plain-torch twin (tests/td3_twin.py), TD3.learn / DDPG.learn
+against the twin's update on copies of the same networks, and the drop-in
+trainer with tournament, mutations, checkpoints and clones."""
+
+import numpy as np
+import pytest
+import torch
+
+from tests import td3_twin
+
+pytestmark = pytest.mark.gpu
+
+TD3_CASES = ["td3_0", "td3_1", "td3_2"]
+DDPG_CASES = ["ddpg_0", "ddpg_1"]
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+# ---- agx_td3_smooth_actions ----------------------------------------------------
+@pytest.mark.parametrize("case", TD3_CASES + DDPG_CASES)
+def test_smooth_actions_matches_reference_golden(golden, case):
+    from agilerl_amd import kernels as K
+
+    g = golden(case)
+    out = K.td3_smooth_actions(_dev(g["mu"]), _dev(g["noise"]), _dev(g["low"]), _dev(g["high"]),
+                               float(g["noise_clip"]))
+    np.testing.assert_array_equal(out.cpu().numpy(), g["next_actions"])
+
+
+@pytest.mark.parametrize("B,A", [(1, 1), (77, 3), (257, 6), (4096, 17)])
+def test_smooth_actions_matches_torch_ops(B, A):
+    """Bit for bit, NaNs and an unbounded dimension included, writing over mu."""
+    from agilerl_amd import kernels as K
+
+    gen = torch.Generator().manual_seed(B * 31 + A)
+    mu = torch.tanh(torch.randn(B, A, generator=gen)) * 1.3
+    noise = torch.randn(B, A, generator=gen) * 0.4
+    low = -1.0 + 0.05 * torch.arange(A, dtype=torch.float32)
+    high = 0.9 - 0.03 * torch.arange(A, dtype=torch.float32)
+    high[A - 1] = float("inf")
+    if A > 2:
+        low[1] = -float("inf")
+    if B > 2:
+        mu[1, 0] = float("nan")
+        noise[2, A - 1] = float("nan")
+    want = td3_twin.smooth(mu, noise, low, high, 0.5)
+    mu_d = mu.cuda()
+    out = K.td3_smooth_actions(mu_d, noise.cuda(), low.cuda(), high.cuda(), 0.5, out=mu_d)
+    assert out.data_ptr() == mu_d.data_ptr()
+    np.testing.assert_array_equal(out.cpu().numpy(), want.numpy())
+    # and against the same three ops on the device
+    dev = td3_twin.smooth(mu.cuda(), noise.cuda(), low.cuda(), high.cuda(), 0.5)
+    np.testing.assert_array_equal(out.cpu().numpy(), dev.cpu().numpy())
+
+
+# ---- agx_td3_critic_target -------------------------------------------------------
+@pytest.mark.parametrize("case", TD3_CASES + DDPG_CASES)
+def test_critic_target_matches_reference_golden(golden, case):
+    """y bit for bit, dL/dQ and the loss to f32 rounding of the mean (the
+    bounds agx_maddpg_critic_target is held to)."""
+    from agilerl_amd import kernels as K
+
+    g = golden(case)
+    twin = "q2" in g
+    flat = lambda k: _dev(g[k].reshape(-1))  # noqa: E731
+    y, g1, g2, loss = K.td3_critic_target(flat("q1"), flat("qn1"), flat("r"), flat("d"), float(g["gamma"]),
+                                          q2=flat("q2") if twin else None, qn2=flat("qn2") if twin else None)
+    np.testing.assert_array_equal(y.cpu().numpy().reshape(-1), g["y"].reshape(-1))
+    np.testing.assert_allclose(g1.cpu().numpy().reshape(-1), g["g_q1"].reshape(-1), rtol=1e-6, atol=1e-9)
+    if twin:
+        np.testing.assert_allclose(g2.cpu().numpy().reshape(-1), g["g_q2"].reshape(-1), rtol=1e-6, atol=1e-9)
+    else:
+        assert g2 is None
+    assert abs(float(loss) - float(g["critic_loss"])) <= 1e-6 * abs(float(g["critic_loss"]))
+
+
+def _critic_inputs(B, twin):
+    gen = torch.Generator().manual_seed(B + (7 if twin else 0))
+    f = lambda: torch.randn(B, 1, generator=gen)  # noqa: E731
+    q = [f() for _ in range(2 if twin else 1)]
+    qn = [f() for _ in range(2 if twin else 1)]
+    if twin:
+        qn[1][::3] = qn[0][::3]  # rows with qn1 == qn2
+    r = f()
+    d = (torch.rand(B, 1, generator=gen) < 0.3).float()
+    d[0] = 1.0
+    return q, qn, r, d
+
+
+@pytest.mark.parametrize("twin", [True, False])
+@pytest.mark.parametrize("B", [1, 77, 257, 4096])
+def test_critic_target_matches_twin_formula(B, twin):
+    from agilerl_amd import _lib
+    from agilerl_amd import kernels as K
+
+    gamma = 0.97
+    q, qn, r, d = _critic_inputs(B, twin)
+    qg = [x.clone().requires_grad_() for x in q]
+    y_want, loss_want = td3_twin.critic_target(qg, qn, r, d, gamma)
+    loss_want.backward()
+    c = lambda x: x.reshape(-1).cuda()  # noqa: E731
+    y, g1, g2, loss = K.td3_critic_target(c(q[0]), c(qn[0]), c(r), c(d), gamma, q2=c(q[1]) if twin else None,
+                                          qn2=c(qn[1]) if twin else None)
+    np.testing.assert_array_equal(y.cpu().numpy(), y_want.detach().numpy())
+    np.testing.assert_allclose(g1.cpu().numpy(), qg[0].grad.numpy(), rtol=1e-6, atol=1e-9)
+    if twin:
+        np.testing.assert_allclose(g2.cpu().numpy(), qg[1].grad.numpy(), rtol=1e-6, atol=1e-9)
+    loss_want = loss_want.item()
+    assert abs(float(loss) - loss_want) <= 1e-6 * abs(loss_want)
+
+    # the optional outputs: y only, then the gradients without y
+    lib = _lib.load()
+    dq = [c(x) for x in q] + [None] * (2 - len(q))
+    dqn = [c(x) for x in qn] + [None] * (2 - len(qn))
+    dr, dd = c(r), c(d)
+    ws = torch.empty(max(16, lib.agx_td3_workspace_bytes(B)), dtype=torch.uint8, device="cuda")
+
+    def call(y_out, g1_out, g2_out):
+        out = torch.full((1,), float("nan"), device="cuda")
+        _lib.call("agx_td3_critic_target", dq[0].data_ptr(), _lib.ptr(dq[1]), dqn[0].data_ptr(), _lib.ptr(dqn[1]),
+                  dr.data_ptr(), dd.data_ptr(), B, gamma, _lib.ptr(y_out), _lib.ptr(g1_out), _lib.ptr(g2_out),
+                  out.data_ptr(), ws.data_ptr(), _lib.stream())
+        return out
+
+    y_only = torch.empty(B, device="cuda")
+    assert torch.equal(call(y_only, None, None), loss)
+    assert torch.equal(y_only, y.reshape(-1))
+    g1_only = torch.empty(B, device="cuda")
+    g2_only = torch.empty(B, device="cuda") if twin else None
+    assert torch.equal(call(None, g1_only, g2_only), loss)
+    assert torch.equal(g1_only, g1.reshape(-1))
+    if twin:
+        assert torch.equal(g2_only, g2.reshape(-1))
+
+
+# ---- learn against the twin ---------------------------------------------------------
+def _env(num_envs=8):
+    from agilerl_amd.envs import SyntheticVecEnv
+
+    # episodes that end: an env of the default ring may never terminate, and evaluation waits for every env
+    return SyntheticVecEnv(num_envs, action_dim=3, action_low=-2.0, action_high=0.5, seed=3, p_done=0.05,
+                           max_episode_steps=60)
+
+
+def _fill(memory, env, agent, steps):
+    obs, _ = env.reset()
+    for _ in range(steps):
+        raw = agent.get_action(obs)
+        nxt, rew, term, trunc, _ = env.step(raw)
+        memory.add({"obs": obs, "action": raw.astype(np.float32),
+                    "reward": np.asarray(rew, dtype=np.float32).reshape(-1, 1), "next_obs": nxt,
+                    "done": np.asarray(term, dtype=np.float32).reshape(-1, 1)})
+        obs = nxt
+
+
+@pytest.mark.parametrize("algo", ["TD3", "DDPG"])
+def test_learn_matches_twin(algo):
+    from agilerl_amd import algorithms
+    from agilerl_amd.components import ReplayBuffer
+
+    env = _env()
+    torch.manual_seed(0)
+    np.random.seed(0)
+    agent = getattr(algorithms, algo)(env.single_observation_space, env.single_action_space, vect_noise_dim=8,
+                                      batch_size=32, policy_freq=2, lr_actor=1e-3, lr_critic=1e-3, tau=0.01)
+    twin = td3_twin.Twin.of(agent)
+    memory = ReplayBuffer(512)
+    _fill(memory, env, agent, 20)
+    memory.storage["done"][::5] = 1.0
+    for k in range(4):
+        torch.manual_seed(100 + k)
+        experiences = memory.sample(32)
+        kept = experiences["action"].clone()
+        torch.manual_seed(k)
+        actor_loss, critic_loss = agent.learn(experiences)
+        assert torch.equal(experiences["action"], kept)  # the reference overwrites it with the noise
+        torch.manual_seed(k)
+        twin_actor_loss, twin_critic_loss = twin.learn(experiences)
+        assert (actor_loss is None) == (k in (0, 2)) and (twin_actor_loss is None) == (actor_loss is None)
+        assert np.isfinite(critic_loss) and abs(critic_loss - twin_critic_loss) <= 1e-4 * abs(twin_critic_loss) + 2e-5
+    mine = [getattr(agent, n) for t in agent._triples() for n in t[:2]]
+    theirs = [twin.actor, twin.actor_target]
+    for critic, target in zip(twin.critics, twin.critic_targets):
+        theirs += [critic, target]
+    assert len(mine) == len(theirs) == (6 if algo == "TD3" else 4)
+    for net, ref in zip(mine, theirs):
+        for p1, p2 in zip(net.parameters(), ref.parameters()):
+            torch.testing.assert_close(p1, p2, rtol=1e-4, atol=2e-5)
+    # the flat-state views stay the torch optimizers' truth: critics stepped 4 times, the actor twice
+    for (_, _, opt), want in zip(agent._triples(), [2.0] + [4.0] * len(twin.critics)):
+        steps = {float(s["step"]) for s in getattr(agent, opt).state_dict()["state"].values()}
+        assert steps == {want}
+    assert agent.learn_counter == 4
+
+
+# ---- the drop-in trainer ---------------------------------------------------------------
+def _state_equal(a, b):
+    return list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
+
+
+def _adam_equal(a, b):
+    sa, sb = a.state_dict()["state"], b.state_dict()["state"]
+    return list(sa) == list(sb) and all(
+        float(sa[k]["step"]) == float(sb[k]["step"]) and torch.equal(sa[k]["exp_avg"].cpu(), sb[k]["exp_avg"].cpu())
+        and torch.equal(sa[k]["exp_avg_sq"].cpu(), sb[k]["exp_avg_sq"].cpu()) for k in sa)
+
+
+@pytest.mark.parametrize("algo", ["TD3", "DDPG"])
+def test_train_off_policy_checkpoint_and_clone(algo, tmp_path):
+    from agilerl_amd.components import ReplayBuffer
+    from agilerl_amd.hpo.mutation import Mutations
+    from agilerl_amd.hpo.registry import HyperparameterConfig, RLParameter
+    from agilerl_amd.hpo.tournament import TournamentSelection
+    from agilerl_amd.training import train_off_policy
+    from agilerl_amd.utils import create_population
+
+    env = _env()
+    INIT_HP = {"BATCH_SIZE": 32, "LEARN_STEP": 8, "POLICY_FREQ": 2}
+    hp_config = HyperparameterConfig(lr_actor=RLParameter(min=1e-5, max=1e-3),
+                                     lr_critic=RLParameter(min=1e-4, max=1e-2))
+    np.random.seed(0)
+    torch.manual_seed(0)
+    make = lambda n: create_population(algo, None, INIT_HP, env.single_observation_space,  # noqa: E731
+                                       env.single_action_space, hp_config=hp_config, population_size=n, num_envs=8)
+    pop = make(2)
+    assert all(a.vect_noise_dim == 8 and a.algo == algo for a in pop)
+    memory = ReplayBuffer(1000)
+    mutations = Mutations(no_mutation=0.1, architecture=0.3, new_layer_prob=0.2, parameters=0.3, activation=0,
+                          rl_hp=0.3, rand_seed=1)
+    pop, fits = train_off_policy(env, "synthetic_continuous", algo, pop, memory, INIT_HP=INIT_HP, max_steps=400,
+                                 evo_steps=200, eval_steps=20, eval_loop=1, tournament=TournamentSelection(2, True, 2, 1),
+                                 mutation=mutations, verbose=False)
+    assert len(fits) == 2 and all(np.isfinite(f).all() for f in fits)
+    assert all(a.steps[-1] >= 400 for a in pop) and len(memory) == 800
+    stored = memory.storage["action"][:800]
+    assert stored.shape == (800, 3) and stored.dtype == torch.float32
+    assert float(stored.min()) >= -1.0 and float(stored.max()) <= 1.0
+    for agent in pop:
+        for net, target, _ in agent._triples():
+            assert all(torch.isfinite(p).all() for n in (net, target) for p in getattr(agent, n).parameters())
+
+    agent = pop[0]
+    torch.manual_seed(5)
+    agent.learn(memory.sample(32))  # Adam state on the agent's current (possibly just mutated) networks
+    agent.learn(memory.sample(32))
+    path = str(tmp_path / "agent.pt")
+    agent.save_checkpoint(path)
+    other = make(1)[0]
+    other.load_checkpoint(path)
+    for net, target, opt in agent._triples():
+        for n in (net, target):
+            assert _state_equal(getattr(agent, n).state_dict(), getattr(other, n).state_dict()), n
+        assert _adam_equal(getattr(agent, opt), getattr(other, opt)), opt
+    assert other.fitness == agent.fitness and other.steps == agent.steps
+    assert other.learn_counter == agent.learn_counter
+
+    clone = agent.clone()
+    experiences = memory.sample(32)
+    for a in (agent, clone):
+        torch.manual_seed(9)
+        a.learn(experiences)
+    for net, target, _ in agent._triples():
+        for n in (net, target):
+            mine, theirs = getattr(agent, n).state_dict(), getattr(clone, n).state_dict()
+            print(n, "max |agent - clone| =", max(float((mine[k] - theirs[k]).abs().max()) for k in mine))
+            assert _state_equal(mine, theirs), n
