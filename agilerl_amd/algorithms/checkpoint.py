@@ -94,24 +94,55 @@ def spaces(ckpt: dict):
     return Box(-float("inf"), float("inf"), tuple(s["obs_shape"])), Discrete(s["n_actions"])
 
 
+def group_state_dicts(agent) -> tuple[dict, dict]:
+    """(modules, optimizers): the state dicts of the agent's network groups
+    (evolvable.py) by attribute name — net, target, net, target, ..., and the
+    optimizers in group order; {agent id: state dict} for a dict-valued group."""
+    def sd(x):
+        return {a: m.state_dict() for a, m in x.items()} if hasattr(x, "items") else x.state_dict()
+
+    return ({n: sd(getattr(agent, n)) for g in agent._groups for n in g[:2]},
+            {g[2]: sd(getattr(agent, g[2])) for g in agent._groups})
+
+
+def load_group_state_dicts(agent, info: dict) -> None:
+    """``network_info`` into the agent's network groups.  An empty module
+    state dict is skipped, as the reference (core/base.py:1006-1010)."""
+    def load(x, sd, module):
+        if hasattr(x, "items"):
+            for a, s in sd.items():
+                load(x[a], s, module)
+        elif sd or not module:
+            x.load_state_dict(sd)
+
+    for g in agent._groups:
+        for n in g[:2]:
+            load(getattr(agent, n), info["modules"].get(f"{n}_state_dict") or {}, True)
+        load(getattr(agent, g[2]), info["optimizers"][f"{g[2]}_state_dict"], False)
+
+
 class TorchCheckpointMixin:
-    """save_checkpoint / load_checkpoint / load for algorithms whose networks
-    are torch modules ``actor`` / ``actor_target`` with one ``optimizer``."""
+    """save_checkpoint / load_checkpoint / load over the agent's network
+    groups; what a class adds to the file goes through the two hooks."""
+
+    _ckpt_spaces = True  # the file carries ``spaces``, so ``load`` can build the agent
+
+    def _ckpt_extra(self, ck: dict) -> None:
+        """Add the class's own top-level keys to a checkpoint being saved."""
+
+    def _ckpt_restore(self, ck: dict) -> None:
+        """Take them back, before the state dicts are loaded."""
 
     def save_checkpoint(self, path: str) -> None:
-        torch.save(checkpoint_dict(self, {"actor": self.actor.state_dict(),
-                                          "actor_target": self.actor_target.state_dict()},
-                                   {"optimizer": self.optimizer.state_dict()}), path)
+        ck = checkpoint_dict(self, *group_state_dicts(self), spaces=self._ckpt_spaces)
+        self._ckpt_extra(ck)
+        torch.save(ck, path)
 
     @torch.no_grad()
     def load_checkpoint(self, path: str) -> None:
         ck = read(path, self.algo)
-        info = ck["network_info"]
-        for name in ("actor", "actor_target"):
-            sd = info["modules"].get(f"{name}_state_dict")
-            if sd:  # an empty state dict is skipped, as the reference (core/base.py:1010)
-                getattr(self, name).load_state_dict(sd)
-        self.optimizer.load_state_dict(info["optimizers"]["optimizer_state_dict"])
+        self._ckpt_restore(ck)
+        load_group_state_dicts(self, ck["network_info"])
         restore_attributes(self, ck)
 
     @classmethod

@@ -37,28 +37,9 @@ from .. import kernels as K
 from ..networks import ContinuousQNetwork, DeterministicActor
 from ..networks.base import as_config, mlp_net_config
 from . import checkpoint as C
-from .evolvable import EvolvableAgentMixin
-from .flat_state import FlatLearnState, _plain_adam
-
-
-class _CriticLoss(torch.autograd.Function):
-    """MSE(Q1, y) [+ MSE(Q2, y)] with y = r + (1 - d) gamma min(Q1', Q2'):
-    agx_td3_critic_target computes y, the loss and dLoss/dQk in one pass."""
-
-    @staticmethod
-    def forward(ctx, q1, q2, qn1, qn2, rewards, dones, gamma):
-        twin = q2 is not None
-        _, g1, g2, loss = K.td3_critic_target(q1.contiguous(), qn1.contiguous(), rewards, dones, gamma,
-                                              q2=q2.contiguous() if twin else None,
-                                              qn2=qn2.contiguous() if twin else None)
-        ctx.twin = twin
-        ctx.save_for_backward(g1.view_as(q1), *((g2.view_as(q2),) if twin else ()))
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gl):
-        g = ctx.saved_tensors
-        return g[0] * gl, (g[1] * gl if ctx.twin else None), None, None, None, None, None
+from .evolvable import EvolvableAgentMixin, NetGroup
+from .flat_state import flat_state
+from .offpolicy import MSECriticLoss, _evaluate, batch
 
 
 def _arch(net) -> dict:
@@ -77,13 +58,13 @@ def _set_arch(net, arch: dict) -> None:
     net.recreate_network(old)
 
 
-class _DeterministicPolicyGradient(EvolvableAgentMixin):
-    """DDPG / TD3 on one actor and ``len(_critics)`` critics."""
+_ACTOR = NetGroup("actor", "actor_target", "actor_optimizer", "lr_actor")
 
-    #: (eval network, target network, optimizer) attribute names, actor first
-    _actor = ("actor", "actor_target", "actor_optimizer")
-    _critics: tuple[tuple[str, str, str], ...] = ()
-    _policy_group = ("actor", "actor_target")
+
+class _DeterministicPolicyGradient(EvolvableAgentMixin, C.TorchCheckpointMixin):
+    """DDPG / TD3: the actor group, then one group per critic."""
+
+    _ckpt_spaces = False
     #: attributes beyond checkpoint.HP_NAMES that a checkpoint carries
     _CKPT_EXTRA = ("lr_actor", "lr_critic", "policy_freq", "learn_counter", "O_U_noise", "vect_noise_dim", "theta",
                    "dt")
@@ -177,61 +158,18 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
 
         # construction order of the reference: actor, its target, then each critic and its target
         self.actor, self.actor_target = create_actor(), create_actor()
-        for net, target, _ in self._critics:
-            setattr(self, net, create_critic())
-            setattr(self, target, create_critic())
+        for g in self._groups[1:]:
+            setattr(self, g.net, create_critic())
+            setattr(self, g.target, create_critic())
         for net, target, _ in self._triples():
             getattr(self, target).load_state_dict(getattr(self, net).state_dict())
         # the networks' own generators (EvolvableModule.rng, shared with their
         # modules; seeded from the agent's initial index so a run is reproducible)
         self.actor.rng = np.random.default_rng((0x5EED, int(index), 0))
-        for i, (net, _, _) in enumerate(self._critics):
-            getattr(self, net).rng = np.random.default_rng((0x5EEE, int(index), i))
+        for i, g in enumerate(self._groups[1:]):
+            getattr(self, g.net).rng = np.random.default_rng((0x5EEE, int(index), i))
         self.reinit_optimizers()
         self._init_registry(hp_config)
-
-    def _triples(self) -> tuple[tuple[str, str, str], ...]:
-        return (self._actor, *self._critics)
-
-    # ---- optimizers: torch Adam as the state, one fused launch as the step ----
-    def reinit_optimizers(self, optimizer=None) -> None:
-        """A fresh Adam at the current learning rate for the actor
-        (``lr_actor``), every critic (``lr_critic``), or all (None)."""
-        for lr_name in (self.get_lr_names() if optimizer is None else [optimizer]):
-            triples = (self._actor,) if lr_name == "lr_actor" else self._critics
-            for net, _, opt in triples:
-                setattr(self, opt, torch.optim.Adam(getattr(self, net).parameters(), lr=getattr(self, lr_name)))
-
-    def _flat(self, triple) -> FlatLearnState | None:
-        """The triple's valid flat state (adopting its current tensors when a
-        mutation, clone or checkpoint load replaced them), or None where it
-        does not apply (CPU, an optimizer other than plain Adam)."""
-        net, target, opt = (getattr(self, n) for n in triple)
-        if self.device.type != "cuda" or not _plain_adam(opt):
-            return None
-        states = self.__dict__.setdefault("_flat_states", {})
-        fs = states.get(triple[0])
-        if fs is None or not fs.valid(net, target, opt):
-            fs = states[triple[0]] = FlatLearnState(net, target, opt)
-        return fs
-
-    def _step(self, triple) -> None:
-        """Where the reference calls ``optimizer.step()`` (no gradient clip)."""
-        fs = self._flat(triple)
-        if fs is None or not fs.step(0.0):
-            getattr(self, triple[2]).step()
-
-    @torch.no_grad()
-    def soft_update(self, triple) -> None:
-        """target <- tau * net + (1 - tau) * target (td3.py:553-566): one
-        agx_polyak launch over the network's flat buffers, else one per
-        parameter tensor."""
-        fs = self._flat(triple)
-        if fs is not None:
-            fs.polyak(self.tau)
-            return
-        for e, t in zip(getattr(self, triple[0]).parameters(), getattr(self, triple[1]).parameters()):
-            K.polyak_(t.data.view(-1), e.data.reshape(-1), float(self.tau))
 
     # ---- architecture mutation (hpo/mutation.py:829-885) ----------------------
     def architecture_mutation(self, new_layer_prob: float, rng) -> str | None:
@@ -241,8 +179,8 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
         table has it; every target re-made from its eval network
         (reinit_shared_networks, :104-160).  -> the applied method or None."""
         applied, mut_dict = self.actor.apply_mutation_dict(self.actor.sample_mutation_method(new_layer_prob, rng))
-        for net, _, _ in self._critics:
-            critic = getattr(self, net)
+        for g in self._groups[1:]:
+            critic = getattr(self, g.net)
             if applied in critic.mutation_methods:
                 critic.apply_mutation_dict(applied, mut_dict)
         for net, target, _ in self._triples():
@@ -297,14 +235,13 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
         fresh tensor of the same shape — the same consumption of the device
         generator and the same values — and ``experiences["action"]`` is
         left as it was."""
-        get = experiences.get if hasattr(experiences, "get") else (lambda k: experiences[k])
-        to = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(self.device)  # noqa: E731
-        obs, next_obs = self._obs(get("obs")), self._obs(get("next_obs"))
-        actions = to(get("action")).to(torch.float32).reshape(obs.shape[0], self.action_dim)
-        rewards = to(get("reward")).to(torch.float32).reshape(-1).contiguous()
-        dones = to(get("done")).to(torch.float32).reshape(-1).contiguous()
-        critics = [getattr(self, net) for net, _, _ in self._critics]
-        targets = [getattr(self, target) for _, target, _ in self._critics]
+        obs, actions, rewards, next_obs, dones = batch(self, experiences, "obs", "action", "reward", "next_obs", "done")
+        actions = actions.to(torch.float32).reshape(obs.shape[0], self.action_dim)
+        rewards = rewards.to(torch.float32).reshape(-1).contiguous()
+        dones = dones.to(torch.float32).reshape(-1).contiguous()
+        critic_groups = self._groups[1:]
+        critics = [getattr(self, g.net) for g in critic_groups]
+        targets = [getattr(self, g.target) for g in critic_groups]
 
         q = [critic(obs, actions) for critic in critics]
         with torch.no_grad():
@@ -315,13 +252,13 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
             K.td3_smooth_actions(next_actions, noise, *self._bounds, noise_clip, out=next_actions)
             q_next = [target(next_obs, next_actions) for target in targets]
         twin = len(critics) == 2
-        critic_loss = _CriticLoss.apply(q[0], q[1] if twin else None, q_next[0], q_next[1] if twin else None,
-                                        rewards, dones, float(self.gamma))
-        for _, _, opt in self._critics:
-            getattr(self, opt).zero_grad()
+        critic_loss = MSECriticLoss.apply(q[0], q[1] if twin else None, q_next[0], q_next[1] if twin else None,
+                                          rewards, dones, float(self.gamma), False)
+        for g in critic_groups:
+            getattr(self, g.opt).zero_grad()
         critic_loss.backward()
-        for triple in self._critics:
-            self._step(triple)
+        for g in critic_groups:
+            self._step(g)
 
         self.learn_counter += 1
         if self.learn_counter % self.policy_freq != 0:
@@ -329,16 +266,14 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
         actor_loss = -critics[0](obs, self.actor(obs)).mean()
         self.actor_optimizer.zero_grad()
         actor_loss.backward()
-        self._step(self._actor)
-        for triple in self._triples():
-            self.soft_update(triple)
+        self._step(_ACTOR)
+        for g in self._groups:
+            self.soft_update(g)
         return actor_loss.item(), critic_loss.item()
 
     # ---- evaluation, clones, checkpoints ----------------------------------------
     @torch.no_grad()
     def test(self, env, swap_channels: bool = False, max_steps: int | None = None, loop: int = 3) -> float:
-        from .dqn import _evaluate
-
         self.set_training_mode(False)
         fitness = _evaluate(self, env, lambda o: self.get_action(o, training=False), max_steps, loop)
         self.set_training_mode(True)
@@ -346,52 +281,35 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
 
     def clone(self, index: int | None = None, wrap: bool = True):
         """Deep copy with a new index (EvolvableAlgorithm.clone, core/base.py).
-        The copy gets flat buffers of its own for every triple whose flat
+        The copy gets flat buffers of its own for every group whose flat
         state is live here, so its tensors are laid out as this agent's are
         and the two compute the same update from the same batch and seed."""
-        flat = self.__dict__.pop("_flat_states", None) or {}
+        flat = self.__dict__.pop("_flat", None) or {}
         try:
-            c = copy.deepcopy(self)
+            c = super().clone(index, wrap)
         finally:
             if flat:
-                self.__dict__["_flat_states"] = flat
-        for triple in self._triples():
-            fs = flat.get(triple[0])
-            if fs is not None and fs.valid(*(getattr(self, n) for n in triple)):
-                c._flat(triple)
-        if index is not None:
-            c.index = index
+                self.__dict__["_flat"] = flat
+        for g in self._groups:
+            fs = flat.get(g.net)
+            if fs is not None and fs.valid(*(getattr(self, n) for n in g[:3])):
+                flat_state(c, g)
         return c
 
-    def save_checkpoint(self, path: str) -> None:
-        """core/base.py:939-1072 layout (checkpoint.py) with the reference's
-        attribute names; ``network_arch`` records what architecture mutations
-        changed, so a freshly built agent can take the weights."""
-        triples = self._triples()
-        mods = {n: getattr(self, n).state_dict() for net, target, _ in triples for n in (net, target)}
-        opts = {opt: getattr(self, opt).state_dict() for _, _, opt in triples}
-        ck = C.checkpoint_dict(self, mods, opts, spaces=False)
+    # core/base.py:939-1072 layout (checkpoint.py) with the reference's attribute
+    # names; ``network_arch`` records what architecture mutations changed, so
+    # a freshly built agent can take the weights
+    def _ckpt_extra(self, ck: dict) -> None:
         for k in self._CKPT_EXTRA:
             ck[k] = C._plain(getattr(self, k))
         for k in self._CKPT_ARRAYS:
             ck[k] = torch.from_numpy(np.array(getattr(self, k), dtype=np.float64))
-        ck["network_arch"] = {n: _arch(getattr(self, n)) for n in mods}
-        torch.save(ck, path)
+        ck["network_arch"] = {n: _arch(getattr(self, n)) for g in self._groups for n in g[:2]}
 
-    @torch.no_grad()
-    def load_checkpoint(self, path: str) -> None:
-        ck = C.read(path, self.algo)
-        info = ck["network_info"]
+    def _ckpt_restore(self, ck: dict) -> None:
         for n, arch in ck.get("network_arch", {}).items():
             _set_arch(getattr(self, n), arch)
         self.reinit_optimizers()  # over the (possibly rebuilt) parameters
-        for net, target, opt in self._triples():
-            for n in (net, target):
-                sd = info["modules"].get(f"{n}_state_dict")
-                if sd:  # an empty state dict is skipped, as the reference (core/base.py:1010)
-                    getattr(self, n).load_state_dict(sd)
-            getattr(self, opt).load_state_dict(info["optimizers"][f"{opt}_state_dict"])
-        C.restore_attributes(self, ck)
         for k in self._CKPT_EXTRA:
             if k in ck:
                 setattr(self, k, ck[k])
@@ -418,8 +336,7 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin):
 
 class DDPG(_DeterministicPolicyGradient):
     algo = "DDPG"
-    _critics = (("critic", "critic_target", "critic_optimizer"),)
-    _lr_optimizers = {"lr_actor": "actor_optimizer", "lr_critic": "critic_optimizer"}
+    _groups = (_ACTOR, NetGroup("critic", "critic_target", "critic_optimizer", "lr_critic"))
     _DEFAULT_TAU = 0.001
 
     def __init__(self, observation_space, action_space, O_U_noise: bool = True, expl_noise=0.1,

@@ -23,6 +23,7 @@ from . import checkpoint as C
 from .evolvable import EvolvableAgentMixin
 from . import learn_graph
 from .flat_state import flat_state
+from .offpolicy import _evaluate, batch
 from ..modules.custom_components import noisy_scope
 from ..networks import QNetwork, RainbowQNetwork
 from ..networks.base import image_norm_bounds, is_image_space, mlp_net_config
@@ -147,76 +148,18 @@ class DQN(EvolvableAgentMixin, C.TorchCheckpointMixin):
                              float(self.gamma), bool(self.double))
         self.optimizer.zero_grad()
         loss.backward()
-        fs = flat_state(self)
-        if fs is None or not fs.step(0.0):  # Adam over the flat buffers: one launch (flat_state.py)
-            self.optimizer.step()
+        self._step(self._groups[0])
         return loss.detach()
 
     def learn(self, experiences) -> float:
         """experiences: mapping with obs, action, reward, next_obs, done (dqn.py:326-348)."""
-        get = experiences.get if hasattr(experiences, "get") else (lambda k: experiences[k])
-        obs = self._obs(get("obs"))
-        next_obs = self._obs(get("next_obs"))
-        to = lambda x: torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(self.device)
-        loss = self.update(obs, to(get("action")), to(get("reward")), next_obs, to(get("done")))
+        loss = self.update(*batch(self, experiences, "obs", "action", "reward", "next_obs", "done"))
         self.soft_update()
         return float(loss.item())
-
-    def _fresh_optimizer(self, lr_name: str):
-        return torch.optim.Adam(self.actor.parameters(), lr=self.lr)
-
-    def clone(self, index: int | None = None, wrap: bool = True):
-        """Deep copy with a new index (EvolvableAlgorithm.clone, core/base.py)."""
-        import copy
-
-        c = copy.deepcopy(self)
-        if index is not None:
-            c.index = index
-        return c
-
-    @torch.no_grad()
-    def soft_update(self) -> None:
-        """target <- tau * online + (1 - tau) * target (dqn.py:349-358): one
-        agx_polyak launch over the flat buffers (flat_state.py), else one per
-        parameter tensor."""
-        fs = flat_state(self)
-        if fs is not None:
-            fs.polyak(self.tau)
-            return
-        for t, o in zip(self.actor_target.parameters(), self.actor.parameters()):
-            K.polyak_(t.data.view(-1), o.data.reshape(-1), float(self.tau))
 
     @torch.no_grad()
     def test(self, env, swap_channels: bool = False, max_steps: int | None = None, loop: int = 3) -> float:
         return _evaluate(self, env, lambda o: self.get_action(o, epsilon=0.0), max_steps, loop)
-
-
-def _evaluate(agent, env, act, max_steps, loop) -> float:
-    """Mean over ``loop`` passes of the score of every env's first finished
-    episode (the reference algorithms' ``test``); appended to agent.fitness."""
-    rewards = []
-    num_envs = env.num_envs if hasattr(env, "num_envs") else 1
-    for _ in range(loop):
-        obs, _ = env.reset()
-        scores = np.zeros(num_envs)
-        completed = np.zeros(num_envs)
-        finished = np.zeros(num_envs, dtype=bool)
-        step = 0
-        while not np.all(finished):
-            obs, r, term, trunc, _ = env.step(act(obs))
-            step += 1
-            scores += np.asarray(r).reshape(num_envs)
-            done = np.logical_or(term, trunc).reshape(num_envs)
-            if max_steps is not None and step == max_steps:
-                done[:] = True
-            for i in range(num_envs):
-                if done[i] and not finished[i]:
-                    completed[i] = scores[i]
-                    finished[i] = True
-        rewards.append(float(np.mean(completed)))
-    f = float(np.mean(rewards))
-    agent.fitness.append(f)
-    return f
 
 
 class _C51Loss(torch.autograd.Function):
@@ -605,18 +548,11 @@ class RainbowDQN(EvolvableAgentMixin, C.TorchCheckpointMixin):
         """-> (loss, idxs, new_priorities) (dqn_rainbow.py:369-490).  The
         device work is replayed from a captured graph from the second update
         of a given shape on (learn_graph.py)."""
-        to = lambda x: torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(self.device)
-        get = lambda e, k: e[k]
+        keys = ("obs", "action", "reward", "next_obs", "done")
         n_step = n_experiences is not None
-        xs = [self._obs(get(experiences, "obs")), to(get(experiences, "action")), to(get(experiences, "reward")),
-              self._obs(get(experiences, "next_obs")), to(get(experiences, "done"))]
-        if n_step:
-            xs += [self._obs(get(n_experiences, "obs")), to(get(n_experiences, "action")),
-                   to(get(n_experiences, "reward")), self._obs(get(n_experiences, "next_obs")),
-                   to(get(n_experiences, "done"))]
-        if per:
-            xs.append(to(get(experiences, "weights")))
-        idxs = get(experiences, "idxs") if (per or n_step) else None
+        xs = batch(self, experiences, *keys) + (batch(self, n_experiences, *keys) if n_step else []) + \
+            (batch(self, experiences, "weights") if per else [])
+        idxs = experiences["idxs"] if (per or n_step) else None
         fs = flat_state(self)
         nets = (self.actor, self.actor_target)
         g = self.optimizer.param_groups[0]
@@ -640,24 +576,3 @@ class RainbowDQN(EvolvableAgentMixin, C.TorchCheckpointMixin):
             loss, el = out
         new_priorities = el.detach().cpu().numpy() + self.prior_eps if per else None
         return loss.item(), idxs, new_priorities
-
-    def _fresh_optimizer(self, lr_name: str):
-        return torch.optim.Adam(self.actor.parameters(), lr=self.lr)
-
-    def clone(self, index: int | None = None, wrap: bool = True):
-        """Deep copy with a new index (EvolvableAlgorithm.clone, core/base.py)."""
-        import copy
-
-        c = copy.deepcopy(self)
-        if index is not None:
-            c.index = index
-        return c
-
-    @torch.no_grad()
-    def soft_update(self) -> None:
-        fs = flat_state(self)
-        if fs is not None:
-            fs.polyak(self.tau)
-            return
-        for t, o in zip(self.actor_target.parameters(), self.actor.parameters()):
-            K.polyak_(t.data.view(-1), o.data.reshape(-1), float(self.tau))

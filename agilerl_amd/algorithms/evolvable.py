@@ -16,18 +16,30 @@ for the object-level agents (DQN, RainbowDQN, DDPG, TD3, MADDPG):
 
 from __future__ import annotations
 
+import copy
+from typing import NamedTuple
+
 import torch
 
+from .. import kernels as K
 from ..modules.mlp import EvolvableMLP
+from .flat_state import flat_state
+
+
+class NetGroup(NamedTuple):
+    """Attribute names of one eval network, its target copy, its optimizer and
+    the learning rate that drives it (each a dict keyed by agent id in MADDPG)."""
+    net: str
+    target: str
+    opt: str
+    lr: str
 
 
 class EvolvableAgentMixin:
     sharded = False  # set by create_population when the agent is one shard of a global population
 
-    #: learning-rate attribute -> the optimizer attribute it drives
-    _lr_optimizers: dict[str, str] = {"lr": "optimizer"}
-    #: (eval network attribute, shared network attribute) of the policy group
-    _policy_group: tuple[str, str] = ("actor", "actor_target")
+    #: the agent's networks; the first group is the policy group
+    _groups: tuple[NetGroup, ...] = (NetGroup("actor", "actor_target", "optimizer", "lr"),)
 
     def _init_registry(self, hp_config) -> None:
         from ..hpo.registry import MutationRegistry
@@ -36,10 +48,10 @@ class EvolvableAgentMixin:
         self.registry = MutationRegistry(hp_config)
 
     def get_lr_names(self) -> list[str]:
-        return list(self._lr_optimizers)
+        return list(dict.fromkeys(g.lr for g in self._groups))
 
-    def _fresh_optimizer(self, lr_name: str):
-        raise NotImplementedError
+    def _triples(self) -> tuple[tuple[str, str, str], ...]:
+        return tuple(g[:3] for g in self._groups)
 
     @property
     def can_mutate_architecture(self) -> bool:
@@ -57,7 +69,7 @@ class EvolvableAgentMixin:
             return False
         from ..modules.cnn import EvolvableCNN
 
-        net = getattr(self, self._policy_group[0])
+        net = getattr(self, self._groups[0].net)
         return isinstance(getattr(net, "encoder", None), (EvolvableMLP, EvolvableCNN)) and \
             isinstance(getattr(net, "head_net", None), EvolvableMLP)
 
@@ -68,27 +80,59 @@ class EvolvableAgentMixin:
         encoder, population/image_arch.py), applied
         with the modules' own generators; the shared (target) network re-made
         from the mutated one (reinit_shared_networks, mutation.py:104-160)."""
-        import copy
-
-        net = getattr(self, self._policy_group[0])
+        net = getattr(self, self._groups[0].net)
         applied = net.apply_mutation(net.sample_mutation_method(new_layer_prob, rng))
-        setattr(self, self._policy_group[1], copy.deepcopy(net))
+        setattr(self, self._groups[0].target, copy.deepcopy(net))
         return applied
 
     def reinit_optimizers(self, optimizer=None) -> None:
-        names = self.get_lr_names() if optimizer is None else [optimizer]
-        for lr_name in names:
-            setattr(self, self._lr_optimizers[lr_name], self._fresh_optimizer(lr_name))
+        """A fresh Adam at the current learning rate for every group, or for
+        the groups that the learning rate named ``optimizer`` drives."""
+        for g in self._groups:
+            if optimizer in (None, g.lr):
+                net, lr = getattr(self, g.net), getattr(self, g.lr)
+                adam = lambda m: torch.optim.Adam(m.parameters(), lr=lr)  # noqa: E731
+                setattr(self, g.opt, {a: adam(m) for a, m in net.items()} if hasattr(net, "items") else adam(net))
+
+    def _step(self, group, max_norm: float = 0.0) -> None:
+        """Where the reference calls ``optimizer.step()``: one launch over the
+        group's flat buffers (flat_state.py), else the torch optimizer."""
+        fs = flat_state(self, group)
+        if fs is None or not fs.step(max_norm):
+            getattr(self, group[2]).step()
+
+    @torch.no_grad()
+    def soft_update(self, group=None) -> None:
+        """target <- tau * net + (1 - tau) * target: one agx_polyak launch over
+        the group's flat buffers, else one per parameter tensor."""
+        group = group or self._groups[0]
+        fs = flat_state(self, group)
+        if fs is not None:
+            fs.polyak(self.tau)
+        else:
+            self._polyak_tensors(getattr(self, group[0]), getattr(self, group[1]))
+
+    def _polyak_tensors(self, net, target) -> None:
+        for n, t in ([(net[a], target[a]) for a in net] if hasattr(net, "items") else [(net, target)]):
+            for e, p in zip(n.parameters(), t.parameters()):
+                K.polyak_(p.data.view(-1), e.data.reshape(-1), float(self.tau))
+
+    def clone(self, index: int | None = None, wrap: bool = True):
+        """Deep copy with a new index (EvolvableAlgorithm.clone, core/base.py)."""
+        c = copy.deepcopy(self)
+        if index is not None:
+            c.index = index
+        return c
 
     def policy_weight_groups(self) -> list[dict[str, torch.Tensor]]:
-        net = getattr(self, self._policy_group[0])
+        net = getattr(self, self._groups[0].net)
         if isinstance(net, torch.nn.ModuleDict):
             return [m.state_dict() for m in net.values()]
         return [net.state_dict()]
 
     @torch.no_grad()
     def sync_shared_networks(self) -> None:
-        net, shared = getattr(self, self._policy_group[0]), getattr(self, self._policy_group[1])
+        net, shared = (getattr(self, n) for n in self._groups[0][:2])
         if isinstance(net, torch.nn.ModuleDict):
             for k in net:
                 shared[k].load_state_dict(net[k].state_dict(), strict=False)

@@ -168,24 +168,27 @@ class FlatLearnState:
         _lib.call("agx_polyak", self.tgt.data_ptr(), self.prm.data_ptr(), self.n, float(tau), _lib.stream())
 
 
-def flat_state(agent) -> FlatLearnState | None:
-    """The agent's valid flat state (adopting its current tensors when the
-    modules / optimizer changed), or None where it does not apply (CPU, an
-    optimizer other than plain single-group Adam)."""
-    actor, target, opt = agent.actor, agent.actor_target, agent.optimizer
+def flat_state(agent, group=None) -> FlatLearnState | None:
+    """The valid flat state of one of the agent's network groups (names of
+    net, target, optimizer; default: the first, the policy group), adopting
+    its current tensors when a mutation, clone or checkpoint load replaced
+    them, or None where it does not apply (CPU, an optimizer other than
+    plain single-group Adam).  Cached per agent under the net's name."""
+    first = agent._groups[0]
+    name = (group or first)[0]
+    actor, target, opt = (getattr(agent, n) for n in (group or first)[:3])
     if agent.device.type != "cuda" or not _plain_adam(opt):
         return None
     # rows of a live RainbowPopulationLearner: it owns the tensors (a learner
     # that was released, or tensors the agent has since replaced, do not count)
-    owned = agent.__dict__.get("_pop_rows")
+    owned = agent.__dict__.get("_pop_rows") if name == first[0] else None
     if owned is not None:
         learner, ptrs = owned[0](), owned[1]
         if learner is not None and tuple(p.data_ptr() for p in actor.parameters()) == ptrs:
             return None
         agent.__dict__.pop("_pop_rows", None)
-    fs = agent.__dict__.get("_flat")
-    if fs is not None and fs.valid(actor, target, opt):
-        return fs
-    fs = FlatLearnState(actor, target, opt)
-    agent.__dict__["_flat"] = fs
+    cache = agent.__dict__.setdefault("_flat", {})
+    fs = cache.get(name)
+    if fs is None or not fs.valid(actor, target, opt):
+        fs = cache[name] = FlatLearnState(actor, target, opt)
     return fs

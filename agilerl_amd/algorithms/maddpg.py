@@ -22,26 +22,12 @@ from typing import Any
 import numpy as np
 import torch
 
-from .. import kernels as K
 from ..envs import Dict as DictSpace
 from ..networks import ContinuousQNetwork, DeterministicActor
 from ..networks.base import as_config, mlp_net_config
 from . import checkpoint as C
-from .evolvable import EvolvableAgentMixin
-
-
-class _CriticLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, q_next, rewards, dones, gamma):
-        _, g_q, loss = K.maddpg_critic_target(q.contiguous(), q_next.contiguous(), rewards.contiguous(),
-                                              dones.contiguous(), gamma)
-        ctx.save_for_backward(g_q.view_as(q))
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gl):
-        (g_q,) = ctx.saved_tensors
-        return g_q * gl, None, None, None, None
+from .evolvable import EvolvableAgentMixin, NetGroup
+from .offpolicy import MSECriticLoss
 
 
 def _as_dict(spaces, agent_ids):
@@ -54,12 +40,13 @@ def _action_dim(space) -> int:
     return int(space.n) if hasattr(space, "n") else int(np.prod(space.shape))
 
 
-class MADDPG(EvolvableAgentMixin):
+class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
     algo = "MADDPG"
     # maddpg.py:424-444: the actors are the policy group (targets shared); one
-    # optimizer set per learning rate
-    _lr_optimizers = {"lr_actor": "actor_optimizers", "lr_critic": "critic_optimizers"}
-    _policy_group = ("actors", "actor_targets")
+    # optimizer set per learning rate, every attribute a dict keyed by agent id
+    _groups = (NetGroup("actors", "actor_targets", "actor_optimizers", "lr_actor"),
+               NetGroup("critics", "critic_targets", "critic_optimizers", "lr_critic"))
+    _ckpt_spaces = False
 
     def __init__(self, observation_spaces, action_spaces, agent_ids: list[str] | None = None,
                  O_U_noise: bool = True, expl_noise: float = 0.1, vect_noise_dim: int = 1, mean_noise: float = 0.0,
@@ -127,14 +114,8 @@ class MADDPG(EvolvableAgentMixin):
             # encoder is of another type)
             self.actors[a].encoder.disable_mutations()
             self.actor_targets[a].encoder.disable_mutations()
-        self.actor_optimizers = {a: torch.optim.Adam(self.actors[a].parameters(), lr=lr_actor) for a in self.agent_ids}
-        self.critic_optimizers = {a: torch.optim.Adam(self.critics[a].parameters(), lr=lr_critic)
-                                  for a in self.agent_ids}
+        self.reinit_optimizers()
         self._init_registry(hp_config)
-
-    def _fresh_optimizer(self, lr_name: str):
-        nets, lr = (self.actors, self.lr_actor) if lr_name == "lr_actor" else (self.critics, self.lr_critic)
-        return {a: torch.optim.Adam(nets[a].parameters(), lr=lr) for a in self.agent_ids}
 
     # ---- network construction (maddpg.py:296-380) ---------------------------
     def _agent_configs(self, net_config) -> dict[str, dict]:
@@ -324,8 +305,8 @@ class MADDPG(EvolvableAgentMixin):
         with torch.no_grad():
             q_next = self.critic_targets[agent_id](next_states, stacked_next_actions)
         # NaN handling, y_j and MSE fused in agx_maddpg_critic_target (maddpg.py:764-781)
-        critic_loss = _CriticLoss.apply(q_value, q_next, rewards[agent_id].float().reshape(-1),
-                                        dones[agent_id].float().reshape(-1), float(self.gamma))
+        critic_loss = MSECriticLoss.apply(q_value, None, q_next, None, rewards[agent_id].float().reshape(-1),
+                                          dones[agent_id].float().reshape(-1), float(self.gamma), True)
         opt_c = self.critic_optimizers[agent_id]
         opt_c.zero_grad()
         critic_loss.backward()
@@ -342,8 +323,7 @@ class MADDPG(EvolvableAgentMixin):
     @torch.no_grad()
     def soft_update(self, net: torch.nn.Module, target: torch.nn.Module) -> None:
         """target <- tau * net + (1 - tau) * target (maddpg.py:822-836), agx_polyak."""
-        for e, t in zip(net.parameters(), target.parameters()):
-            K.polyak_(t.data.view(-1), e.data.reshape(-1), float(self.tau))
+        self._polyak_tensors(net, target)
 
     # ---- evaluation (maddpg.py:838-960) ------------------------------------
     def test(self, env, swap_channels: bool = False, max_steps: int | None = None, loop: int = 3,
@@ -384,31 +364,6 @@ class MADDPG(EvolvableAgentMixin):
         self.fitness.append(mean_fit)
         return mean_fit
 
-    def clone(self, index: int | None = None, wrap: bool = True):
-        c = copy.deepcopy(self)
-        if index is not None:
-            c.index = index
-        return c
-
     # ---- checkpoints (core/base.py:939-1072 layout, see checkpoint.py) --------
-    def save_checkpoint(self, path: str) -> None:
-        mods = {n: {a: m.state_dict() for a, m in getattr(self, n).items()}
-                for n in ("actors", "actor_targets", "critics", "critic_targets")}
-        opts = {n: {a: o.state_dict() for a, o in getattr(self, n).items()}
-                for n in ("actor_optimizers", "critic_optimizers")}
-        ck = C.checkpoint_dict(self, mods, opts, spaces=False)
+    def _ckpt_extra(self, ck: dict) -> None:
         ck["lr_actor"], ck["lr_critic"], ck["agent_ids"] = self.lr_actor, self.lr_critic, self.agent_ids
-        torch.save(ck, path)
-
-    @torch.no_grad()
-    def load_checkpoint(self, path: str) -> None:
-        ck = C.read(path, self.algo)
-        info = ck["network_info"]
-        for n in ("actors", "actor_targets", "critics", "critic_targets"):
-            for a, sd in info["modules"][f"{n}_state_dict"].items():
-                if sd:  # empty ones are skipped, as the reference (core/base.py:1006-1008)
-                    getattr(self, n)[a].load_state_dict(sd)
-        for n in ("actor_optimizers", "critic_optimizers"):
-            for a, sd in info["optimizers"][f"{n}_state_dict"].items():
-                getattr(self, n)[a].load_state_dict(sd)
-        C.restore_attributes(self, ck)

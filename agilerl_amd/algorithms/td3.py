@@ -14,15 +14,15 @@ from __future__ import annotations
 
 from typing import Any
 
-from .ddpg import _DeterministicPolicyGradient
+from .ddpg import _ACTOR, _DeterministicPolicyGradient
+from .evolvable import NetGroup
 
 
 class TD3(_DeterministicPolicyGradient):
     algo = "TD3"
-    _critics = (("critic_1", "critic_target_1", "critic_1_optimizer"),
-                ("critic_2", "critic_target_2", "critic_2_optimizer"))
     # lr_critic drives both critic optimizers (reinit_optimizers re-makes the two)
-    _lr_optimizers = {"lr_actor": "actor_optimizer", "lr_critic": "critic_1_optimizer"}
+    _groups = (_ACTOR, NetGroup("critic_1", "critic_target_1", "critic_1_optimizer", "lr_critic"),
+               NetGroup("critic_2", "critic_target_2", "critic_2_optimizer", "lr_critic"))
     _DEFAULT_TAU = 0.005
 
     def __init__(self, observation_space, action_space, O_U_noise: bool = True, vect_noise_dim: int = 1,

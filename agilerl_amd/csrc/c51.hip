@@ -1,9 +1,4 @@
-// DQN TD target and Rainbow C51 categorical projection + cross entropy.
-//
-// TD target — agilerl/algorithms/dqn.py:296-314 (DQN.update):
-//   q_t = max_a Qtgt(s')  |  Qtgt(s')[argmax_a Q(s')] (double)
-//   y   = r + (gamma*q_t)*(1-d)        (f32, one rounding per op)
-//   loss = MSE(Q(s)[a], y);  dloss/dQ(s)[a] = 2 (Q[a]-y) / B
+// Rainbow C51 categorical projection + cross entropy.
 //
 // C51 — agilerl/algorithms/dqn_rainbow.py:313-367 (RainbowDQN._dqn_loss), f32:
 //   a* = argmax Q_online(s') (first maximum, like torch.argmax)
@@ -25,109 +20,6 @@
 #include "agx_common.h"
 
 namespace agx {
-
-constexpr int kTdBlock = 256;
-
-// one row per lane; the squared TD errors are reduced per block (f64, fixed
-// order) into partials[blockIdx] and summed by td_loss_finalize
-__global__ __launch_bounds__(kTdBlock) void td_target_kernel(
-    const float *__restrict__ qno, const float *__restrict__ qnt, const float *__restrict__ qc,
-    const int64_t *__restrict__ act, const float *__restrict__ r, const float *__restrict__ d, int64_t B, int A,
-    float g, int dbl, float *__restrict__ y, float *__restrict__ g_q, double *__restrict__ partials) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    double sq = 0.0;
-    if (i < B) {
-        const float *tn = qnt + i * A;
-        float qt;
-        if (dbl) {
-            const float *on = qno + i * A;
-            int best = 0;
-            float bv = on[0];
-            for (int a = 1; a < A; ++a)
-                if (on[a] > bv) {
-                    bv = on[a];
-                    best = a;
-                }
-            qt = tn[best];
-        } else {
-            qt = tn[0];
-            for (int a = 1; a < A; ++a) qt = fmaxf(qt, tn[a]);
-        }
-        const float yi = r[i] + (g * qt) * (1.0f - d[i]);
-        y[i] = yi;
-        if (qc) {
-            const int64_t ai = act[i];
-            const float qa = qc[i * A + ai];
-            if (g_q) {
-                const float diff = qa - yi;
-                const float scale = 2.0f / (float)B;
-                for (int a = 0; a < A; ++a) g_q[i * A + a] = (a == ai) ? diff * scale : 0.0f;
-            }
-            const double dd = (double)qa - (double)yi;
-            sq = dd * dd;
-        }
-    }
-    if (partials) {
-        __shared__ double red[kTdBlock / kWave];
-        sq = wave_sum(sq);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = sq;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int w = 0; w < kTdBlock / kWave; ++w) t += red[w];
-            partials[blockIdx.x] = t;
-        }
-    }
-}
-
-// MADDPG critic target (agilerl/algorithms/maddpg.py:764-781): NaN rewards ->
-// 0, NaN dones -> 1, dones cast to uint8 (truncation), then
-//   y = r + ((1 - d) * gamma) * q'        ((1 - d) in uint8 arithmetic)
-//   loss = MSE(q, y);  dloss/dq = 2 (q - y) / B
-// One row per lane, squared errors reduced like td_target_kernel.
-__global__ __launch_bounds__(kTdBlock) void maddpg_critic_kernel(
-    const float *__restrict__ q, const float *__restrict__ qn, const float *__restrict__ r,
-    const float *__restrict__ d, int64_t B, float g, float *__restrict__ y, float *__restrict__ g_q,
-    double *__restrict__ partials) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    double sq = 0.0;
-    if (i < B) {
-        const float ri = __builtin_isnan(r[i]) ? 0.0f : r[i];
-        const float di = __builtin_isnan(d[i]) ? 1.0f : d[i];
-        const unsigned char du = (unsigned char)(int)di;           // .to(torch.uint8)
-        const float nd = (float)(unsigned char)(1u - du);           // 1 - uint8 tensor (wraps)
-        const float yi = ri + (nd * g) * qn[i];
-        if (y) y[i] = yi;
-        const float diff = q[i] - yi;
-        if (g_q) g_q[i] = diff * (2.0f / (float)B);
-        const double dd = (double)q[i] - (double)yi;
-        sq = dd * dd;
-    }
-    __shared__ double red[kTdBlock / kWave];
-    sq = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kTdBlock / kWave; ++w) t += red[w];
-        partials[blockIdx.x] = t;
-    }
-}
-
-__global__ __launch_bounds__(1024) void td_loss_finalize(const double *__restrict__ partials, int64_t nblk,
-                                                         int64_t B, float *__restrict__ loss) {
-    __shared__ double red[1024 / kWave];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < nblk; i += blockDim.x) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < (int)(blockDim.x / 64); ++w) t += red[w];
-        *loss = (float)(t / (double)B);
-    }
-}
 
 constexpr int kC51Waves = 4;   // rows per block
 constexpr int kC51MaxZ = 256;  // atoms per row (lane handles Z/64 of them)
@@ -602,48 +494,6 @@ __global__ __launch_bounds__(64) void c51_dma_kernel(
 }  // namespace agx
 
 using namespace agx;
-
-extern "C" size_t agx_td_workspace_bytes(int64_t B) {
-    return B > 0 ? (size_t)ceil_div(B, kTdBlock) * sizeof(double) : 0;
-}
-
-extern "C" int agx_td_target(const float *q_next_online, const float *q_next_target,
-                             const float *q_cur, const int64_t *actions, const float *rewards,
-                             const float *dones, int64_t B, int64_t A, double gamma, int double_q,
-                             float *y, float *g_q, float *loss, void *workspace, void *stream) {
-    AGX_REQUIRE(q_next_target && rewards && dones && y && B >= 0 && A > 0 && A < 65536,
-                "agx_td_target: bad arguments");
-    AGX_REQUIRE(!double_q || q_next_online, "agx_td_target: double_q needs q_next_online");
-    AGX_REQUIRE(!(g_q || loss) || (q_cur && actions), "agx_td_target: loss needs q_cur/actions");
-    AGX_REQUIRE(!loss || workspace, "agx_td_target: loss needs the workspace (agx_td_workspace_bytes)");
-    if (B == 0) return AGX_OK;
-    hipStream_t s = as_stream(stream);
-    const int64_t nblk = ceil_div(B, kTdBlock);
-    double *part = loss ? static_cast<double *>(workspace) : nullptr;
-    td_target_kernel<<<(unsigned)nblk, kTdBlock, 0, s>>>(q_next_online, q_next_target, q_cur, actions, rewards,
-                                                         dones, B, (int)A, (float)gamma, double_q, y, g_q, part);
-    int rc = check_launch("agx_td_target");
-    if (rc || !loss) return rc;
-    td_loss_finalize<<<1, 1024, 0, s>>>(part, nblk, B, loss);
-    return check_launch("agx_td_target loss");
-}
-
-extern "C" int agx_maddpg_critic_target(const float *q, const float *q_next, const float *rewards,
-                                        const float *dones, int64_t B, double gamma, float *y, float *g_q,
-                                        float *loss, void *workspace, void *stream) {
-    AGX_REQUIRE(q && q_next && rewards && dones && loss && workspace && B >= 0,
-                "agx_maddpg_critic_target: bad arguments");
-    if (B == 0) return AGX_OK;
-    hipStream_t s = as_stream(stream);
-    const int64_t nblk = ceil_div(B, kTdBlock);
-    double *part = static_cast<double *>(workspace);
-    maddpg_critic_kernel<<<(unsigned)nblk, kTdBlock, 0, s>>>(q, q_next, rewards, dones, B, (float)gamma, y, g_q,
-                                                            part);
-    int rc = check_launch("agx_maddpg_critic_target");
-    if (rc) return rc;
-    td_loss_finalize<<<1, 1024, 0, s>>>(part, nblk, B, loss);
-    return check_launch("agx_maddpg_critic_target loss");
-}
 
 extern "C" int agx_c51_project_loss_rows(const float *target_rows, const float *logp_rows, const float *rewards,
                                          const float *dones, const float *support, int64_t B, int64_t Z,

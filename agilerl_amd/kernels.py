@@ -238,19 +238,35 @@ def td_target(q_next_target, rewards, dones, gamma, q_next_online=None, double=F
     return y, g_q, loss
 
 
+def _critic_target(maddpg, q1, qn1, rewards, dones, gamma, q2=None, qn2=None):
+    """Shape checks, outputs and the launch of agx_maddpg_critic_target or
+    agx_td3_critic_target -> (y, dloss/dq1, dloss/dq2 | None, loss)."""
+    B = q1.shape[0]
+    f1, fn1, r, d = q1.reshape(-1), qn1.reshape(-1), rewards.reshape(-1), dones.reshape(-1)
+    f2, fn2 = (q2.reshape(-1), qn2.reshape(-1)) if q2 is not None else (None, None)
+    named = [(f1, "q" if maddpg else "q1"), (fn1, "q_next" if maddpg else "qn1"), (r, "rewards"), (d, "dones")]
+    for t, name in named + ([(f2, "q2"), (fn2, "qn2")] if q2 is not None else []):
+        _need(t, name, _f32, (B,))
+    dev = r.device
+    y, g1 = torch.empty(B, 1, dtype=_f32, device=dev), torch.empty(B, 1, dtype=_f32, device=dev)
+    g2 = torch.empty(B, 1, dtype=_f32, device=dev) if q2 is not None else None
+    loss = torch.empty(1, dtype=_f32, device=dev)
+    if maddpg:
+        ws = _ws(_lib.load().agx_td_workspace_bytes(B), dev)
+        _lib.call("agx_maddpg_critic_target", f1.data_ptr(), fn1.data_ptr(), r.data_ptr(), d.data_ptr(), B,
+                  float(gamma), y.data_ptr(), g1.data_ptr(), loss.data_ptr(), ws.data_ptr(), _lib.stream())
+    else:
+        ws = _ws(_lib.load().agx_td3_workspace_bytes(B), dev)
+        _lib.call("agx_td3_critic_target", f1.data_ptr(), _lib.ptr(f2), fn1.data_ptr(), _lib.ptr(fn2), r.data_ptr(),
+                  d.data_ptr(), B, float(gamma), y.data_ptr(), g1.data_ptr(), _lib.ptr(g2), loss.data_ptr(),
+                  ws.data_ptr(), _lib.stream())
+    return y, g1, g2, loss
+
+
 def maddpg_critic_target(q, q_next, rewards, dones, gamma):
     """-> (y (B,1), dloss/dq (B,1), loss (1,)) of MADDPG._learn_individual's
     critic step (maddpg.py:764-790) in one launch (+ the fixed-order loss sum)."""
-    B = q.shape[0]
-    qf, qn, r, d = (t.reshape(-1) for t in (q, q_next, rewards, dones))
-    for t, name in ((qf, "q"), (qn, "q_next"), (r, "rewards"), (d, "dones")):
-        _need(t, name, _f32, (B,))
-    y = torch.empty(B, 1, dtype=_f32, device=r.device)
-    g_q = torch.empty(B, 1, dtype=_f32, device=r.device)
-    loss = torch.empty(1, dtype=_f32, device=r.device)
-    ws = _ws(_lib.load().agx_td_workspace_bytes(B), r.device)
-    _lib.call("agx_maddpg_critic_target", qf.data_ptr(), qn.data_ptr(), r.data_ptr(), d.data_ptr(), B,
-              float(gamma), y.data_ptr(), g_q.data_ptr(), loss.data_ptr(), _lib.ptr(ws), _lib.stream())
+    y, g_q, _, loss = _critic_target(True, q, q_next, rewards, dones, gamma)
     return y, g_q, loss
 
 
@@ -280,24 +296,7 @@ def td3_critic_target(q1, qn1, rewards, dones, gamma, q2=None, qn2=None):
     (ddpg.py:457-461), in one launch (+ the fixed-order loss sums)."""
     if (q2 is None) != (qn2 is None):
         raise ValueError("q2 and qn2 go together (both None: the single-critic form)")
-    B = q1.shape[0]
-    q1f, qn1f, r, d = (t.reshape(-1) for t in (q1, qn1, rewards, dones))
-    named = [(q1f, "q1"), (qn1f, "qn1"), (r, "rewards"), (d, "dones")]
-    q2f = qn2f = None
-    if q2 is not None:
-        q2f, qn2f = q2.reshape(-1), qn2.reshape(-1)
-        named += [(q2f, "q2"), (qn2f, "qn2")]
-    for t, name in named:
-        _need(t, name, _f32, (B,))
-    y = torch.empty(B, 1, dtype=_f32, device=r.device)
-    g_q1 = torch.empty(B, 1, dtype=_f32, device=r.device)
-    g_q2 = torch.empty(B, 1, dtype=_f32, device=r.device) if q2 is not None else None
-    loss = torch.empty(1, dtype=_f32, device=r.device)
-    ws = _ws(_lib.load().agx_td3_workspace_bytes(B), r.device)
-    _lib.call("agx_td3_critic_target", q1f.data_ptr(), _lib.ptr(q2f), qn1f.data_ptr(), _lib.ptr(qn2f), r.data_ptr(),
-              d.data_ptr(), B, float(gamma), y.data_ptr(), g_q1.data_ptr(), _lib.ptr(g_q2), loss.data_ptr(),
-              ws.data_ptr(), _lib.stream())
-    return y, g_q1, g_q2, loss
+    return _critic_target(False, q1, qn1, rewards, dones, gamma, q2, qn2)
 
 
 def c51_project_loss(q_next_online, target_dist, logp_cur, actions, rewards, dones, support, v_min,

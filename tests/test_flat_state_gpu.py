@@ -27,9 +27,10 @@ def _batch(rng, B, obs_dim, n_act, per=True):
 
 def _torch_tail(monkeypatch):
     """Route learn() through the torch optimizer tail (no flat state)."""
-    from agilerl_amd.algorithms import dqn
+    from agilerl_amd.algorithms import dqn, evolvable
 
-    monkeypatch.setattr(dqn, "flat_state", lambda agent: None)
+    for module in (dqn, evolvable):  # learn()'s own look-ups and the mixin's step / soft update
+        monkeypatch.setattr(module, "flat_state", lambda agent, group=None: None)
 
 
 @pytest.mark.parametrize("sizes", [[(5, 7)], [(64, 64), (64, 4), (512, 512), (1, 1)],
@@ -71,7 +72,7 @@ def test_rainbow_flat_tail_matches_torch_tail(per, monkeypatch):
         assert abs(l1 - l2) <= 1e-5 * abs(l2) + 1e-7, (it, l1, l2)
         if per:
             np.testing.assert_allclose(p1, p2, rtol=1e-5, atol=1e-7)
-    assert a.__dict__.get("_flat") is not None and r.__dict__.get("_flat") is None
+    assert a.__dict__["_flat"].get("actor") is not None and not r.__dict__.get("_flat")
     for (k, x), y in zip(a.actor.named_parameters(), r.actor.parameters()):
         torch.testing.assert_close(x, y, rtol=1e-4, atol=5e-5, msg=lambda m: f"{k}: {m}")
         sa, sr = a.optimizer.state[x], r.optimizer.state[y]
@@ -205,7 +206,7 @@ def test_rainbow_cnn_update_replayed_from_graph_equals_eager(per, n_step, monkey
         assert l1 == l2, (it, l1, l2)
         if per:
             np.testing.assert_array_equal(p1, p2)
-    fs = a.__dict__["_flat"]
+    fs = a.__dict__["_flat"]["actor"]
     assert any(ent.graph is not None for ent in learn_graph._GRAPHS.get(fs, {}).values())  # replayed
     for (k, x), y in zip(a.actor.named_parameters(), r.actor.parameters()):
         assert torch.equal(x, y), k

@@ -137,6 +137,32 @@ def test_critic_target_matches_twin_formula(B, twin):
         assert torch.equal(g2_only, g2.reshape(-1))
 
 
+@pytest.mark.parametrize("B", [1, 257, 1025])
+def test_critic_target_entries_share_arithmetic(B):
+    """On clean inputs (no NaN, d in {0, 1}) agx_maddpg_critic_target and the
+    single-critic agx_td3_critic_target are the same computation bit for bit,
+    and the twin loss is the f32 sum of the two single-critic losses against
+    the twin's own y."""
+    from agilerl_amd import kernels as K
+
+    gamma = 0.97
+    c = lambda x: x.reshape(-1).cuda()  # noqa: E731
+    q, qn, r, d = _critic_inputs(B, True)
+    q, qn, r, d = [c(x) for x in q], [c(x) for x in qn], c(r), c(d)
+    y_m, g_m, loss_m = K.maddpg_critic_target(q[0], qn[0], r, d, gamma)
+    y_s, g_s, none, loss_s = K.td3_critic_target(q[0], qn[0], r, d, gamma)
+    assert none is None
+    assert torch.equal(y_m, y_s) and torch.equal(g_m, g_s) and torch.equal(loss_m, loss_s)
+
+    y_t, g1, g2, loss_t = K.td3_critic_target(q[0], qn[0], r, d, gamma, q2=q[1], qn2=qn[1])
+    q_min = torch.minimum(qn[0], qn[1])
+    y_1, g_1, _, loss_1 = K.td3_critic_target(q[0], q_min, r, d, gamma)
+    y_2, g_2, _, loss_2 = K.td3_critic_target(q[1], q_min, r, d, gamma)
+    assert torch.equal(y_1, y_t) and torch.equal(y_2, y_t)
+    assert torch.equal(g_1, g1) and torch.equal(g_2, g2)
+    assert loss_1.dtype == torch.float32 and torch.equal(loss_1 + loss_2, loss_t)
+
+
 # ---- learn against the twin ---------------------------------------------------------
 def _env(num_envs=8):
     from agilerl_amd.envs import SyntheticVecEnv
