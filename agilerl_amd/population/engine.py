@@ -197,13 +197,13 @@ class PopulationEngine:
         """target_kl: the reference draws one shuffle per epoch an agent
         actually runs; re-advance the global stream from the generation's
         start by exactly those, over the global population (every rank
-        replays the same re-advance; see PPOPopulation)."""
+        replays the same re-advance; see population/perms.py)."""
         pops = [g.pop for g in self.groups]
         if self._gen_state is None or all(p.target_kl is None for p in pops):
             return
         ran_local = [None] * self.P
         for g in self.groups:
-            rows = [t.cpu().numpy() for t in g.pop._gen_ran]
+            rows = g.pop.orders.generation_epochs_run()
             for r, slot in enumerate(g.slots):
                 ran_local[slot] = [int(x[r]) for x in rows]
         if self.world > 1:

@@ -42,8 +42,8 @@ import torch
 
 from .. import _lib
 from .. import kernels as K
-from ..rng import numpy_shuffle_perms, numpy_shuffle_perms_shard
 from .nets import ActorCriticSpec, categorical
+from .perms import MinibatchOrders
 
 
 class _PPOLossFn(torch.autograd.Function):
@@ -138,7 +138,6 @@ class PPOPopulation:
         # refresh the other shards' entries after a mutation)
         self.global_epochs = [self.update_epochs] * self.global_P
         self.global_batch_max = None
-        self._shard_scratch: dict = {}
         self.act_counter = 0
         self._desc = None
         self._gdesc = None
@@ -148,21 +147,8 @@ class PPOPopulation:
         self.learn_steps = 0
         self.rollout_id = 0
         self.prefetch_perms = os.environ.get("AGX_PREFETCH_PERMS", "1") != "0"
-        self._perm_next = None
-        self._perm_stream = None
-        self._perm_host = None
-        self._perm_k = 0
+        self.orders = MinibatchOrders(self)  # which permutation the next learn() gets (perms.py)
         self._gae_launch = None
-        # target-KL runs: numpy state before the current learn's shuffles, and
-        # the correction owed to the global stream once its epochs_run is known
-        self._perm_drawn_state = None
-        self._kl_pending = None
-        # a generation's shuffles drawn ahead by the population engine, agent by
-        # agent (set_generation_perms): [K, E, P, S], learn k reads row k
-        self._gen_block = None
-        self._gen_block_d = None
-        self._gen_k = 0
-        self._gen_ran: list[torch.Tensor] = []
 
     # ------------------------------------------------------------------ #
     def _alloc_rollout(self):
@@ -321,64 +307,18 @@ class PPOPopulation:
 
             loss = fused_learn(self, skip_if_set=skip_if_set)
             self.last_kl = self._fused.kl
-            self._record_kl_pending(self._fused.epochs_run)
+            self.orders.report(self._fused.epochs_run)
             # with target_kl the next learn's shuffles depend on this one's stops
             if prefetch and self.prefetch_perms and self.target_kl is None:
                 self.prefetch_permutations()
             return loss
         loss = self._learn_torch()
-        self._record_kl_pending(self.last_epochs_run)
+        self.orders.report(self.last_epochs_run)
         return loss
 
-    # ------------------------------------------------------------------ #
-    # target_kl and the global numpy stream (ppo.py:836-842, 917-918)
-    #
-    # The reference's agents learn one after another, each drawing one
-    # np.random.shuffle per epoch it actually runs; an agent that stops early
-    # on target_kl draws fewer.  The engine draws every agent's E shuffles
-    # before the learn (all agents run at once), so after an early stop:
-    #   * agents after the first early-stopping agent learn from shuffles
-    #     that are shifted against the reference's (agent p's would start at
-    #     shuffle sum(epochs_run[:p]), which is only known once every agent
-    #     before it has finished — a serial dependency the population breaks);
-    #   * the GLOBAL stream is put back in step: once the learn's epochs_run
-    #     is known, the state is rewound to before the draw and advanced by
-    #     exactly sum(epochs_run) shuffles, the reference's count, so every
-    #     later consumer (tournament and mutation draws, the next learn) sees
-    #     the state the reference would.
-    # Without target_kl every agent runs all its epochs and both are exact.
-    def _record_kl_pending(self, epochs_run) -> None:
-        if self.target_kl is not None and self._gen_block is not None:
-            self._gen_ran.append(torch.as_tensor(epochs_run).detach().clone())  # the engine re-syncs the stream
-            return
-        if self.target_kl is None or self.perm_source != "numpy" or self._perm_drawn_state is None:
-            return
-        planned = list(self.agent_epochs) if self.heterogeneous else [self.update_epochs] * self.P
-        ev = None
-        if self.device.type == "cuda":
-            ev = torch.cuda.Event()
-            ev.record()
-        self._kl_pending = (self._perm_drawn_state, planned, epochs_run, ev)
-        self._perm_drawn_state = None
-
     def sync_numpy_stream(self) -> None:
-        """Apply the correction a target-KL learn owes the global numpy stream
-        (waits for that learn's epochs_run; see above).  Called before anything
-        draws from the stream: the next permutation draw, tournament and
-        mutation draws (discard_prefetch)."""
-        if self._kl_pending is None:
-            return
-        state, planned, epochs_run, ev = self._kl_pending
-        self._kl_pending = None
-        if ev is not None:
-            ev.synchronize()
-        ran = [int(x) for x in torch.as_tensor(epochs_run).cpu().tolist()]
-        if ran == planned:
-            return
-        np.random.set_state(state)
-        total = int(sum(ran))
-        if total:
-            numpy_shuffle_perms(1, total, self.S)
+        """Apply the correction a target-KL learn owes the global numpy stream."""
+        self.orders.settle()
 
     def check_errors(self) -> None:
         """Raise AgxError if a fused learn() since the last check left an agent's
@@ -479,9 +419,7 @@ class PPOPopulation:
         if max(self.agent_epochs) != self.update_epochs:
             self.update_epochs = max(self.agent_epochs)
             self._fused = None      # workspace is sized by the epochs
-            self._perm_host = None  # pinned [E, P, S] staging
-            self.discard_prefetch()
-            self._perm_next = None
+            self.orders.epochs_changed()
         self._hetero = not (len(set(self.agent_batch)) == 1 and len(set(self.agent_epochs)) == 1
                             and len(set(self.agent_ent)) == 1)
 
@@ -507,108 +445,14 @@ class PPOPopulation:
         b = self.batch_size
         return [(s, min(s + b, self.S)) for s in range(0, self.S, b)]
 
+    # minibatch orders: MinibatchOrders (perms.py) owns the draws and the numpy stream
     def permutations(self) -> torch.Tensor:
-        """[E, P, S] int64 per-agent minibatch orders for the next learn():
-        numpy's global np.random.shuffle stream (default, ppo.py:836-842) or a
-        device draw.  Returns the draw made ahead by prefetch_permutations()
-        if there is one (the same draw, in the same order, as drawing here)."""
-        if self._perm_next is not None:
-            perms, ev, state = self._perm_next[:3]
-            self._perm_next = None
-            self._perm_drawn_state = state
-            main = torch.cuda.current_stream()
-            if ev is not None:
-                main.wait_event(ev)
-            perms.record_stream(main)  # (a block row: the block stays allocated until this stream is past it)
-            return perms
-        if self.perm_source == "numpy" and self._gen_block_d is not None:
-            perms = self._next_block_row()
-            perms.record_stream(torch.cuda.current_stream(self.device))
-            return perms
-        if self.perm_source == "numpy":
-            host = self._host_perm_buffer()
-            self._perm_drawn_state = self._fill_numpy_perms(host.numpy())
-            perms = host.to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._perm_host[self._perm_k ^ 1][1] = ev
-            return perms
-        keys = torch.rand(self.update_epochs, self.P, self.S, generator=self.gen, device=self.device)
-        return torch.argsort(keys, dim=-1)
+        """[E, P, S] int64 per-agent minibatch orders for the next learn()."""
+        return self.orders.permutations()
 
     def set_generation_perms(self, block: np.ndarray | None) -> None:
-        """The population engine's draw of this population's shuffles for a
-        whole generation ([K, E, P, S] int64: learn k of local agent p visits
-        block[k, e, p] in epoch e), drawn agent by agent over the global
-        population as the reference's agents learn one after another
-        (train_on_policy.py:210-248 -> ppo.py:836-842).  None: draw per learn."""
-        self.discard_prefetch()
-        if block is not None:
-            if block.ndim != 4 or block.shape[1:] != (self.update_epochs, self.P, self.S):
-                raise ValueError(f"generation shuffles {block.shape}, expected [K, {self.update_epochs}, {self.P}, "
-                                 f"{self.S}]")
-        self._gen_block, self._gen_k, self._gen_ran = block, 0, []
-        # the whole block in HBM once (one copy at the generation's start, before
-        # any launch): each learn then takes its row without host work
-        self._gen_block_d = (torch.from_numpy(block).to(self.device)
-                             if block is not None and self.device.type == "cuda" else None)
-
-    def _next_block_row(self) -> torch.Tensor:
-        """The next learn's [E, P, S] row of the generation block in HBM."""
-        if self._gen_k >= self._gen_block.shape[0]:
-            raise RuntimeError("more learns than the generation's shuffles were drawn for")
-        row = self._gen_block_d[self._gen_k]
-        self._gen_k += 1
-        return row
-
-    def _fill_numpy_perms(self, out: np.ndarray):
-        """The next learn's [E, P, S] numpy-stream permutations into ``out``;
-        -> the global numpy state before the draw (None when they come from
-        the engine's generation block, which owns the stream)."""
-        if self._gen_block is not None:
-            if self._gen_k >= self._gen_block.shape[0]:
-                raise RuntimeError("more learns than the generation's shuffles were drawn for")
-            np.copyto(out, self._gen_block[self._gen_k])
-            self._gen_k += 1
-            return None
-        self.sync_numpy_stream()
-        state = np.random.get_state(legacy=True)
-        self._draw_numpy_perms(out)
-        return state
-
-    def _draw_numpy_perms(self, out: np.ndarray) -> None:
-        """[E, P, S] from the global numpy stream: this shard's agents' shuffles
-        in the global agent order (rng.py).  An agent with fewer epochs than E
-        draws fewer shuffles; its rows beyond get arange(S), so no row of the
-        (reused, uninitialised pinned) buffer ever holds an out-of-range index
-        — the gather prologue and the PyTorch learner index with every row."""
-        if self.global_P == self.P:
-            numpy_shuffle_perms(self.P, self.update_epochs, self.S, out=out,
-                                epochs_per_agent=self.agent_epochs if self.heterogeneous else None)
-        else:
-            eg = list(self.global_epochs)
-            eg[self.agent_offset:self.agent_offset + self.P] = self.agent_epochs
-            numpy_shuffle_perms_shard(out, self.agent_offset, self.global_P, eg, self._shard_scratch)
-        E = out.shape[0]
-        for p, e in enumerate(self.agent_epochs):
-            if e < E:
-                out[e:, p, :] = np.arange(self.S, dtype=np.int64)
-
-    def _host_perm_buffer(self) -> torch.Tensor:
-        """One of two pinned [E, P, S] int64 host buffers, alternating (the H2D
-        copy that last read a buffer finished long before it is reused: it
-        precedes a whole learn() on the stream; checked by its event)."""
-        self._alloc_perm_host()
-        slot = self._perm_host[self._perm_k]
-        self._perm_k ^= 1
-        if slot[1] is not None:
-            slot[1].synchronize()
-        return slot[0]
-
-    def _alloc_perm_host(self) -> None:
-        if self._perm_host is None:
-            shape = (self.update_epochs, self.P, self.S)
-            self._perm_host = [[torch.empty(shape, dtype=torch.int64, pin_memory=True), None] for _ in range(2)]
+        """A generation's shuffles drawn ahead ([K, E, P, S]); None: draw per learn."""
+        self.orders.set_generation_perms(block)
 
     def prepare_learn(self) -> None:
         """Do now what the next learn() would otherwise do on first use: build
@@ -623,64 +467,17 @@ class PPOPopulation:
 
             if learner_stale(self):
                 self._fused = make_learner(self)
-        if self.perm_source == "numpy":
-            self._alloc_perm_host()
+        self.orders.alloc_staging()
         if self.prefetch_perms:
             self.prefetch_permutations()
 
     def prefetch_permutations(self) -> None:
-        """Draw the next learn's permutations now, off the critical path:
-        device mode enqueues rand + a radix sort on a side stream (beside the
-        learner and the next rollout); numpy mode runs the native host shuffle
-        (~0.5 ms of host time while the GPU learns) and an async H2D copy.
-        Anything else that draws from the global numpy generator in between
-        (tournament selection, mutations) must call discard_prefetch() first,
-        so the draws stay in the reference's order."""
-        if self._perm_next is not None or self.device.type != "cuda":
-            return
-        if self._gen_block is not None and self._gen_k >= self._gen_block.shape[0]:
-            return  # the generation's learns are all served: the next block is drawn with the next generation
-        if self._perm_stream is None:
-            self._perm_stream = torch.cuda.Stream(device=self.device)
-        side = self._perm_stream
-        state = None
-        from_block = False
-        if self.perm_source == "numpy" and self._gen_block_d is not None:
-            self._perm_next = (self._next_block_row(), None, None, True)
-            return
-        if self.perm_source == "numpy":
-            # waits for a target-KL learn's epochs_run (before any rollout launch)
-            from_block = self._gen_block is not None
-            host = self._host_perm_buffer()
-            state = self._fill_numpy_perms(host.numpy())
-            with torch.cuda.stream(side):
-                perms = host.to(self.device, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            self._perm_host[self._perm_k ^ 1][1] = ev
-        else:
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                keys = torch.rand(self.update_epochs, self.P, self.S, generator=self.gen, device=self.device)
-                perms = torch.argsort(keys, dim=-1)
-                ev = torch.cuda.Event()
-                ev.record(side)
-        self._perm_next = (perms, ev, state, from_block)
+        """Draw the next learn's permutations now, off the critical path."""
+        self.orders.prefetch()
 
     def discard_prefetch(self) -> None:
-        """Undo a prefetched numpy draw: the global numpy state goes back to
-        before it, so the next consumer of the stream draws what it would have
-        drawn without the prefetch (the permutations are re-drawn later)."""
-        if self._perm_next is not None and len(self._perm_next) > 3 and self._perm_next[3]:
-            self._perm_next = None  # a generation-block row: served again by the next permutations()
-            self._gen_k -= 1
-            return
-        if self._perm_next is None or self._perm_next[2] is None:
-            self.sync_numpy_stream()
-            return  # nothing drawn ahead from numpy (device draws use the pop's own generator)
-        perms, ev, state = self._perm_next[:3]
-        self._perm_next = None
-        np.random.set_state(state)
+        """Undo a prefetched numpy draw (and settle the global numpy stream)."""
+        self.orders.discard()
 
     def _learn_torch(self, perms: torch.Tensor | None = None) -> torch.Tensor:
         """Plain-PyTorch fp32 autograd learner over the stacked networks (HIP

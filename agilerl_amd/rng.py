@@ -12,7 +12,7 @@
   later agent's minibatch order; the population draws all agents' shuffles
   before its (parallel) learn, so those later agents' orders differ from the
   reference's, while the global state itself is re-synchronised to the
-  reference's count afterwards (PPOPopulation.sync_numpy_stream).
+  reference's count afterwards (ShuffleStream.settle, population/perms.py).
 """
 
 from __future__ import annotations

@@ -271,14 +271,14 @@ def test_heterogeneous_epoch_permutation_rows_stay_in_range():
 
     from types import SimpleNamespace
 
-    from agilerl_amd.population.ppo_pop import PPOPopulation
+    from agilerl_amd.population.perms import draw_host_perms
 
-    # the host-side state _draw_numpy_perms reads (a population of 3, S = 32,
-    # agent 1 mutated to 1 update epoch)
+    # the host-side inputs of the draw (a population of 3, S = 32, agent 1
+    # mutated to 1 update epoch)
     pop = SimpleNamespace(P=3, global_P=3, S=32, update_epochs=3, agent_epochs=[3, 1, 3], heterogeneous=True)
-    out = np.full((3, 3, pop.S), -7, dtype=np.int64)  # garbage a reused buffer may hold
+    out = np.full((pop.update_epochs, pop.P, pop.S), -7, dtype=np.int64)  # garbage a reused buffer may hold
     np.random.seed(0)
-    PPOPopulation._draw_numpy_perms(pop, out)
+    draw_host_perms(out, pop.agent_epochs, pop.heterogeneous, pop.global_P)
     assert out.min() >= 0 and out.max() < pop.S
     assert np.array_equal(out[1:, 1], np.tile(np.arange(pop.S), (2, 1)))
     for e in range(3):

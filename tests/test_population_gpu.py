@@ -542,6 +542,38 @@ def test_permutation_prefetch_keeps_the_draw_sequence(monkeypatch, source):
         assert torch.equal(a, b)
 
 
+def test_generation_block_rows_survive_a_discarded_prefetch():
+    """A generation's block of K = 3 learns: a row drawn ahead and discarded
+    is served again, the rows come in order without touching the global numpy
+    stream, a fourth learn raises, and clearing the block returns to one draw
+    per learn from the global stream."""
+    from agilerl_amd.rng import numpy_shuffle_perms
+
+    pop = _pop(P=2, N=8, learn_step=16, batch=16, epochs=2)
+    assert pop.perm_source == "numpy" and (pop.update_epochs, pop.P, pop.S) == (2, 2, 16)
+    np.random.seed(8)
+    block = numpy_shuffle_perms(3 * 2, 2, 16).reshape(2, 3, 2, 16).transpose(1, 0, 2, 3).copy()  # [K, E, P, S]
+    np.random.seed(31)
+    before = np.random.get_state(legacy=True)
+    pop.set_generation_perms(block)
+    pop.prefetch_permutations()
+    pop.discard_prefetch()
+    for k in range(3):
+        assert np.array_equal(pop.permutations().cpu().numpy(), block[k]), k
+    with pytest.raises(RuntimeError, match="more learns than the generation's shuffles were drawn for"):
+        pop.permutations()
+    now = np.random.get_state(legacy=True)
+    assert np.array_equal(now[1], before[1]) and now[2:] == before[2:]
+
+    pop.set_generation_perms(None)
+    got = pop.permutations().cpu().numpy()
+    after = np.random.get_state(legacy=True)
+    np.random.seed(31)
+    assert np.array_equal(got, numpy_shuffle_perms(2, 2, 16))
+    want = np.random.get_state(legacy=True)
+    assert np.array_equal(after[1], want[1]) and after[2:] == want[2:]
+
+
 def test_env_exception_mid_rollout_leaves_learner_state_untouched(monkeypatch):
     """The pipelined iteration queues GAE and the learner behind the
     persistent rollout before the host paces it.  An env that raises mid
