@@ -23,7 +23,7 @@ _F = ctypes.c_float
 _INT = ctypes.c_int
 _SZ = ctypes.c_size_t
 
-# name -> (restype, argtypes); mirrors include/agx.h one-to-one
+# name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -55,6 +55,11 @@ SIGNATURES = {
                                              _D, _P, _P]),
     "agx_ppo_act_graph": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
                                  _P, _I, _P, _P, _P, _P]),
+    # include/agx_gauss.h: PPO for Box actions
+    "agx_ppo_act_gauss_graph_workspace_bytes": (_SZ, [_P, _I, _I]),
+    "agx_ppo_act_gauss_graph": (_INT, [_P, _I, _I, _I, _P, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
+                                       _P, _I, _P, _P, _P, _P, _P, _P]),
+    "agx_ppo_gauss_loss_fwd_bwd": (_INT, [_P] * 9 + [_I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "agx_ppo_learn": (_INT, [_P, _P, _P, _P]),
     "agx_ppo_act": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                            _I, _P, _P, _P]),

@@ -8,7 +8,8 @@ Differences of form: classes and spaces are not pickled (the file holds only
 tensors, numbers, strings, lists and dicts), so it is written by
 ``torch.save`` and read back with ``torch.load(weights_only=True)`` — nothing
 in a checkpoint is executed on load.  Spaces are stored as
-``{"obs_shape", "n_actions"}`` for ``load``.
+``{"obs_shape", "n_actions"}`` (a Box action space: ``{"obs_shape",
+"action_low", "action_high"}``, its bounds as flat lists) for ``load``.
 
 Checkpoints the reference itself wrote (dill-pickled agents, spaces and
 registries) are read by ``refckpt.read_reference`` — the same weights-only
@@ -26,7 +27,7 @@ import torch
 HP_NAMES = ("index", "batch_size", "lr", "learn_step", "gamma", "tau", "double", "beta", "prior_eps", "num_atoms",
             "v_min", "v_max", "noise_std", "n_step", "combined_reward", "gae_lambda", "clip_coef", "ent_coef",
             "vf_coef", "max_grad_norm", "target_kl", "update_epochs", "num_envs", "net_config", "scores", "fitness",
-            "steps", "mut", "normalize_images")
+            "steps", "mut", "normalize_images", "action_std_init")
 
 
 def _plain(v: Any) -> Any:
@@ -47,7 +48,12 @@ def checkpoint_dict(agent, modules: dict[str, dict[str, torch.Tensor]], optimize
     out["algo"] = agent.algo
     out["agilerl_version"] = "agx"
     if spaces:
-        out["spaces"] = {"obs_shape": list(agent.observation_space.shape), "n_actions": int(agent.action_space.n)}
+        out["spaces"] = {"obs_shape": list(agent.observation_space.shape)}
+        if hasattr(agent.action_space, "n"):
+            out["spaces"]["n_actions"] = int(agent.action_space.n)
+        else:  # Box actions (1-D)
+            out["spaces"]["action_low"] = [float(x) for x in agent.action_space.low]
+            out["spaces"]["action_high"] = [float(x) for x in agent.action_space.high]
     out["network_info"] = {
         "network_names": list(modules),
         "modules": {f"{k}_state_dict": _plain(v) for k, v in modules.items()},
@@ -91,7 +97,12 @@ def spaces(ckpt: dict):
     from ..envs import Box, Discrete
 
     s = ckpt["spaces"]
-    return Box(-float("inf"), float("inf"), tuple(s["obs_shape"])), Discrete(s["n_actions"])
+    obs = Box(-float("inf"), float("inf"), tuple(s["obs_shape"]))
+    if "n_actions" not in s:
+        act = Box(0.0, 0.0, (len(s["action_low"]),))
+        act.low[:], act.high[:] = s["action_low"], s["action_high"]
+        return obs, act
+    return obs, Discrete(s["n_actions"])
 
 
 def group_state_dicts(agent) -> tuple[dict, dict]:

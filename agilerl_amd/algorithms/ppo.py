@@ -1,5 +1,5 @@
-"""Drop-in ``PPO`` (agilerl/algorithms/ppo.py:108-1290) for discrete-action
-MLP actor-critics, backed by the HBM population engine.
+"""Drop-in ``PPO`` (agilerl/algorithms/ppo.py:108-1290) for MLP actor-critics
+over Discrete or Box action spaces, backed by the HBM population engine.
 
 A ``PPO`` object is a *view* of one row of a :class:`PPOPopulation` (its
 parameters, Adam state and rollout SoA live in HBM, stacked with the other
@@ -8,14 +8,16 @@ one population and P views, so ``train_on_policy`` can run the whole
 population with one launch per kernel; a standalone ``PPO(...)`` owns a
 population of one.
 
-Supported: Discrete action spaces, Box observations, ``net_config`` with
+Supported: Discrete action spaces (and 1-D Box action spaces of up to 32
+dimensions with vector observations: a diagonal Gaussian with a learned
+``log_std`` started at ``action_std_init``), Box observations, ``net_config`` with
 ``encoder_config`` / ``head_config`` MLP ``hidden_size`` lists and
 ``latent_dim`` (the reference's defaults: encoder [64, 64] -> latent 32,
 actor head [32], critic head [16] unless ``head_config`` is given,
 ppo.py:286-320 via networks/base.py and networks/actors.py),
 LayerNorm on, shared encoder.  ``get_action`` / ``learn`` / ``test`` keep the
 reference's signatures and return types; recurrent policies,
-continuous actions and custom ``actor_network`` objects raise
+squashed Box outputs and custom ``actor_network`` objects raise
 NotImplementedError (outside the hot path).  ``get_action(obs, action_mask)``
 applies the reference's legal-action masks (logits of illegal actions ->
 -1e8, ppo.py:529-565); ``target_kl`` stops an agent's epochs early exactly
@@ -91,19 +93,37 @@ def _limits(cfg, config_default: bool) -> tuple:
             int(get("min_mlp_nodes", d[2])), int(get("max_mlp_nodes", d[3])))
 
 
+def _box_action_space(action_space) -> bool:
+    return not hasattr(action_space, "n") and hasattr(action_space, "low") and hasattr(action_space, "high")
+
+
 def spec_from_net_config(observation_space, action_space, net_config: dict | None, normalize_images: bool = True,
-                         share_encoders: bool = True):
+                         share_encoders: bool = True, action_std_init: float = 0.0):
     """The networks ppo.py:286-320 builds, as the reference's defaults fill
     them in: no encoder_config -> get_default_encoder_config's MlpNetConfig
     [64, 64] (utils/evolvable_networks.py:168-217); latent_dim 32 with limits
     8 / 128 (networks/base.py:191-194); no head_config -> actor head
     MlpNetConfig [32] (networks/actors.py:300-303), critic head [16]
     (ppo.py:292-300)."""
-    if not hasattr(action_space, "n"):
-        raise NotImplementedError("agx PPO supports Discrete action spaces")
+    box = _box_action_space(action_space)
+    if not hasattr(action_space, "n") and not box:
+        raise NotImplementedError("agx PPO supports Discrete and Box action spaces")
     net_config = dict(net_config or {})
     from ..networks.base import is_image_space
 
+    if box:
+        # StochasticActor over a Box space (networks/actors.py:296-336): the head's
+        # output_activation is forced to None whatever head_config says (the spec's
+        # output layers are plain Linear, so there is nothing to switch off)
+        if net_config.get("squash_output", False):
+            # ppo.py:561, 601: a squashed policy's entropy is -log_prob.mean(), another loss
+            raise NotImplementedError("agx PPO: squash_output=True is not supported for Box action spaces")
+        if len(action_space.shape) != 1:
+            raise NotImplementedError(f"agx PPO: Box action spaces are 1-D (got shape {tuple(action_space.shape)})")
+        if not 1 <= int(action_space.shape[0]) <= 32:
+            raise NotImplementedError(f"agx PPO: Box actions of 1..32 dimensions (got {int(action_space.shape[0])})")
+        if is_image_space(observation_space):
+            raise NotImplementedError("agx PPO: Box action spaces with image observations")
     if is_image_space(observation_space):
         if not share_encoders:
             raise NotImplementedError("agx image PPO: the shared CNN encoder (share_encoders=True)")
@@ -118,11 +138,20 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
     enc_lim = _limits(enc_cfg, enc_cfg is None or not isinstance(enc_cfg, dict))
     head_lim = _limits(head, head is None or not isinstance(head, dict))
     lat_lim = (int(net_config.get("min_latent_dim", 8)), int(net_config.get("max_latent_dim", 128)))
-    return ActorCriticSpec(obs_dim=obs_dim, n_actions=int(action_space.n), encoder_hidden=enc, latent_dim=latent,
-                           actor_hidden=actor_hidden, critic_hidden=critic_hidden, encoder_limits=enc_lim,
-                           actor_limits=head_lim, critic_limits=head_lim if head is not None else (1, 3, 16, 500),
-                           latent_limits=lat_lim, share_encoders=bool(share_encoders),
-                           encoder_name="shared_encoder" if share_encoders else "actor_encoder")
+    kw = dict(obs_dim=obs_dim, encoder_hidden=enc, latent_dim=latent, actor_hidden=actor_hidden,
+              critic_hidden=critic_hidden, encoder_limits=enc_lim, actor_limits=head_lim,
+              critic_limits=head_lim if head is not None else (1, 3, 16, 500), latent_limits=lat_lim,
+              share_encoders=bool(share_encoders), encoder_name="shared_encoder" if share_encoders else "actor_encoder")
+    if box:
+        from ..population.nets import GaussianActorCriticSpec
+
+        A = int(action_space.shape[0])
+        low = np.broadcast_to(np.asarray(action_space.low, dtype=np.float32), (A,))
+        high = np.broadcast_to(np.asarray(action_space.high, dtype=np.float32), (A,))
+        return GaussianActorCriticSpec(n_actions=A, action_std_init=float(action_std_init),
+                                       action_low=tuple(float(x) for x in low),
+                                       action_high=tuple(float(x) for x in high), **kw)
+    return ActorCriticSpec(n_actions=int(action_space.n), **kw)
 
 
 class PPO:
@@ -145,6 +174,7 @@ class PPO:
         self.share_encoders = bool(share_encoders)
         assert isinstance(batch_size, int) and batch_size >= 1, "Batch size must be an integer greater than or equal to one."
         assert lr > 0, "Learning rate must be greater than zero."
+        assert action_std_init >= 0, "Action standard deviation must be greater than or equal to zero."
         assert isinstance(learn_step, int) and learn_step >= 1, "Learn step rate must be an integer greater than or equal to one."
         from ..hpo.registry import MutationRegistry
 
@@ -156,6 +186,10 @@ class PPO:
         self.clip_coef, self.vf_coef = clip_coef, vf_coef
         self.max_grad_norm, self.target_kl = max_grad_norm, target_kl
         self.num_envs = num_envs
+        self.action_std_init = action_std_init
+        # the reference's training flag (set_training_mode): off while test() acts, when a
+        # Box policy's actions are clipped to the bounds for the env (ppo.py:604-614)
+        self.training = True
         # hyperparameters the HPO may mutate (core/base.py:301, registry.py:190-242)
         self.registry = MutationRegistry(hp_config)
         self.device = torch.device(device)
@@ -164,7 +198,7 @@ class PPO:
         self.steps: list[int] = [0]
         if _population is None:
             spec = spec_from_net_config(observation_space, action_space, net_config, normalize_images,
-                                        share_encoders=share_encoders)
+                                        share_encoders=share_encoders, action_std_init=action_std_init)
             _population = PPOPopulation(spec, 1, num_envs, learn_step=learn_step, batch_size=batch_size, lr=lr,
                                         gamma=gamma, gae_lambda=gae_lambda, clip_coef=clip_coef, ent_coef=ent_coef,
                                         vf_coef=vf_coef, max_grad_norm=max_grad_norm, update_epochs=update_epochs,
@@ -388,7 +422,7 @@ class PPO:
         obs_space, act_space = C.spaces(ck)
         kw = {k: ck[k] for k in ("batch_size", "lr", "learn_step", "gamma", "gae_lambda", "clip_coef", "ent_coef",
                                  "vf_coef", "max_grad_norm", "target_kl", "update_epochs", "num_envs",
-                                 "net_config", "index") if k in ck}
+                                 "net_config", "index", "action_std_init") if k in ck}
         agent = cls(obs_space, act_space, device=device, **kw)
         agent.load_checkpoint(path)
         return agent
@@ -407,6 +441,8 @@ class PPO:
         if action_mask is not None:
             mask = torch.as_tensor(np.asarray(action_mask), device=self.device).reshape(n, pop.spec.n_actions)
             mask = (mask != 0).to(torch.uint8).contiguous()
+        if pop.gaussian:
+            return self._get_action_gauss(o, action_mask)
         out = dict(actions=torch.empty(n, dtype=torch.int64, device=self.device),
                    log_probs=torch.empty(n, device=self.device), values=torch.empty(n, device=self.device),
                    entropy=torch.empty(n, device=self.device))
@@ -442,6 +478,34 @@ class PPO:
                       out["actions"].data_ptr(), out["log_probs"].data_ptr(), out["values"].data_ptr(),
                       out["entropy"].data_ptr(), 0, None, None, _lib.stream())
         return tuple(out[k].cpu().numpy() for k in ("actions", "log_probs", "entropy", "values"))
+
+    def _get_action_gauss(self, o: torch.Tensor, action_mask):
+        """get_action of a Box policy: one agx_ppo_act_gauss_graph launch on
+        this agent's row -> float actions [n, A]; outside training the
+        returned actions are clipped to the bounds (ppo.py:604-614), the
+        log-prob stays the unclipped sample's."""
+        if action_mask is not None:
+            raise ValueError("action masks apply to Discrete action spaces")
+        pop = self.population
+        n, A = o.shape[0], pop.spec.n_actions
+        gdesc = pop.gauss_descriptor()
+        self._counter += 1
+        ws = getattr(self, "_act_graph_ws", None)
+        if ws is None or ws[0] is not gdesc or ws[1] < n:
+            nbytes = _lib.load().agx_ppo_act_gauss_graph_workspace_bytes(ctypes.byref(gdesc), 1, n)
+            ws = self._act_graph_ws = (gdesc, n, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
+        actions = torch.empty(n, A, device=self.device)
+        logp, value, ent = (torch.empty(n, device=self.device) for _ in range(3))
+        clip = None if self.training else pop.action_clip()
+        env_copy = torch.empty(n, A, device=self.device) if clip is not None else None
+        _lib.call("agx_ppo_act_gauss_graph", ctypes.byref(gdesc), pop.spec.log_std, 1, n,
+                  pop.params.data[self.row].data_ptr(), o.data_ptr(), 0, 1,
+                  pop.act_seed + 7919 * pop.agent_ids[self.row], (1 << 40) + self._counter, actions.data_ptr(),
+                  logp.data_ptr(), value.data_ptr(), ent.data_ptr(), 0, _lib.ptr(env_copy),
+                  _lib.ptr(clip[0]) if clip else None, _lib.ptr(clip[1]) if clip else None, None, ws[2].data_ptr(),
+                  _lib.stream())
+        a = env_copy if env_copy is not None else actions
+        return tuple(t.cpu().numpy() for t in (a, logp, ent, value))
 
     @property
     def rollout_buffer(self) -> "AgentRolloutBuffer":
@@ -479,7 +543,7 @@ class PPO:
         and Adam (agx_clip_adam on this agent's row); target_kl checked after
         each epoch on the last minibatch's approx_kl.  -> mean_loss /
         (num_samples * update_epochs)."""
-        from ..population.nets import categorical
+        from ..population.nets import categorical, gaussian
 
         if not experiences:
             raise ValueError("Experiences must be provided when use_rollout_buffer is False")
@@ -498,7 +562,9 @@ class PPO:
 
         obs, actions, log_probs, rewards, dones, values, next_obs, next_done = experiences
         obs = stack(obs, torch.float32)
-        actions, log_probs = stack(actions, torch.int64), stack(log_probs, torch.float32)
+        gauss = pop.gaussian  # a Box policy: float actions [.., A]
+        actions = stack(actions, torch.float32 if gauss else torch.int64)
+        log_probs = stack(log_probs, torch.float32)
         rewards, dones, values = stack(rewards, torch.float32), stack(dones, torch.float32), stack(values, torch.float32)
         next_obs, next_done = stack(next_obs, torch.float32), stack(next_done, torch.float32)
         T = rewards.shape[0]
@@ -515,7 +581,8 @@ class PPO:
                 adv[t] = last = delta + self.gamma * self.gae_lambda * nnt * last
             returns = adv + values
         obs_f = obs.reshape(-1, spec.obs_dim)
-        act_f, lp_f, adv_f = actions.reshape(-1), log_probs.reshape(-1), adv.reshape(-1)
+        act_f = actions.reshape(-1, spec.n_actions) if gauss else actions.reshape(-1)
+        lp_f, adv_f = log_probs.reshape(-1), adv.reshape(-1)
         ret_f, val_f = returns.reshape(-1), values.reshape(-1)
         n = obs_f.shape[0]
         idxs = np.arange(n)
@@ -533,8 +600,11 @@ class PPO:
                 sel = torch.as_tensor(mb, device=self.device)
                 w = pop.params.data[r:r + 1].detach().clone().requires_grad_(True)
                 logits, value = spec.forward(w, obs_f[sel].unsqueeze(0))
-                logp_all, entropy = categorical(logits[0])
-                logp = logp_all.gather(-1, act_f[sel].unsqueeze(-1)).squeeze(-1)
+                if gauss:
+                    logp, entropy = gaussian(logits[0], spec.log_std_view(w), act_f[sel])
+                else:
+                    logp_all, entropy = categorical(logits[0])
+                    logp = logp_all.gather(-1, act_f[sel].unsqueeze(-1)).squeeze(-1)
                 logratio = logp - lp_f[sel]
                 ratio = logratio.exp()
                 with torch.no_grad():
@@ -559,8 +629,15 @@ class PPO:
              vectorized: bool = True, callback=None) -> float:
         """Mean score over ``loop`` passes in which every env finishes one
         episode (ppo.py:1113-1289); appends to ``self.fitness``."""
-        rewards = []
         num_envs = env.num_envs if hasattr(env, "num_envs") and vectorized else 1
+        self.training = False  # set_training_mode(False), ppo.py:1143: Box actions clipped to the bounds
+        try:
+            return self._test_loops(env, num_envs, max_steps, loop)
+        finally:
+            self.training = True  # ppo.py:1285
+
+    def _test_loops(self, env, num_envs: int, max_steps: int | None, loop: int) -> float:
+        rewards = []
         for _ in range(loop):
             obs, _info = env.reset()
             scores = np.zeros(num_envs)

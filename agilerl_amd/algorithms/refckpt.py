@@ -149,8 +149,14 @@ def _space_shapes(ck: dict) -> dict | None:
         return None
     shape = obs.attr("_shape")
     n = act.attr("n")
-    if shape is None or n is None:
+    if shape is None:
         return None
+    if n is None:  # a Box action space: its bounds
+        low, high = act.attr("low"), act.attr("high")
+        if low is None or high is None or np.ndim(low) != 1:
+            return None
+        return {"obs_shape": [int(s) for s in shape], "action_low": [float(x) for x in low],
+                "action_high": [float(x) for x in high]}
     return {"obs_shape": [int(s) for s in shape], "n_actions": int(n)}
 
 

@@ -767,8 +767,10 @@ struct GActArgs {
 // ---------------------------------------------------------------------------
 long long r4(long long x) { return (x + 3) & ~3ll; }
 
-// validate the layer list; fill the layer table and the per-agent scratch plan
-int plan_graph(const agx_ppo_graph *net, int64_t batch, GArgs &a) {
+// validate the layer list; fill the layer table and the per-agent scratch plan.
+// extra: floats of the parameter row that no layer owns (the Gaussian head's
+// log_std, agx_gauss.h); the layers and they cover the row exactly
+int plan_graph(const agx_ppo_graph *net, int64_t batch, GArgs &a, int extra = 0) {
     AGX_REQUIRE(net, "agx_ppo_graph: null graph");
     const int nl = net->n_layers;
     AGX_REQUIRE(nl >= 2 && nl <= kGL, "agx_ppo_graph: %d layers (2..%d)", nl, kGL);
@@ -804,7 +806,8 @@ int plan_graph(const agx_ppo_graph *net, int64_t batch, GArgs &a) {
         maxw = x.fout > maxw ? x.fout : maxw;
         nw += (long long)x.fin * x.fout + x.fout * (x.ln == 2 ? 3 : 1);
     }
-    AGX_REQUIRE(nw == net->n_params, "agx_ppo_graph: layers cover %lld of %d parameters", nw, net->n_params);
+    AGX_REQUIRE(extra >= 0 && nw + extra == net->n_params, "agx_ppo_graph: layers cover %lld of %d parameters", nw,
+                net->n_params - (extra > 0 ? extra : 0));
     const agx_ppo_layer &la = net->layers[net->actor_out], &lc = net->layers[net->critic_out];
     AGX_REQUIRE(la.fout == net->n_actions && lc.fout == 1 && la.ln == 0 && lc.ln == 0 && !la.relu && !lc.relu &&
                     !is_src[net->actor_out] && !is_src[net->critic_out],

@@ -144,6 +144,49 @@ def ppo_loss_fwd_bwd(logp, old_logp, adv, ret, old_value, value, entropy, batch,
     return out[0], out[1], out[2], stats
 
 
+def ppo_gauss_loss_fwd_bwd(mean, value, log_std, actions, old_logp, adv, ret, old_value, batch, clip_coef=0.2,
+                           vf_coef=0.5, ent_coef=0.01, index=None, out=None, stats=None):
+    """The Gaussian twin of ppo_loss_fwd_bwd (agx_ppo_gauss_loss_fwd_bwd): mean
+    [nmb * batch, A], value [nmb * batch], log_std [nmb, A] (one minibatch per
+    row of log_std); actions [rows, A] and old_logp / adv / ret / old_value
+    [rows] are the rollout, gathered through ``index`` when given.
+    Returns (g_mean, g_value, g_log_std, stats[nmb, 8])."""
+    _need(mean, "mean", _f32)
+    if mean.dim() != 2:
+        raise ValueError("mean: expected [samples, A]")
+    S, A = mean.shape
+    if S % batch:
+        raise ValueError(f"samples ({S}) must be a multiple of batch ({batch}); call per minibatch")
+    nmb = S // batch
+    _need(value, "value", _f32)
+    if value.numel() != S:
+        raise ValueError(f"value: expected {S} elements")
+    _need(log_std, "log_std", _f32, (nmb, A))
+    _need(actions, "actions", _f32)
+    if actions.dim() != 2 or actions.shape[1] != A:
+        raise ValueError(f"actions: expected [rows, {A}]")
+    src = actions.shape[0]
+    for t, n in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
+        _need(t, n, _f32)
+        if t.numel() != src:
+            raise ValueError(f"{n}: expected {src} elements")
+    if index is not None:
+        _need(index, "index", _i64)
+        if index.numel() != S:
+            raise ValueError("index: one entry per sample")
+    elif src != S:
+        raise ValueError("without an index the rollout arrays must match mean")
+    if out is None:
+        out = (torch.empty_like(mean), torch.empty_like(value), torch.empty_like(log_std))
+    if stats is None:
+        stats = torch.empty(nmb, 8, dtype=_f32, device=mean.device)
+    _lib.call("agx_ppo_gauss_loss_fwd_bwd", mean.data_ptr(), value.data_ptr(), log_std.data_ptr(),
+              actions.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(), old_value.data_ptr(),
+              _lib.ptr(index), int(batch), int(nmb), int(A), float(clip_coef), float(vf_coef), float(ent_coef),
+              out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), stats.data_ptr(), _lib.stream())
+    return out[0], out[1], out[2], stats
+
+
 # --------------------------------------------------------------------------- #
 # PER                                                                         #
 # --------------------------------------------------------------------------- #

@@ -149,7 +149,7 @@ def _row_dict(spec: ActorCriticSpec, flat: torch.Tensor, net: str) -> dict[str, 
     out = {"encoder": {}, "head": {}}
     for key, (off, shape) in spec.state_dict_keys().items():
         top, part = key.split(".")[:2]
-        if top != net:
+        if top != net or ".model." not in key:  # (a Gaussian head's log_std is no layer's: mutate carries it over)
             continue
         out["encoder" if part == "encoder" else "head"][key.split(".model.", 1)[1]] = \
             flat[off:off + int(np.prod(shape))].view(shape)
@@ -227,6 +227,10 @@ def mutate(spec: ActorCriticSpec, flat: torch.Tensor, method: str, rng: np.rando
         top, part = key.split(".")[:2]
         if top == "critic" and part == "encoder":
             continue  # one shared encoder region: the actor's (share_encoder_parameters)
+        if ".model." not in key:  # log_std of a Gaussian head: no architecture mutation touches it
+            n = int(np.prod(shape))
+            out[off:off + n] = flat[spec.log_std: spec.log_std + n]
+            continue
         which = "encoder" if part == "encoder" else "head"
         name = key.split(".model.", 1)[1]
         src = new_mods.get((top, which))

@@ -34,7 +34,7 @@ class AgxPPONet(ctypes.Structure):
 def net_descriptor(spec: ActorCriticSpec) -> AgxPPONet | None:
     """The fused-kernel descriptor, or None when the architecture is outside
     what agx_ppo_learn covers (then the torch learner runs)."""
-    if (len(spec.actor) != 2 or len(spec.critic) != 2 or not spec.layer_norm
+    if (spec.head != "categorical" or len(spec.actor) != 2 or len(spec.critic) != 2 or not spec.layer_norm
             or not 2 <= len(spec.encoder) <= 3 or not getattr(spec, "share_encoders", True)):
         return None
     d = AgxPPONet()
@@ -84,8 +84,19 @@ def graph_descriptor(spec) -> AgxPPOGraph | None:
     chain when share_encoders is off), or None when agx_ppo_learn_graph does
     not cover it (more than 16 layers, a LayerNorm / ReLU layer wider than 512,
     more than 32 actions): then the torch learner runs."""
-    if not isinstance(spec, ActorCriticSpec):
+    if not isinstance(spec, ActorCriticSpec) or spec.head != "categorical":
+        return None  # a Gaussian head never reaches the categorical kernels
+    d = layer_list(spec)
+    if d is None:
         return None
+    lib = _lib.load(require_gpu=False)  # pure host-side validation
+    if lib.agx_ppo_graph_check(ctypes.byref(d)) != 0:
+        return None
+    return d
+
+
+def layer_list(spec: ActorCriticSpec) -> AgxPPOGraph | None:
+    """agx_ppo_graph of an MLP actor-critic's layers (None: more than 16)."""
     layers: list[tuple] = []
 
     def chain(lays, src):
@@ -107,9 +118,6 @@ def graph_descriptor(spec) -> AgxPPOGraph | None:
         x = d.layers[i]
         x.fin, x.fout, x.w, x.b = lay.fin, lay.fout, lay.w, lay.b
         x.ln_w, x.ln_b, x.ln, x.relu, x.src = lay.g, lay.beta, _LN_KIND[lay.ln], int(lay.act), src
-    lib = _lib.load(require_gpu=False)  # pure host-side validation
-    if lib.agx_ppo_graph_check(ctypes.byref(d)) != 0:
-        return None
     return d
 
 
@@ -283,3 +291,31 @@ def policy_step_graph(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_strid
               _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy), out_agent_stride,
               _lib.ptr(actions_flat), pop.env_base_d.data_ptr(), ws[1].data_ptr(), _lib.stream())
 
+
+
+def gauss_act_workspace(pop, desc: AgxPPOGraph):
+    """(desc, scratch) of agx_ppo_act_gauss_graph for this population, as
+    graph_act_workspace."""
+    ws = getattr(pop, "_act_ws", None)
+    if ws is None or ws[0] is not desc:
+        lib = _lib.load()
+        nbytes = lib.agx_ppo_act_gauss_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
+        if nbytes == 0:
+            raise _lib.AgxError(f"agx_ppo_act_gauss_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+        ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
+    return ws
+
+
+def policy_step_gauss(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
+                      counter: int, actions=None, log_probs=None, values=None, entropy=None,
+                      out_agent_stride: int = 0, actions_flat=None, clip=None) -> None:
+    """agx_ppo_act_gauss_graph over all P agents x N envs: the policy step of a
+    Box-action population (one launch), the agents' own Philox streams;
+    ``clip``: (low, high) device tensors [A] for the actions_flat copy."""
+    ws = gauss_act_workspace(pop, desc)
+    lo, hi = clip if clip is not None else (None, None)
+    _lib.call("agx_ppo_act_gauss_graph", ctypes.byref(desc), pop.spec.log_std, pop.P, pop.N,
+              pop.params.data.data_ptr(), obs.data_ptr(), obs_agent_stride, 1 if sample else 0, pop.act_seed, counter,
+              _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy), out_agent_stride,
+              _lib.ptr(actions_flat), _lib.ptr(lo), _lib.ptr(hi), pop.env_base_d.data_ptr(), ws[1].data_ptr(),
+              _lib.stream())

@@ -72,6 +72,10 @@ class ActorCriticSpec:
     share_encoders: bool = True
     critic_encoder_name: str = "critic_encoder"
 
+    # the policy head over the actor's output: "categorical" (logits), or
+    # "gaussian" (GaussianActorCriticSpec: the mean, with log_std parameters)
+    head = "categorical"
+
     def shape_key(self) -> tuple:
         """Agents with equal keys share a network layout (population groups)."""
         return (self.obs_dim, self.n_actions, tuple(self.encoder_hidden), self.latent_dim, tuple(self.actor_hidden),
@@ -104,9 +108,15 @@ class ActorCriticSpec:
                 lay.beta = off
                 off += lay.fout
             if lay is self.actor[-1]:
+                off = self._after_actor_output(off)
                 self.actor_end = off
         self.n_params = off
         self.group_offsets = [0, self.actor_end, self.n_params]
+
+    def _after_actor_output(self, off: int) -> int:
+        """Parameters of the policy head that no layer owns, laid out at
+        ``off`` (the end of the actor's output layer) -> the actor group's end."""
+        return off
 
     def _head(self, name, hidden, nout, ln):
         dims = [self.latent_dim, *hidden]
@@ -196,6 +206,75 @@ class ActorCriticSpec:
         return out
 
 
+@dataclass
+class GaussianActorCriticSpec(ActorCriticSpec):
+    """The actor-critic of a Box action space (networks/actors.py:296-336 with
+    networks/distributions.py:152-183): the actor's output layer gives the mean
+    of a diagonal Gaussian, and the distribution wrapper's ``log_std`` [1, A]
+    (filled with ``action_std_init``) is a parameter of the actor.  The A
+    log_std floats sit directly after the actor's output layer, inside the
+    actor clip group [0, actor_end) (ppo.py:910-911).  ``n_actions`` is the
+    action dimension A.  The categorical kernels (agx_ppo_learn, agx_ppo_act,
+    the persistent rollout and evaluation) never see this spec: the Gaussian
+    policy step is agx_ppo_act_gauss_graph over ``gauss_descriptor()``."""
+
+    action_std_init: float = 0.0
+    log_std: int = -1  # offset of the A log_std floats in the row (set by __post_init__)
+    # the Box's bounds (A floats each, inf where unbounded): what the env's copy
+    # of an action is clipped to at inference (ppo.py:604-614); () = unbounded
+    action_low: tuple = ()
+    action_high: tuple = ()
+
+    head = "gaussian"
+
+    @property
+    def action_dim(self) -> int:
+        return self.n_actions
+
+    def shape_key(self) -> tuple:
+        return super().shape_key() + (self.head, float(self.action_std_init), tuple(self.action_low),
+                                      tuple(self.action_high))
+
+    def _after_actor_output(self, off: int) -> int:
+        self.log_std = off
+        return off + self.n_actions
+
+    def init_params(self, P: int, seeds: list[int] | None = None, device="cpu") -> torch.Tensor:
+        flat = super().init_params(P, seeds, "cpu")  # the layers draw exactly as a Discrete spec's
+        flat[:, self.log_std: self.log_std + self.n_actions] = float(self.action_std_init)
+        return flat.to(device)
+
+    def log_std_view(self, flat: torch.Tensor) -> torch.Tensor:
+        """[P, A] view of the agents' log_std."""
+        return flat[:, self.log_std: self.log_std + self.n_actions]
+
+    def state_dict_keys(self) -> dict[str, tuple[int, tuple[int, ...]]]:
+        # log_std is the distribution wrapper's own parameter, so it precedes
+        # head_net._wrapped.* in the reference's actor.parameters() / state dict
+        # (distributions.py:152-156); the flat row has it after the output layer
+        out = {}
+        for k, v in super().state_dict_keys().items():
+            if "actor.head_net.log_std" not in out and k.startswith("actor.head_net._wrapped."):
+                out["actor.head_net.log_std"] = (self.log_std, (1, self.n_actions))
+            out[k] = v
+        return out
+
+    def gauss_descriptor(self):
+        """agx_ppo_graph of the networks for agx_ppo_act_gauss_graph (n_params
+        counts the log_std floats, which no layer owns), or None when the
+        layer list is outside what the kernel takes."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+
+        d = layer_list(self)
+        lib = _lib.load(require_gpu=False)  # pure host-side validation
+        if d is None or lib.agx_ppo_act_gauss_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
+            return None
+        return d
+
+
 def categorical(logits: torch.Tensor):
     """log-softmax and entropy as ``agilerl/utils/torch_utils.py:142-199``:
     H = -sum p * log(p + 1e-8)."""
@@ -203,3 +282,17 @@ def categorical(logits: torch.Tensor):
     p = torch.softmax(logits, dim=-1)
     ent = -(p * torch.log(p + 1e-8)).sum(-1)
     return logp_all, ent
+
+
+_LOG_2PI = math.log(2 * math.pi)
+
+
+def gaussian(mean: torch.Tensor, log_std: torch.Tensor, action: torch.Tensor):
+    """log-prob of ``action`` and entropy of the diagonal Gaussian N(mean,
+    exp(log_std)^2) as ``agilerl/utils/torch_utils.py:225-257``; log_std
+    broadcasts against mean [..., A].  -> (logp [...], entropy [...])."""
+    log_std = log_std.expand_as(mean)
+    var = torch.exp(2 * log_std)
+    logp = (-0.5 * ((action - mean) ** 2 / var + 2 * log_std + _LOG_2PI)).sum(-1)
+    ent = 0.5 * (1 + _LOG_2PI) * mean.size(-1) + log_std.sum(-1)
+    return logp, ent

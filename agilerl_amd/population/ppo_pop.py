@@ -30,6 +30,11 @@ Two learner back ends share this state:
                     the HIP loss / clip+Adam kernels — the numerics reference
                     for the fused kernel and the path for architectures it does
                     not cover.
+
+A Gaussian spec (Box actions, nets.GaussianActorCriticSpec) stores float
+actions (P, T, N, A), acts through agx_ppo_act_gauss_graph and learns on the
+``fused=False`` path with the fused Gaussian loss kernel
+(agx_ppo_gauss_loss_fwd_bwd); the categorical kernels never see it.
 """
 
 from __future__ import annotations
@@ -66,6 +71,30 @@ class _PPOLossFn(torch.autograd.Function):
         return (g1.view(s) * gl, g2.view(s) * gl, g3.view(s) * gl) + (None,) * 9
 
 
+class _PPOGaussLossFn(torch.autograd.Function):
+    """_PPOLossFn for a Gaussian head (agx_ppo_gauss_loss_fwd_bwd): the
+    log-prob of the stored actions, the entropy and the loss in one launch;
+    ``log_std`` [P, A] is the slice of the parameter rows, so its gradient
+    lands in the rows' gradient through autograd's slice backward."""
+
+    @staticmethod
+    def forward(ctx, mean, value, log_std, actions, old_logp, adv, ret, old_v, gidx, b, clip, vf, ent):
+        A = mean.shape[-1]
+        g1, g2, g3, stats = K.ppo_gauss_loss_fwd_bwd(
+            mean.contiguous().view(-1, A), value.contiguous().view(-1), log_std.contiguous(), actions, old_logp,
+            adv, ret, old_v, b, clip, vf, ent, index=gidx)
+        ctx.save_for_backward(g1, g2, g3)
+        ctx.shapes = (mean.shape, value.shape, log_std.shape)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum(), stats
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        g1, g2, g3 = ctx.saved_tensors
+        sm, sv, sl = ctx.shapes
+        return (g1.view(sm) * gl, g2.view(sv) * gl, g3.view(sl) * gl) + (None,) * 10
+
+
 class PPOPopulation:
     def __init__(self, spec: ActorCriticSpec, pop_size: int, num_envs: int, *, learn_step=2048,
                  batch_size=128, lr=1e-3, gamma=0.99, gae_lambda=0.95, clip_coef=0.2, ent_coef=0.01,
@@ -73,6 +102,10 @@ class PPOPopulation:
                  device="cuda", fused=True, perm_source="numpy", action_masks=False, agent_offset=0,
                  global_pop_size=None, seed_base=None, agent_ids=None, init_params=True):
         self.spec = spec
+        # a Box action space: float actions [.., A], the Gaussian policy step and loss (agx_gauss.h)
+        self.gaussian = getattr(spec, "head", "categorical") == "gaussian"
+        if self.gaussian and action_masks:
+            raise ValueError("action masks apply to Discrete action spaces, not to a Gaussian policy")
         self.P, self.N = int(pop_size), int(num_envs)
         # a shard of a population spread over ranks: these P agents are global
         # agents agent_offset .. agent_offset + P of global_pop_size (their
@@ -142,6 +175,7 @@ class PPOPopulation:
         self._desc = None
         self._gdesc = None
         self._edesc = None
+        self._gauss = None
         self._alloc_rollout()
         self.env_base_d = torch.tensor([i * self.N for i in self.agent_ids], dtype=torch.int64, device=self.device)
         self.learn_steps = 0
@@ -156,7 +190,8 @@ class PPOPopulation:
         f32 = dict(dtype=torch.float32, device=dev)
         # image specs keep uint8 frames (normalised inside the first conv's load)
         self.obs = torch.zeros(P, T, N, D, dtype=getattr(self.spec, "obs_dtype", torch.float32), device=dev)
-        self.actions = torch.zeros(P, T, N, dtype=torch.int64, device=dev)
+        self.actions = (torch.zeros(P, T, N, self.spec.n_actions, dtype=torch.float32, device=dev) if self.gaussian
+                        else torch.zeros(P, T, N, dtype=torch.int64, device=dev))
         self.rewards = torch.zeros(P, T, N, **f32)
         self.dones = torch.zeros(P, T, N, dtype=torch.uint8, device=dev)
         self.values = torch.zeros(P, T, N, **f32)
@@ -176,7 +211,22 @@ class PPOPopulation:
         """obs [P, N, D] (device) -> action, log_prob, entropy, value, each [P, N].
         Gumbel-max sampling; with ``counter`` every agent draws from its own
         generator keyed by (population seed, global agent id, counter), so an
-        agent's draws do not depend on which other agents share its population."""
+        agent's draws do not depend on which other agents share its population.
+        A Gaussian population: one agx_ppo_act_gauss_graph launch, float
+        actions [P, N, A] (``counter`` None: the next rollout counter)."""
+        if self.gaussian:
+            from .learner import policy_step_gauss
+
+            if counter is None:
+                self.act_counter += 1
+                counter = self.act_counter
+            P, N = self.P, self.N
+            action = torch.empty(P, N, self.spec.n_actions, dtype=torch.float32, device=self.device)
+            logp, ent, value = (torch.empty(P, N, dtype=torch.float32, device=self.device) for _ in range(3))
+            policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), N * self.spec.obs_dim, sample=True,
+                              counter=int(counter), actions=action, log_probs=logp, values=value, entropy=ent,
+                              out_agent_stride=N)
+            return action, logp, ent, value
         logits, value = self.spec.forward(self.params.data, obs)
         logp_all, ent = categorical(logits)
         if counter is None:
@@ -195,8 +245,8 @@ class PPOPopulation:
     def fused_descriptor(self):
         """agx_ppo_net for this architecture, or None when the fused kernels do
         not cover it (then the plain-PyTorch forward / learner run)."""
-        if not self.fused or not isinstance(self.spec, ActorCriticSpec):
-            return None  # the fused kernels take the MLP actor-critic shapes only
+        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian:
+            return None  # the fused kernels take the categorical MLP actor-critic shapes only
         if self._desc is None:
             from .learner import net_descriptor
 
@@ -208,7 +258,7 @@ class PPOPopulation:
         shapes, else agx_ppo_graph (agx_ppo_learn_graph: any MLP actor-critic
         an architecture mutation produces); None: the plain-PyTorch learner."""
         desc = self.fused_descriptor()
-        if desc is not None or not self.fused or not isinstance(self.spec, ActorCriticSpec):
+        if desc is not None or not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian:
             return desc
         if self._gdesc is None:
             from .learner import graph_descriptor
@@ -221,7 +271,7 @@ class PPOPopulation:
         actor-critic, the compiled shapes included, so that a population's
         agents are evaluated together in one launch whatever kernels they train
         on (agx_ppo_eval_multi_persistent).  None: the PyTorch policy step."""
-        if not self.fused or not isinstance(self.spec, ActorCriticSpec):
+        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian:
             return None
         if self.fused_descriptor() is None:
             return self.learn_descriptor()  # already the runtime layer list
@@ -231,11 +281,33 @@ class PPOPopulation:
             self._edesc = graph_descriptor(self.spec) or False
         return self._edesc or None
 
+    def gauss_descriptor(self):
+        """agx_ppo_graph of a Gaussian population's networks for
+        agx_ppo_act_gauss_graph.  There is no other policy step for a Box
+        population: a layer list the kernel does not take is an error."""
+        if not self.gaussian:
+            return None
+        if self._gauss is None:
+            self._gauss = self.spec.gauss_descriptor()
+            if self._gauss is None:
+                raise _lib.AgxError("agx_ppo_act_gauss_graph does not take this network: " +
+                                    _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
+        return self._gauss
+
     @torch.no_grad()
     def act_into(self, t: int, actions_flat: torch.Tensor | None = None) -> None:
         """Rollout policy step for slot t: reads obs[:, t], writes actions /
         log_probs / values[:, t] in place (and a contiguous [P*N] copy of the
-        actions for the host env step)."""
+        actions for the host env step; [P*N*A] floats for a Gaussian population)."""
+        if self.gaussian:
+            from .learner import policy_step_gauss
+
+            self.act_counter += 1
+            TN = self.T * self.N
+            policy_step_gauss(self, self.gauss_descriptor(), self.obs[:, t], TN * self.spec.obs_dim, sample=True,
+                              counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
+                              values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat)
+            return
         desc = self.fused_descriptor()
         if desc is None and self.learn_descriptor() is not None:  # a mutated shape: the runtime-shape kernel
             from .learner import policy_step_graph
@@ -277,7 +349,9 @@ class PPOPopulation:
         """Bootstrap value + GAE (+ per-agent advantage statistics).  The fused
         runner computes last_value in its final rollout-step launch."""
         self.rollout_id += 1
-        if last_value is None:
+        if last_value is None and self.gaussian:
+            last_value = self.values_of(last_obs)
+        elif last_value is None:
             with torch.no_grad():
                 _, last_value = self.spec.forward(self.params.data, last_obs)
         if not last_value.is_contiguous():
@@ -294,6 +368,27 @@ class PPOPopulation:
                                 self.gae_lambda, True, self.advantages, self.returns, self.adv_stats, self.gae_ws)
         # keep a launcher only for the runner's persistent last_value / last_done
         self._gae_launch = (key, launch, last_value, last_done)
+
+    def action_clip(self):
+        """(low, high) device tensors [A] of a Gaussian population's Box
+        bounds for the env's copy of the actions at inference, or None."""
+        if not self.gaussian or not self.spec.action_low:
+            return None
+        if getattr(self, "_clip", None) is None:
+            self._clip = tuple(torch.tensor(b, dtype=torch.float32, device=self.device)
+                               for b in (self.spec.action_low, self.spec.action_high))
+        return self._clip
+
+    @torch.no_grad()
+    def values_of(self, obs: torch.Tensor) -> torch.Tensor:
+        """The critic's values [P, N] of obs [P, N, D] from a Gaussian
+        population's policy-step kernel (sample = 0, values only)."""
+        from .learner import policy_step_gauss
+
+        value = torch.empty(self.P, self.N, dtype=torch.float32, device=self.device)
+        policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim, sample=False,
+                          counter=0, values=value, out_agent_stride=self.N)
+        return value
 
     # ------------------------------------------------------------------ #
     def learn(self, prefetch: bool = True, skip_if_set: int | None = None) -> torch.Tensor:
@@ -508,13 +603,25 @@ class PPOPopulation:
         self.last_epochs_run = ran
         return out
 
+    def _categorical_loss(self, ob, ac, masks, idx, rows, image, rollout, gidx, b, ent_coef):
+        """Forward of one minibatch per agent and the categorical head's loss
+        (log-softmax and entropy in torch, agx_ppo_loss_fwd_bwd)."""
+        logits, value = (self.spec.forward(self.params, ob, rows=rows) if image
+                         else self.spec.forward(self.params, ob))
+        if masks is not None:
+            mk = torch.gather(masks, 1, idx.unsqueeze(-1).expand(-1, -1, masks.shape[-1]))
+            logits = torch.where(mk.bool(), logits, torch.full_like(logits, -1e8))
+        logp_all, ent = categorical(logits)
+        logp = logp_all.gather(-1, ac.unsqueeze(-1)).squeeze(-1)
+        return _PPOLossFn.apply(logp, value, ent, *rollout, gidx, b, self.clip_coef, self.vf_coef, ent_coef)
+
     def _learn_torch_group(self, perms, rows, batch_size, epochs, ent_coef) -> torch.Tensor:
         """E epochs x minibatches of ``batch_size`` for the agents in ``rows``
         (None: all agents); -> the reference's mean loss per agent [P]."""
         P, S, D = self.P, self.S, self.spec.obs_dim
         image = not isinstance(self.spec, ActorCriticSpec)
         obs = self.obs.view(P, S, D)
-        act = self.actions.view(P, S)
+        act = self.actions.view(P * S, -1) if self.gaussian else self.actions.view(P, S)
         masks = None if self.action_masks is None else self.action_masks.view(P, S, -1)
         old_logp = self.log_probs.view(-1)
         adv = self.advantages.view(-1)
@@ -536,17 +643,15 @@ class PPOPopulation:
             for s0, s1 in plan:
                 idx = perms[e][:, s0:s1]  # [P, b]
                 ob = torch.gather(obs, 1, idx.unsqueeze(-1).expand(-1, -1, D))
-                ac = torch.gather(act, 1, idx)
-                logits, value = (self.spec.forward(self.params, ob, rows=rows) if image
-                                 else self.spec.forward(self.params, ob))
-                if masks is not None:
-                    mk = torch.gather(masks, 1, idx.unsqueeze(-1).expand(-1, -1, masks.shape[-1]))
-                    logits = torch.where(mk.bool(), logits, torch.full_like(logits, -1e8))
-                logp_all, ent = categorical(logits)
-                logp = logp_all.gather(-1, ac.unsqueeze(-1)).squeeze(-1)
                 gidx = (idx + base).reshape(-1).contiguous()
-                loss, stats = _PPOLossFn.apply(logp, value, ent, old_logp, adv, ret, old_v, gidx,
-                                               s1 - s0, self.clip_coef, self.vf_coef, ent_coef)
+                if self.gaussian:  # the loss kernel gathers the float actions and computes their log-prob
+                    mean, value = self.spec.forward(self.params, ob)
+                    loss, stats = _PPOGaussLossFn.apply(mean, value, self.spec.log_std_view(self.params), act,
+                                                        old_logp, adv, ret, old_v, gidx, s1 - s0, self.clip_coef,
+                                                        self.vf_coef, ent_coef)
+                else:
+                    loss, stats = self._categorical_loss(ob, torch.gather(act, 1, idx), masks, idx, rows, image,
+                                                         (old_logp, adv, ret, old_v), gidx, s1 - s0, ent_coef)
                 self.params.grad.zero_()
                 loss.backward()
                 self.opt.step(active)
@@ -570,7 +675,15 @@ class PPOPopulation:
     # ------------------------------------------------------------------ #
     @torch.no_grad()
     def evaluate(self, obs: torch.Tensor) -> torch.Tensor:
-        """Greedy actions (mode of the categorical) for fitness evaluation."""
+        """Greedy actions (mode of the categorical; the mean of a Gaussian
+        policy, [P, N, A]) for fitness evaluation."""
+        if self.gaussian:
+            from .learner import policy_step_gauss
+
+            action = torch.empty(self.P, self.N, self.spec.n_actions, dtype=torch.float32, device=self.device)
+            policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim,
+                              sample=False, counter=0, actions=action, out_agent_stride=self.N)
+            return action
         logits, _ = self.spec.forward(self.params.data, obs)
         return torch.argmax(logits, dim=-1)
 

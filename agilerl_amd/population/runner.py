@@ -37,7 +37,10 @@ where its step may use the device freely.  A gymnasium env that does not touch
 the GPU can opt in by setting the attribute.
 
 Architectures outside the fused kernels use the plain-PyTorch policy step
-with per-field copies (``_collect_torch``).
+with per-field copies (``_collect_torch``).  A Gaussian (Box-action)
+population takes the same per-step path with its own HIP policy step
+(agx_ppo_act_gauss_graph, one launch per vector step): float32 action staging
+of P*N*A, the env is handed [P*N, A].
 """
 
 from __future__ import annotations
@@ -192,10 +195,10 @@ class PopulationRunner:
         else:
             self.stage_h, self.obs_h, self.rew_h, self.done_h = _packed(P, N, D, obs_dtype=pop.obs.dtype,
                                                                         pin_memory=True)
-            self.act_h = torch.zeros(P * N, dtype=torch.int64, pin_memory=True)
+            self.act_h = self._action_staging(pin_memory=True)
         self.stage_d, self.obs_d, self.rew_d, self.done_d = _packed(P, N, D, obs_dtype=pop.obs.dtype, device=dev)
         self.term_h = torch.zeros(P * N, dtype=torch.bool, pin_memory=True)
-        self.act_d = torch.zeros(P * N, dtype=torch.int64, device=dev)
+        self.act_d = self._action_staging(device=dev)
         self.last_obs = torch.zeros(P, N, D, dtype=pop.obs.dtype, device=dev)
         self.last_done = torch.zeros(P, N, dtype=torch.uint8, device=dev)
         self.last_value = torch.zeros(P, N, dtype=torch.float32, device=dev)
@@ -211,6 +214,14 @@ class PopulationRunner:
         self._np = None
         self._ctl_words = None
         self.stats_event = None
+
+    def _action_staging(self, **kw) -> torch.Tensor:
+        """The env's actions of one vector step: int64 [P*N], or float32
+        [P*N*A] for a Gaussian (Box-action) population."""
+        pop = self.pop
+        if pop.gaussian:
+            return torch.zeros(pop.P * pop.N * pop.spec.n_actions, dtype=torch.float32, **kw)
+        return torch.zeros(pop.P * pop.N, dtype=torch.int64, **kw)
 
     def _ctl_bytes(self) -> int:
         lib, P, N = _lib.load(), self.pop.P, self.pop.N
@@ -270,7 +281,10 @@ class PopulationRunner:
     def _env_step(self) -> None:
         # numpy views of the staging made once (Tensor.numpy() costs ~1-3 us a call)
         if self._np is None:
-            self._np = (self.act_h.numpy(), self.obs_h.numpy(), self.rew_h.numpy(), self.done_h.numpy(),
+            act = self.act_h.numpy()
+            if self.pop.gaussian:  # a Box env takes [P*N, A]
+                act = act.reshape(self.pop.P * self.pop.N, -1)
+            self._np = (act, self.obs_h.numpy(), self.rew_h.numpy(), self.done_h.numpy(),
                         self.term_h.numpy())
         act, obs, rew, done, term_np = self._np
         _, _, term, trunc, _ = self.env.step(act, out_obs=obs, out_rew=rew, out_done=done)
@@ -418,7 +432,13 @@ class PopulationRunner:
             self.episodes_env += d.long()
             self.scores.masked_fill_(d, 0.0)
         gdesc = pop.learn_descriptor()
-        if gdesc is not None:  # a mutated shape: the bootstrap value from the runtime-shape kernel too
+        if pop.gaussian:  # the bootstrap value from the Gaussian policy-step kernel (sample = 0, values only)
+            from .learner import policy_step_gauss
+
+            policy_step_gauss(pop, pop.gauss_descriptor(), self.last_obs, N * pop.spec.obs_dim, sample=False,
+                              counter=0, values=self.last_value, out_agent_stride=N)
+            self.last_value_valid = True
+        elif gdesc is not None:  # a mutated shape: the bootstrap value from the runtime-shape kernel too
             from .learner import policy_step_graph
 
             policy_step_graph(pop, gdesc, self.last_obs, N * pop.spec.obs_dim, sample=False, counter=0,
@@ -712,8 +732,8 @@ class _EvalDriver:
             else:
                 self.n_wg = runner.n_wg
         else:
-            self.act_d = torch.empty(P * N, dtype=torch.int64, device=pop.device)
-            self.act_h = torch.empty(P * N, dtype=torch.int64, pin_memory=True)
+            self.act_d = runner._action_staging(device=pop.device)
+            self.act_h = runner._action_staging(pin_memory=True)
             self.obs_h = torch.empty(P * N * D, dtype=pop.obs.dtype, pin_memory=True)
             self.obs_d = torch.empty(P, N, D, dtype=pop.obs.dtype, device=pop.device)
             self.ev = torch.cuda.Event()
@@ -725,6 +745,10 @@ class _EvalDriver:
             from .learner import graph_act_workspace
 
             graph_act_workspace(self.pop, self.gdesc)
+        elif pop.gaussian:
+            from .learner import gauss_act_workspace
+
+            gauss_act_workspace(pop, pop.gauss_descriptor())
         self.obs = None
         self.stream = None  # a dedicated non-blocking stream, assigned by run_lockstep
         self._pipelined = False
@@ -799,7 +823,12 @@ class _EvalDriver:
         self.obs_h.numpy()[:] = np.asarray(self.obs).reshape(-1)
         self.obs_d.view(-1).copy_(self.obs_h, non_blocking=True)
         counter = self.counter0 + self.step
-        if self.edescs is not None:  # the evaluation layer list (as the multi launch samples)
+        if pop.gaussian:  # a Box population: the env's copy clipped to the bounds (ppo.py:604-614)
+            from .learner import policy_step_gauss
+
+            policy_step_gauss(pop, pop.gauss_descriptor(), self.obs_d, N * D, sample=True, counter=counter,
+                              out_agent_stride=N, actions_flat=self.act_d, clip=pop.action_clip())
+        elif self.edescs is not None:  # the evaluation layer list (as the multi launch samples)
             from .learner import policy_step_graph
 
             policy_step_graph(pop, self.edescs[0], self.obs_d, N * D, sample=True, counter=counter,
@@ -848,7 +877,9 @@ class _EvalDriver:
                 raise
             reward = rew_n
         else:
-            self.obs, reward, term, trunc, _ = self.env.step(self.act_h.numpy().copy())
+            act = self.act_h.numpy().copy()
+            self.obs, reward, term, trunc, _ = self.env.step(act.reshape(self.P * self.N, -1) if self.pop.gaussian
+                                                             else act)
         self.step += 1
         self.scores += np.asarray(reward).reshape(-1)
         done = np.asarray(term, dtype=bool).reshape(-1)

@@ -57,8 +57,12 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
                   update_epochs=INIT_HP.get("UPDATE_EPOCHS", 4))
         if INIT_HP.get("RECURRENT", False):
             raise NotImplementedError("recurrent PPO is outside the agx hot path")
+        # a Box action space: the Gaussian policy's initial log_std (ppo.py:121, 168)
+        algo_kwargs.setdefault("action_std_init", float(INIT_HP.get("ACTION_STD_INIT", 0.0)))
+        assert algo_kwargs["action_std_init"] >= 0, "Action standard deviation must be greater than or equal to zero."
         spec = spec_from_net_config(observation_space, action_space, net_config,
-                                    share_encoders=bool(algo_kwargs.get("share_encoders", True)))
+                                    share_encoders=bool(algo_kwargs.get("share_encoders", True)),
+                                    action_std_init=algo_kwargs["action_std_init"])
         G = population_size if shard and world > 1 else P
         pop = PPOPopulation(spec, P, num_envs, seeds=list(range(lo, lo + P)), device=torch.device(device),
                             agent_offset=lo, global_pop_size=G, seed_base=0, **hp)
