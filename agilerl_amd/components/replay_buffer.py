@@ -109,6 +109,7 @@ class ReplayBuffer:
         agx_replay_gather launch on the GPU (one index op per field on the CPU)."""
         st = self._storage
         if (self.device.type != "cuda" or not st or len(st) > 8
+                or indices.numel() >= 65536  # agx_replay_gather: one grid row per sample
                 or any(not v.is_contiguous() or v.shape[0] != self.max_size for v in st.values())):
             return self._gather(indices)
         import ctypes

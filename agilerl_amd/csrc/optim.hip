@@ -351,8 +351,9 @@ extern "C" int agx_clip_adam(float *params, float *grads, float *exp_avg, float 
 }
 
 extern "C" int agx_polyak(float *target, const float *online, int64_t n, float tau, void *stream) {
-    AGX_REQUIRE(target && online && n >= 0, "agx_polyak: bad arguments");
-    if (n == 0) return AGX_OK;
+    AGX_REQUIRE(n >= 0, "agx_polyak: bad arguments");
+    if (n == 0) return AGX_OK;  // an empty tensor's data pointer is null
+    AGX_REQUIRE(target && online, "agx_polyak: null pointer");
     const int64_t blocks = ceil_div(n, 256);
     polyak_kernel<<<(unsigned)(blocks > 4096 ? 4096 : blocks), 256, 0, as_stream(stream)>>>(target, online, n, tau);
     return check_launch("agx_polyak");

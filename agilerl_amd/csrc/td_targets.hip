@@ -3,6 +3,8 @@
 //
 // DQN — agilerl/algorithms/dqn.py:296-314 (DQN.update):
 //   q_t = max_a Qtgt(s')  |  Qtgt(s')[argmax_a Q(s')] (double)
+//         (torch.max / torch.argmax: a NaN is the maximum, the first NaN's
+//         index the argmax, ties take the first index)
 //   y   = r + (gamma*q_t)*(1-d)        (f32, one rounding per op)
 //   loss = MSE(Q(s)[a], y);  dloss/dQ(s)[a] = 2 (Q[a]-y) / B
 // Critics — td3.py:503-515, ddpg.py:457-461 (one critic), maddpg.py:764-781:
@@ -72,7 +74,20 @@ __global__ __launch_bounds__(1024) void loss_finalize(const double *__restrict__
     }
 }
 
-// one row per lane
+// torch.min / torch.max (and clamp) propagate NaN; fminf / fmaxf do not
+__device__ __forceinline__ float nan_min(float a, float b) {
+    if (a != a) return a;
+    if (b != b) return b;
+    return fminf(a, b);
+}
+__device__ __forceinline__ float nan_max(float a, float b) {
+    if (a != a) return a;
+    if (b != b) return b;
+    return fmaxf(a, b);
+}
+
+// one row per lane.  A NaN among the next-state values is the row's maximum,
+// as for torch.max / torch.argmax (argmax: the first NaN's index)
 __global__ __launch_bounds__(kTdBlock) void td_target_kernel(
     const float *__restrict__ qno, const float *__restrict__ qnt, const float *__restrict__ qc,
     const int64_t *__restrict__ act, const float *__restrict__ r, const float *__restrict__ d, int64_t B, int A,
@@ -86,15 +101,17 @@ __global__ __launch_bounds__(kTdBlock) void td_target_kernel(
             const float *on = qno + i * A;
             int best = 0;
             float bv = on[0];
-            for (int a = 1; a < A; ++a)
-                if (on[a] > bv) {
-                    bv = on[a];
+            for (int a = 1; a < A; ++a) {
+                const float v = on[a];
+                if (v > bv || (v != v && bv == bv)) {
+                    bv = v;
                     best = a;
                 }
+            }
             qt = tn[best];
         } else {
             qt = tn[0];
-            for (int a = 1; a < A; ++a) qt = fmaxf(qt, tn[a]);
+            for (int a = 1; a < A; ++a) qt = nan_max(qt, tn[a]);
         }
         const float yi = r[i] + (g * qt) * (1.0f - d[i]);
         y[i] = yi;
@@ -111,18 +128,6 @@ __global__ __launch_bounds__(kTdBlock) void td_target_kernel(
         }
     }
     if (partials) block_partials<false>(sq, 0.0, partials, nullptr);
-}
-
-// torch.min / torch.max (and clamp) propagate NaN; fminf / fmaxf do not
-__device__ __forceinline__ float nan_min(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return fminf(a, b);
-}
-__device__ __forceinline__ float nan_max(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return fmaxf(a, b);
 }
 
 // one row per lane.  TWIN: two critics against the smaller target value;

@@ -59,12 +59,13 @@ def _obs(P, N, seed=1):
 # ---- 1. the policy step, greedy --------------------------------------------------- #
 @pytest.mark.parametrize("few", ["few", "general"])
 @pytest.mark.parametrize("shape", list(SHAPES))
-@pytest.mark.parametrize("A", [1, 3, 6, 17])
+@pytest.mark.parametrize("A", [1, 3, 6, 16, 17, 32])
 def test_gauss_policy_step_greedy_matches_torch_forward(A, shape, few, monkeypatch):
     """sample = 0: the action is the mean; mean and value against spec.forward
     at the bar of test_graph_policy_step_matches_torch_forward, the log-prob of
     the mean and the entropy against the float64 formulas.  21 envs: two row
-    blocks, the second partial; A = 17: the second dimension per lane.  Both
+    blocks, the second partial; A = 16 / 17: either side of the 16-lane split
+    (17: the second dimension per lane), A = 32: the maximum.  Both
     forward forms (AGX_GRAPH_FEW=0: the general one)."""
     if few == "general":
         monkeypatch.setenv("AGX_GRAPH_FEW", "0")
@@ -92,7 +93,18 @@ def test_gauss_policy_step_samples_the_philox_stream(log_std, P, N):
     plus the rounding of the stored a (|a| 2^-23 / sigma).  The log-prob against
     the float64 formula on the stored (a, mu, log_std): each dimension's term
     is <= ~18 with a few ulp of error, so rtol 1e-5, atol 1e-5 A."""
-    A = 6
+    _sampled_step_follows_philox(6, log_std, P, N)
+
+
+@pytest.mark.parametrize("log_std", [0.0, -1.0])
+@pytest.mark.parametrize("A", [16, 32])
+def test_gauss_policy_step_samples_the_philox_stream_wide(A, log_std):
+    """The same at A = 16 (the last dimension of a lane's first slot) and at
+    A = 32 (every lane's second slot in use: the most the kernel takes)."""
+    _sampled_step_follows_philox(A, log_std, 3, 21)
+
+
+def _sampled_step_follows_philox(A, log_std, P, N):
     pop = _pop(A, "default", P, N, log_std=np.full((P, A), log_std, np.float32))
     obs = _obs(P, N)
     mu = _step(pop, obs, sample=False)["actions"].numpy().astype(np.float64)
@@ -177,8 +189,8 @@ def _float32_formula_error(rec, b, clip, vf, ent, ref):
 
 
 @pytest.mark.parametrize("gather", [False, True], ids=["direct", "gather"])
-@pytest.mark.parametrize("b,nmb", [(1, 1), (5, 3), (128, 8)])
-@pytest.mark.parametrize("A", [1, 3, 6, 17])
+@pytest.mark.parametrize("b,nmb", [(1, 1), (5, 3), (6, 5), (128, 8)])
+@pytest.mark.parametrize("A", [1, 3, 6, 16, 17, 32])
 def test_gauss_loss_matches_float64_restatement(A, b, nmb, gather):
     """agx_ppo_gauss_loss_fwd_bwd against tests/gauss_twin.py loss_and_grads
     (float64), rows on the tie rules included: adv = 0 and every unclipped row
@@ -188,7 +200,9 @@ def test_gauss_loss_matches_float64_restatement(A, b, nmb, gather):
     on 1 +- clip other than through adv = 0 cannot be written down for both
     precisions at once (exp of a float32 log-prob difference), so the closed
     interval of the ratio clamp is covered by the value clamp's edge rows, which
-    go through the same rule in loss_sample.
+    go through the same rule in loss_sample.  (b, nmb) = (6, 5): a batch that
+    is no multiple of the four rows per pass, and one full block of four
+    minibatches followed by a partial one.
 
     Bars: the categorical kernel's (tests/test_kernels_gpu.py): rtol 1e-5 /
     atol 1e-8 on the gradients, rtol 1e-5 / atol 1e-6 on the stats; for g_mean

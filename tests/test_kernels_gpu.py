@@ -443,7 +443,7 @@ def test_c51_paths_vs_c_oracle(vmin, vmax, gamma, Z):
 # optimiser                                                                   #
 # --------------------------------------------------------------------------- #
 @pytest.mark.parametrize("P,n,split", [(3, 5000, 3100), (3, 5001, 3101), (2, 40_000, 24_002)],
-                         ids=["float4", "scalar", "pre-reduced-norm"])
+                         ids=["float4", "scalar", "five-sum-chunks"])  # nsum = 5: every block re-reduces the partials
 def test_clip_adam_matches_torch(P, n, split):
     torch.manual_seed(0)
     p0 = torch.randn(P, n)
