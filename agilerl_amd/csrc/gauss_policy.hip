@@ -5,15 +5,13 @@
 // loss of ppo_loss_sample.h and the gradients of mean / value / log_std in one
 // pass).
 #include "../../include/agx_gauss.h"
+#include "gauss_head.h"
 #include "graph_net.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
 namespace agx {
 namespace {
-
-constexpr float kLog2Pi = 1.8378770664093453f;         // log(2 pi)
-constexpr double kGaussEntropy = 1.4189385332046727;   // 0.5 (1 + log(2 pi)) per dimension
 
 // eps of dimension d (agx_gauss.h): words (x, y) (d even) or (z, w) (d odd) of
 // the Philox block of (env, counter ^ (d >> 1) << 56) -> u1, u2 -> Box-Muller.
@@ -27,12 +25,6 @@ __device__ __forceinline__ float gauss_noise(int d, unsigned long long env, unsi
     const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float u2 = ((float)(w2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
     return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
-}
-
-// one dimension's log-prob term of action a under N(mu, exp(log_std)^2)
-__device__ __forceinline__ float gauss_logp_term(float a, float mu, float ls) {
-    const float z = a - mu;
-    return -0.5f * (z * z / expf(2.f * ls) + 2.f * ls + kLog2Pi);
 }
 
 // what the Gaussian step writes besides the ActArgs' log_probs / values / entropy
@@ -54,7 +46,7 @@ __device__ __forceinline__ void gauss_step(const ActArgs &g, const GaussHead &h,
     const int d0 = sub, d1 = sub + 16;
     const bool on0 = d0 < A, on1 = d1 < A;
     const float ls0 = on0 ? log_std[d0] : 0.f, ls1 = on1 ? log_std[d1] : 0.f;
-    const float H = (float)(kGaussEntropy * (double)A) + row_sum(ls0 + ls1);
+    const float H = gauss_entropy(A, row_sum(ls0 + ls1));
     for (int r0 = 0; r0 < nrow; r0 += 4 * kGW) {
         const int r = r0 + 4 * wave + rq;
         const bool live = r < nrow;
@@ -145,8 +137,8 @@ __global__ __launch_bounds__(256) void ppo_gauss_loss_kernel(
     const int d0 = sub, d1 = sub + 16;
     const bool on0 = d0 < A, on1 = d1 < A;
     const float ls0 = on0 ? log_std[m * A + d0] : 0.f, ls1 = on1 ? log_std[m * A + d1] : 0.f;
-    const float iv0 = 1.f / expf(2.f * ls0), iv1 = 1.f / expf(2.f * ls1);
-    const float H = (float)(kGaussEntropy * (double)A) + row_sum(ls0 + ls1);
+    const float iv0 = gauss_inv_var(ls0), iv1 = gauss_inv_var(ls1);
+    const float H = gauss_entropy(A, row_sum(ls0 + ls1));
     Acc acc;
     float gs0 = 0.f, gs1 = 0.f;
     const int64_t base = m * b;
@@ -172,12 +164,12 @@ __global__ __launch_bounds__(256) void ppo_gauss_loss_kernel(
         }
         const float z0 = a0 - mu0, z1 = a1 - mu1;
         if (on0) {
-            g_mean[o * A + d0] = gl * (z0 * iv0);
-            gs0 += gl * (z0 * z0 * iv0 - 1.f);
+            g_mean[o * A + d0] = gauss_g_mean(gl, z0, iv0);
+            gs0 += gauss_g_log_std(gl, z0, iv0);
         }
         if (on1) {
-            g_mean[o * A + d1] = gl * (z1 * iv1);
-            gs1 += gl * (z1 * z1 * iv1 - 1.f);
+            g_mean[o * A + d1] = gauss_g_mean(gl, z1, iv1);
+            gs1 += gauss_g_log_std(gl, z1, iv1);
         }
     }
     gs0 += __shfl_xor(gs0, 16, 64);

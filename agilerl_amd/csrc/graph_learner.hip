@@ -29,7 +29,17 @@
 // The layer table, its plans, the GEMM and the forward are graph_net.h's
 // (shared with the policy step, graph_rollout.hip); this unit is the backward,
 // the learn kernels and their host side.
+//
+// GAUSS (a compile-time parameter of the three kernels): the diagonal-Gaussian
+// head of a Box action space (include/agx_gauss.h).  The actor's output is the
+// mean, the stored actions are float [A] per row, and the A log_std floats at
+// GArgs::lso are parameters no layer owns: the loss row pass computes their
+// gradient (a column sum over the rows, as the output-layer bias gradients),
+// the clip counts them in the actor group and Adam steps them with the row.
+#include "../../include/agx_gauss.h"
+#include "gauss_head.h"
 #include "graph_net.h"
+#include "ppo_loss_sample.h"
 
 namespace agx {
 namespace {
@@ -205,6 +215,130 @@ __device__ __forceinline__ void bwd_rows(const GLay &L, float *base, const float
     }
 }
 
+// words per wave of the output layers' column partials (colo): 32 logits /
+// means and the value; the Gaussian head adds its 32 log_std (and a pad word)
+template <bool GAUSS>
+constexpr int kColo = GAUSS ? 66 : 33;
+
+// loss_sample's coefficients for a minibatch of 1 / inv_b rows
+__device__ __forceinline__ LossCoef loss_coef(const GArgs &g, float inv_b, float entp) {
+    LossCoef k;
+    k.clip = g.clip;
+    k.lo = 1.f - g.clip;
+    k.hi = 1.f + g.clip;
+    k.inv_b = inv_b;
+    k.vf = g.vf;
+    k.ent = entp;
+    k.vf_half_inv_b = g.vf * 0.5f * inv_b;
+    k.g_h = -entp * inv_b;
+    return k;
+}
+
+// The Gaussian head's loss row pass over `bsz` rows of the general form (the
+// geometry of the categorical pass in minibatch_grads: 16 lanes per row,
+// dimensions sub and sub + 16 per lane, four rows per lane group in flight):
+// mean / value / log_std -> d(mean) in both layouts, d(value), and per wave
+// the column partials of the output-layer biases and of log_std in colo
+// ([kGW][66]: 32 means, the value, 32 log_std).  The row math is gauss_head.h's
+// and loss_sample's, as in agx_ppo_gauss_loss_fwd_bwd.
+__device__ __forceinline__ void gauss_loss_rows(const GArgs &g, float *base, const float *pr, const float *act_e,
+                                                const float *grow_e, long long s0, int bsz, float inv_b, float entp,
+                                                float *colo, float &lsum, float &klsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, rq = lane >> 4;
+    const int bp = g.bp, A = g.A;
+    const long long S = g.S;
+    const GLay &La = g.L[g.aout];
+    const GLay &Lc = g.L[g.cout];
+    const float *mup = base + La.yr;
+    const float *vp = base + Lc.yr;
+    float *dla = base + La.dy;
+    float *dlac = base + La.dyc;
+    float *dlv = base + Lc.dy;
+    const int a0 = sub, a1 = sub + 16;
+    const bool on0 = a0 < A, on1 = a1 < A;
+    const float l0 = pr[g.lso + (on0 ? a0 : 0)], l1 = pr[g.lso + (on1 ? a1 : 0)];
+    const float ls0 = on0 ? l0 : 0.f, ls1 = on1 ? l1 : 0.f;
+    const float iv0 = gauss_inv_var(ls0), iv1 = gauss_inv_var(ls1);
+    const float H = gauss_entropy(A, row_sum(ls0 + ls1));
+    const LossCoef k = loss_coef(g, inv_b, entp);
+    float cb0 = 0.f, cb1 = 0.f, cbv = 0.f;  // output-layer bias gradients (column partials)
+    float gs0 = 0.f, gs1 = 0.f;             // log_std gradients (column partials)
+    constexpr int R = 4;
+    for (int rb = 0; rb < bsz; rb += R * 4 * kGW) {
+        float pmu0[R], pmu1[R], pa0[R], pa1[R], polp[R], pad[R], pret[R], pov[R], pv[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row0 = rb + 4 * wave + rq + 4 * kGW * u;
+            const int row = row0 < bsz ? row0 : 0;
+            pmu0[u] = mup[(size_t)row * A + (on0 ? a0 : 0)];
+            pmu1[u] = mup[(size_t)row * A + (on1 ? a1 : 0)];
+            pa0[u] = act_e[(size_t)(s0 + row) * A + (on0 ? a0 : 0)];
+            pa1[u] = act_e[(size_t)(s0 + row) * A + (on1 ? a1 : 0)];
+            polp[u] = grow_e[s0 + row];
+            pad[u] = grow_e[S + s0 + row];
+            pret[u] = grow_e[2 * S + s0 + row];
+            pov[u] = grow_e[3 * S + s0 + row];
+            pv[u] = vp[row];
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row0 = rb + 4 * wave + rq + 4 * kGW * u;
+            const bool live = row0 < bsz;
+            const int row = live ? row0 : 0;
+            const float mu0 = on0 ? pmu0[u] : 0.f, mu1 = on1 ? pmu1[u] : 0.f;
+            const float av0 = on0 ? pa0[u] : 0.f, av1 = on1 ? pa1[u] : 0.f;
+            const float lp = row_sum((on0 ? gauss_logp_term(av0, mu0, ls0) : 0.f) +
+                                     (on1 ? gauss_logp_term(av1, mu1, ls1) : 0.f));
+            float gl, gv;
+            Acc one;
+            loss_sample(lp, polp[u], pad[u], pret[u], pov[u], pv[u], H, k, gl, gv, one);
+            if (live) {
+                const float z0 = av0 - mu0, z1 = av1 - mu1;
+                if (on0) {
+                    const float d0 = gauss_g_mean(gl, z0, iv0);
+                    dla[(size_t)row * A + a0] = d0;
+                    dlac[(size_t)a0 * bp + row] = d0;
+                    cb0 += d0;
+                    gs0 += gauss_g_log_std(gl, z0, iv0);
+                }
+                if (on1) {
+                    const float d1 = gauss_g_mean(gl, z1, iv1);
+                    dla[(size_t)row * A + a1] = d1;
+                    dlac[(size_t)a1 * bp + row] = d1;
+                    cb1 += d1;
+                    gs1 += gauss_g_log_std(gl, z1, iv1);
+                }
+                if (sub == 0) {
+                    dlv[row] = gv;
+                    cbv += gv;
+                    lsum += (one.pg + g.vf * 0.5f * one.vl - entp * H) * inv_b;
+                    klsum += one.kl * inv_b;  // approx_kl (ppo.py:899-902)
+                }
+            }
+        }
+    }
+    // the wave's four row groups, then per wave into LDS (the caller sums the waves in order)
+    cb0 += __shfl_xor(cb0, 16, 64);
+    cb0 += __shfl_xor(cb0, 32, 64);
+    cb1 += __shfl_xor(cb1, 16, 64);
+    cb1 += __shfl_xor(cb1, 32, 64);
+    cbv += __shfl_xor(cbv, 16, 64);
+    cbv += __shfl_xor(cbv, 32, 64);
+    gs0 += __shfl_xor(gs0, 16, 64);
+    gs0 += __shfl_xor(gs0, 32, 64);
+    gs1 += __shfl_xor(gs1, 16, 64);
+    gs1 += __shfl_xor(gs1, 32, 64);
+    if (rq == 0) {
+        float *co = colo + wave * kColo<true>;
+        co[a0] = cb0;
+        co[a1] = cb1;
+        if (sub == 0) co[32] = cbv;
+        co[33 + a0] = gs0;
+        co[33 + a1] = gs1;
+    }
+}
+
 // One minibatch's forward, PPO loss and backward over `bsz` rows (rows
 // s0 .. s0 + bsz - 1 of the epoch's minibatch-ordered rollout, observations at
 // xobs), accumulating the gradient row G (every entry written: dW by GEMM
@@ -213,6 +347,8 @@ __device__ __forceinline__ void bwd_rows(const GLay &L, float *base, const float
 // it).  base: this workgroup's activation scratch; wb: where the transposed
 // weights live (wb + L.wt).  Shared by the one-workgroup-per-agent learner and
 // the partnered one (each partner over its slice of the rows).
+// GAUSS: gact_e holds the rows' float actions [A]; colo has kColo<GAUSS> words per wave.
+template <bool GAUSS>
 __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, const float *wb, const float *pr, float *G,
                                                 const float *xobs, const int *gact_e, const unsigned *gmask_e,
                                                 const float *grow_e, long long s0, int bsz, float inv_b, float entp,
@@ -234,7 +370,11 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
     forward_layers(g.L, g.nl, xobs, bsz, base, pr, bp, lds, g.dbg, st);
 
     // ---- loss row pass: logits / value -> d(logits), d(value) (ppo.py:876-908)
-    if (!(g.dbg & 8)) {
+    if constexpr (GAUSS) {
+        if (!(g.dbg & 8))
+            gauss_loss_rows(g, base, pr, reinterpret_cast<const float *>(gact_e), grow_e, s0, bsz, inv_b, entp, colo,
+                            lsum, klsum);
+    } else if (!(g.dbg & 8)) {
         const GLay &La = g.L[g.aout];
         const GLay &Lc = g.L[g.cout];
         const float *lgp = base + La.yr;
@@ -346,8 +486,17 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
     __syncthreads();
     if (!(g.dbg & 8) && tid <= A) {
         float sb = 0.f;
-        for (int w = 0; w < kGW; ++w) sb += colo[w * 33 + (tid < A ? tid : 32)];
+        for (int w = 0; w < kGW; ++w) sb += colo[w * kColo<GAUSS> + (tid < A ? tid : 32)];
         G[tid < A ? g.L[g.aout].b + tid : g.L[g.cout].b] = sb;
+    }
+    if constexpr (GAUSS) {
+        // d(log_std): the waves' partials in order, and the entropy's -ent_coef / b per row of the slice
+        const int d = tid - kWave;
+        if (!(g.dbg & 8) && d >= 0 && d < A) {
+            float sg = 0.f;
+            for (int w = 0; w < kGW; ++w) sg += colo[w * kColo<GAUSS> + 33 + d];
+            G[g.lso + d] = sg + (-entp * inv_b) * (float)bsz;
+        }
     }
     if (st) st[17] = (long long)__builtin_readcyclecounter();
 
@@ -449,11 +598,12 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
 
 }
 
+template <bool GAUSS>
 __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
     __shared__ float red[2 * kGW];
     __shared__ __attribute__((aligned(16))) float lds[kGemmLds];
     __shared__ float colp[2 * 3 * kGW * 128];  // per-wave bias / LN-affine column partials (F <= 128), by layer parity
-    __shared__ float colo[kGW * 33];       // per-wave output-layer bias partials (32 logits + the value)
+    __shared__ float colo[kGW * kColo<GAUSS>];  // per-wave output-layer partials (32 logits + the value; + log_std)
     if (g.skip && __hip_atomic_load(g.skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;
     const int p = blockIdx.x;
     const int tid = threadIdx.x;
@@ -492,7 +642,7 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
     for (int e = 0; e < Ep; ++e) {
         const size_t ge = (size_t)e * g.P + p;
         const float *gobs_e = g.gobs + ge * S * D;
-        const int *gact_e = g.gact + ge * S;
+        const int *gact_e = g.gact + ge * S * (GAUSS ? g.A : 1);
         const unsigned *gmask_e = g.gmask ? g.gmask + ge * S : nullptr;
         const float *grow_e = g.grow + ge * 4 * S;
         for (int mb = 0; mb < nmb; ++mb) {
@@ -502,8 +652,8 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
             const float *xobs = gobs_e + s0 * D;
 
             float lsum = 0.f, klsum = 0.f;
-            minibatch_grads(g, base, base, pr, G, xobs, gact_e, gmask_e, grow_e, s0, bsz, inv_b, entp, lds, colp,
-                            colo, lsum, klsum);
+            minibatch_grads<GAUSS>(g, base, base, pr, G, xobs, gact_e, gmask_e, grow_e, s0, bsz, inv_b, entp, lds,
+                                   colp, colo, lsum, klsum);
             // ---- loss / kl, clip, Adam ------------------------------------------
             block_sum2(lsum, klsum, red);
             if (tid == 0) loss_total += lsum;
@@ -567,6 +717,9 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
                 const int f0 = kind == 0 ? L.w : kind == 1 ? L.b : kind == 2 ? L.g : L.be;
                 adam_region(f0, kind == 0 ? L.fout * L.fin : L.fout, kind == 0 ? L.wt : -1, kind == 0 ? L.fin : 1,
                             kind == 0 ? L.fout : 1);
+            }
+            if constexpr (GAUSS) {  // log_std: owned by no layer, no transposed copy
+                if (!(g.dbg & 32)) adam_region((int)g.lso, g.A, -1, 1, 1);
             }
             __syncthreads();
         }  // minibatches
@@ -749,10 +902,69 @@ __device__ __forceinline__ void few_row_back(float *dy, const float *xh, float *
     }
 }
 
+// The Gaussian head's loss row pass of the few-row form: the lane group's row
+// (4 wave + rq) of the partner's rk <= 16 rows, gauss_loss_rows' math per
+// element.  d(mean) / d(value) go to the output layers' dY tiles (zero past the
+// slice); the row's d(log_std) terms overwrite its means in the actor output's
+// Y tile, which nothing reads after this pass (the caller sums them over the
+// 16 rows in row order).
+__device__ __forceinline__ void few_gauss_loss_rows(const GArgs &g, float *S, const float *pr, const float *act_e,
+                                                    const float *grow_e, long long s0, int rk, float inv_b, float entp,
+                                                    float &lsum, float &klsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, rq = lane >> 4;
+    const int row = 4 * wave + rq;
+    const int A = g.A;
+    const long long S_ = g.S;
+    const GLay &La = g.L[g.aout];
+    const GLay &Lc = g.L[g.cout];
+    float *mup = S + La.yr + row * La.ld;
+    float *dla = S + La.dy + row * La.ld;
+    const bool live = row < rk;
+    const int rr = live ? row : 0;
+    const int a0 = sub, a1 = sub + 16;
+    const bool on0 = a0 < A, on1 = a1 < A;
+    const float l0 = pr[g.lso + (on0 ? a0 : 0)], l1 = pr[g.lso + (on1 ? a1 : 0)];
+    const float pa0 = act_e[(size_t)(s0 + rr) * A + (on0 ? a0 : 0)], pa1 = act_e[(size_t)(s0 + rr) * A + (on1 ? a1 : 0)];
+    const float pm0 = mup[on0 ? a0 : 0], pm1 = mup[on1 ? a1 : 0];
+    const float olp = grow_e[s0 + rr], Ad = grow_e[S_ + s0 + rr];
+    const float Rt = grow_e[2 * S_ + s0 + rr], ov = grow_e[3 * S_ + s0 + rr];
+    const float v = S[Lc.yr + row * Lc.ld];
+    const float ls0 = on0 ? l0 : 0.f, ls1 = on1 ? l1 : 0.f;
+    const float iv0 = gauss_inv_var(ls0), iv1 = gauss_inv_var(ls1);
+    const float H = gauss_entropy(A, row_sum(ls0 + ls1));
+    const LossCoef k = loss_coef(g, inv_b, entp);
+    const float mu0 = on0 ? pm0 : 0.f, mu1 = on1 ? pm1 : 0.f;
+    const float av0 = on0 ? pa0 : 0.f, av1 = on1 ? pa1 : 0.f;
+    const float lp = row_sum((on0 ? gauss_logp_term(av0, mu0, ls0) : 0.f) + (on1 ? gauss_logp_term(av1, mu1, ls1) : 0.f));
+    float gl, gv;
+    Acc one;
+    loss_sample(lp, olp, Ad, Rt, ov, v, H, k, gl, gv, one);
+    const float z0 = av0 - mu0, z1 = av1 - mu1;
+    // rows past the slice: a zero gradient (their tiles hold the last minibatch's rows)
+    if (on0) {
+        dla[a0] = live ? gauss_g_mean(gl, z0, iv0) : 0.f;
+        mup[a0] = live ? gauss_g_log_std(gl, z0, iv0) : 0.f;
+    }
+    if (on1) {
+        dla[a1] = live ? gauss_g_mean(gl, z1, iv1) : 0.f;
+        mup[a1] = live ? gauss_g_log_std(gl, z1, iv1) : 0.f;
+    }
+    if (sub == 0) {
+        S[Lc.dy + row * Lc.ld] = live ? gv : 0.f;
+        if (live) {
+            lsum += (one.pg + g.vf * 0.5f * one.vl - entp * H) * inv_b;
+            klsum += one.kl * inv_b;  // approx_kl (ppo.py:899-902)
+        }
+    }
+}
+
 // One update's gradient of a partner's rows (rk <= 16 of them, observations
 // at xobs, rollout rows s0 ..) into the gradient row G, plus the loss /
 // approx_kl partial sums: the few-row counterpart of minibatch_grads, same
 // float operations per element.  S: the LDS tiles (plan_few).
+// GAUSS: gact_e holds the rows' float actions [A] (few_gauss_loss_rows).
+template <bool GAUSS>
 __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float *pr, const float *wb, float *G,
                                           const float *xobs, const int *gact_e, const unsigned *gmask_e,
                                           const float *grow_e, long long s0, int rk, float inv_b, float entp,
@@ -781,7 +993,10 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
     few_forward(g.L, g.nl, S, pr, prs, g.oc, g.ld0, st);
 
     // ---- PPO loss row pass: logits / value -> d(logits), d(value) (ppo.py:876-908)
-    {
+    if constexpr (GAUSS) {
+        few_gauss_loss_rows(g, S, pr, reinterpret_cast<const float *>(gact_e), grow_e, s0, rk, inv_b, entp, lsum,
+                            klsum);
+    } else {
         const GLay &La = g.L[g.aout];
         const GLay &Lc = g.L[g.cout];
         const float *lgp = S + La.yr + row * La.ld;
@@ -841,6 +1056,20 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
         }
     }
     __syncthreads();
+    if constexpr (GAUSS) {
+        // d(log_std): the 16 rows' terms (left in the mean tile) in row order, and
+        // the entropy's -ent_coef / b per row of the slice
+        if (wave == kGW - 1 && lane < A) {
+            const GLay &La = g.L[g.aout];
+            float v[kFR];
+#pragma unroll
+            for (int b = 0; b < kFR; ++b) v[b] = S[La.yr + b * La.ld + lane];
+            float sum = 0.f;
+#pragma unroll
+            for (int b = 0; b < kFR; ++b) sum += v[b];
+            G[g.lso + lane] = sum + (-entp * inv_b) * (float)rk;
+        }
+    }
     if (st) st[17] = (long long)__builtin_readcyclecounter();
 
     // ---- backward, layer by layer (reverse) ------------------------------
@@ -928,12 +1157,12 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
 
 // FEW: the few-row form (few_grads, activations in dynamic LDS); else the
 // general form (minibatch_grads over the partner's global scratch)
-template <bool FEW>
+template <bool FEW, bool GAUSS>
 __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g) {
     __shared__ float red[2 * kGW];
     __shared__ __attribute__((aligned(16))) float lds[kGemmLds];
     __shared__ float colp[2 * 3 * kGW * 128];
-    __shared__ float colo[kGW * 33];
+    __shared__ float colo[kGW * kColo<GAUSS>];
     __shared__ int s_ok;
     __shared__ long long s_st[16 + kGStampsIn];  // phase stamps (agent 0, partner 0, update 1), then per layer
     if (g.skip && __hip_atomic_load(g.skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;
@@ -1008,7 +1237,7 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g
     for (int e = 0; e < Ep; ++e) {
         const size_t ge = (size_t)e * P + p;
         const float *gobs_e = g.gobs + ge * S * D;
-        const int *gact_e = g.gact + ge * S;
+        const int *gact_e = g.gact + ge * S * (GAUSS ? g.A : 1);
         const unsigned *gmask_e = g.gmask ? g.gmask + ge * S : nullptr;
         const float *grow_e = g.grow + ge * 4 * S;
         for (int mb = 0; mb < nmb; ++mb) {
@@ -1029,12 +1258,12 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g
             float lsum = 0.f, klsum = 0.f;
             if (rk > 0) {
                 if constexpr (FEW)
-                    few_grads(g, base, pr, wb, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e, s0 + r0, rk, inv_b,
-                              entp, lsum, klsum, stamp ? s_st + 16 : nullptr);
+                    few_grads<GAUSS>(g, base, pr, wb, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e, s0 + r0, rk,
+                                     inv_b, entp, lsum, klsum, stamp ? s_st + 16 : nullptr);
                 else
-                    minibatch_grads(g, base, wb, pr, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e,
-                                                      grow_e, s0 + r0, rk, inv_b, entp, lds, colp, colo, lsum, klsum,
-                                                      stamp ? s_st + 16 : nullptr);
+                    minibatch_grads<GAUSS>(g, base, wb, pr, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e,
+                                           s0 + r0, rk, inv_b, entp, lds, colp, colo, lsum, klsum,
+                                           stamp ? s_st + 16 : nullptr);
             } else {  // no rows this minibatch (a short last minibatch): publish zeros
                 for (int i = tid; i < n; i += kGT) G[i] = 0.f;
             }
@@ -1247,26 +1476,27 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g
 struct GraphWs {
     size_t gobs, gact, gmask, grow, agents, total;
 };
-GraphWs graph_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs) {
+// aw: 4-byte words of a row's gathered action (1: the categorical index; A: a Gaussian head's floats)
+GraphWs graph_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int aw) {
     GraphWs w;
     const size_t per = (size_t)epochs * P * S;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     w.gobs = 0;
     w.gact = up(per * a.D * 4);
-    w.gmask = w.gact + up(per * 4);
+    w.gmask = w.gact + up(per * 4 * aw);
     w.grow = w.gmask + up(per * 4);
     w.agents = w.grow + up(per * 4 * 4);
     w.total = w.agents + (size_t)P * a.ws_agent * 4;
     return w;
 }
 
-template <bool FEW>
+template <bool FEW, bool GAUSS>
 int part_occupancy(size_t dyn) {  // co-resident partner workgroups per CU with dyn bytes of dynamic LDS
     static size_t last = (size_t)-1;
     static int n = 1;
     if (dyn != last) {
         int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, ppo_learn_graph_part_kernel<FEW>, kGT, dyn) != hipSuccess)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, ppo_learn_graph_part_kernel<FEW, GAUSS>, kGT, dyn) != hipSuccess)
             v = 1;
         n = v < 1 ? 1 : v;
         last = dyn;
@@ -1274,16 +1504,17 @@ int part_occupancy(size_t dyn) {  // co-resident partner workgroups per CU with 
     return n;
 }
 // dynamic LDS the few-row form may take: the CU's 160 KB less the kernel's
-// static LDS (queried once)
+// static LDS (queried once per head)
+template <bool GAUSS>
 size_t few_lds_budget() {
     static size_t b = 0;
     if (!b) {
         hipFuncAttributes fa{};
-        const size_t st = hipFuncGetAttributes(&fa, (const void *)ppo_learn_graph_part_kernel<true>) == hipSuccess
+        const size_t st = hipFuncGetAttributes(&fa, (const void *)ppo_learn_graph_part_kernel<true, GAUSS>) == hipSuccess
                               ? fa.sharedSizeBytes
                               : 8 * 1024;
         b = st < kLdsMax ? kLdsMax - st : 1;
-        (void)hipFuncSetAttribute((const void *)ppo_learn_graph_part_kernel<true>,
+        (void)hipFuncSetAttribute((const void *)ppo_learn_graph_part_kernel<true, GAUSS>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
     }
     return b;
@@ -1293,8 +1524,9 @@ size_t few_lds_budget() {
 // LDS: per layer Y, xhat + rstd (LayerNorm), dY, each [16][ld]; the
 // observation tile; one dY' tile for the LN-affine gradients.  -> LDS bytes
 // (0: the plan does not fit, or the graph is invalid)
+template <bool GAUSS>
 size_t plan_few(const agx_ppo_graph *net, GArgs &a) {
-    if (plan_graph(net, kFR, a) != AGX_OK) return 0;
+    if (plan_graph(net, kFR, a, GAUSS ? net->n_actions : 0) != AGX_OK) return 0;
     auto ldof = [](int w) { return (w + 15) / 16 * 16 + 4; };
     long long off = 0;
     int ldmax = 0;
@@ -1331,7 +1563,7 @@ size_t plan_few(const agx_ppo_graph *net, GArgs &a) {
     a.lds_floats = (off + 3) & ~3ll;
     a.ws_part = 0;  // no global activation scratch
     const size_t bytes = (size_t)a.lds_floats * 4;
-    return bytes <= few_lds_budget() ? bytes : 0;
+    return bytes <= few_lds_budget<GAUSS>() ? bytes : 0;
 }
 // How a learn() runs, chosen per call (the workspace query makes the same
 // choice): the few-row partnered form when a minibatch splits into at most
@@ -1345,6 +1577,7 @@ struct Split {
     bool few = false;
     size_t dyn = 0;  // dynamic LDS bytes (few-row form)
 };
+template <bool GAUSS>
 Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
     Split sp;
     int rows = 16;
@@ -1359,8 +1592,8 @@ Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
     if (k > cap) k = cap;
     if (few_ok && k > 1 && (batch + k - 1) / k <= kFR) {
         GArgs a{};
-        const size_t dyn = plan_few(net, a);
-        if (dyn && (int64_t)sp.Q * k <= (int64_t)part_occupancy<true>(dyn) * cus) {
+        const size_t dyn = plan_few<GAUSS>(net, a);
+        if (dyn && (int64_t)sp.Q * k <= (int64_t)part_occupancy<true, GAUSS>(dyn) * cus) {
             sp.few = true;
             sp.dyn = dyn;
             sp.K = k;
@@ -1368,8 +1601,8 @@ Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
             return sp;
         }
     }
-    while (k > 1 && (int64_t)sp.Q * k > (int64_t)part_occupancy<false>(0) * cus) --k;
-    if (k > 1 && (int64_t)P * k > (int64_t)part_occupancy<false>(0) * cus) k = 1;
+    while (k > 1 && (int64_t)sp.Q * k > (int64_t)part_occupancy<false, GAUSS>(0) * cus) --k;
+    if (k > 1 && (int64_t)P * k > (int64_t)part_occupancy<false, GAUSS>(0) * cus) k = 1;
     sp.K = k < 1 ? 1 : k;
     sp.R = (int)((batch + sp.K - 1) / sp.K);
     return sp;
@@ -1378,14 +1611,14 @@ struct PartWs {
     size_t cnt, gobs, gact, gmask, grow, scratch, wt, slabs, sums, total;
     long long nslab;
 };
-PartWs part_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int K) {
+PartWs part_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int K, int aw) {
     PartWs w;
     const size_t per = (size_t)epochs * P * S;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     w.cnt = 0;
     w.gobs = up(((size_t)4 * P + 1 + (size_t)kMaxGK * P) * 4);
     w.gact = w.gobs + up(per * a.D * 4);
-    w.gmask = w.gact + up(per * 4);
+    w.gmask = w.gact + up(per * 4 * aw);
     w.grow = w.gmask + up(per * 4);
     w.scratch = w.grow + up(per * 4 * 4);
     w.wt = w.scratch + up((size_t)P * K * a.ws_part * 4);
@@ -1396,59 +1629,130 @@ PartWs part_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int K) {
     return w;
 }
 
-}  // namespace
-}  // namespace agx
-
-using namespace agx;
-
-static long long *&g_graph_stamps() {
-    static long long *p = nullptr;
-    return p;
+// ppo_gather_kernel (learner.hip) for a Gaussian head: the rollout's float
+// actions [P][S][A] gathered in minibatch order to gact [E P][S][A]; the
+// observations, the advantage normalisation, the rollout rows, the counters
+// and the permutation check as there.
+__global__ void ppo_gauss_gather_kernel(const float *__restrict__ obs, const float *__restrict__ act,
+                                        const float *__restrict__ old_logp, const float *__restrict__ adv,
+                                        const float *__restrict__ ret, const float *__restrict__ old_v,
+                                        const double *__restrict__ adv_stats, const long long *__restrict__ perms,
+                                        int A, long long S, int D, int P, float *__restrict__ gobs,
+                                        float *__restrict__ gact, float *__restrict__ grow,
+                                        unsigned *__restrict__ counters, int ncounters,
+                                        const int *__restrict__ epochs_p, unsigned *__restrict__ err) {
+    const int ep = blockIdx.y;  // e * P + p
+    const int p = ep % P;
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int i = threadIdx.x; i < ncounters; i += blockDim.x) counters[i] = 0u;
+    if (j >= S) return;
+    if (epochs_p && ep / P >= epochs_p[p]) return;
+    long long src = perms[(size_t)ep * S + j];
+    if (src < 0 || src >= S) {
+        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        src = 0;
+    }
+    const size_t sp = (size_t)p * S + src, dst = (size_t)ep * S + j;
+    for (int d = 0; d < D; ++d) gobs[dst * D + d] = obs[sp * D + d];
+    for (int d = 0; d < A; ++d) gact[dst * A + d] = act[sp * A + d];
+    float *gr = grow + (size_t)ep * 4 * S;
+    double a = adv[sp];
+    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
+    gr[j] = old_logp[sp];
+    gr[S + j] = (float)a;
+    gr[2 * S + j] = ret[sp];
+    gr[3 * S + j] = old_v[sp];
 }
-extern "C" int agx_debug_graph_stamps(int64_t *buf) {
-    g_graph_stamps() = reinterpret_cast<long long *>(buf);
+
+// The layers and the A log_std floats at lso tile the parameter row exactly,
+// and log_std lies in the actor clip group [0, critic_start).
+int gauss_check(const agx_ppo_graph *net, int64_t lso) {
+    GArgs a{};
+    AGX_REQUIRE(net, "agx_ppo_gauss_graph_check: null graph");
+    const int rc = plan_graph(net, 1, a, net->n_actions);
+    if (rc != AGX_OK) return rc;
+    const int A = net->n_actions;
+    AGX_REQUIRE(lso >= 0 && lso + A <= net->critic_start,
+                "agx_ppo_gauss_graph_check: log_std [%lld, %lld) outside the actor group [0, %d)", (long long)lso,
+                (long long)lso + A, net->critic_start);
+    // every parameter range by offset: each must start where the previous one ends
+    long long beg[4 * kGL + 1], len[4 * kGL + 1];
+    int nr = 0;
+    auto add = [&](long long b, long long n) {
+        int i = nr++;
+        for (; i > 0 && beg[i - 1] > b; --i) {
+            beg[i] = beg[i - 1];
+            len[i] = len[i - 1];
+        }
+        beg[i] = b;
+        len[i] = n;
+    };
+    for (int l = 0; l < net->n_layers; ++l) {
+        const agx_ppo_layer &x = net->layers[l];
+        add(x.w, (long long)x.fin * x.fout);
+        add(x.b, x.fout);
+        if (x.ln == 2) {
+            add(x.ln_w, x.fout);
+            add(x.ln_b, x.fout);
+        }
+    }
+    add(lso, A);
+    long long at = 0;
+    for (int i = 0; i < nr; ++i) {
+        AGX_REQUIRE(beg[i] == at, "agx_ppo_gauss_graph_check: log_std_off %lld is not the gap the layers leave",
+                    (long long)lso);
+        at += len[i];
+    }
+    AGX_REQUIRE(at == net->n_params, "agx_ppo_gauss_graph_check: log_std_off %lld is not the gap the layers leave",
+                (long long)lso);
     return AGX_OK;
 }
 
-extern "C" int agx_ppo_graph_check(const agx_ppo_graph *net) {
-    GArgs a{};
-    return plan_graph(net, 1, a);
-}
-
-extern "C" size_t agx_ppo_learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S,
-                                                      int64_t epochs, int64_t batch) {
+template <bool GAUSS>
+size_t learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S, int64_t epochs, int64_t batch) {
     GArgs a{};
     if (P <= 0 || S <= 0 || epochs <= 0 || batch <= 0) return 0;
     const int64_t bb = batch < S ? batch : S;
-    if (plan_graph(net, bb, a) != AGX_OK) return 0;
-    size_t total = graph_ws(a, P, S, epochs).total;
-    const Split sp = graph_split(net, P, bb);
+    const int extra = GAUSS ? net->n_actions : 0, aw = GAUSS ? net->n_actions : 1;
+    if (plan_graph(net, bb, a, extra) != AGX_OK) return 0;
+    size_t total = graph_ws(a, P, S, epochs, aw).total;
+    const Split sp = graph_split<GAUSS>(net, P, bb);
     if (sp.K > 1) {  // room for either kernel: the split may change with the call's batch
         GArgs ap{};
-        if (sp.few ? !plan_few(net, ap) : plan_graph(net, sp.R, ap) != AGX_OK) return 0;
-        const size_t t = part_ws(ap, P, S, epochs, sp.K).total;
+        if (sp.few ? !plan_few<GAUSS>(net, ap) : plan_graph(net, sp.R, ap, extra) != AGX_OK) return 0;
+        const size_t t = part_ws(ap, P, S, epochs, sp.K, aw).total;
         total = t > total ? t : total;
     }
     return total;
 }
 
-extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn_args *x, void *workspace,
-                                   void *stream) {
-    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_graph: null net / args / workspace");
+long long *&g_graph_stamps() {
+    static long long *p = nullptr;
+    return p;
+}
+
+// agx_ppo_learn_graph (GAUSS: agx_ppo_learn_gauss_graph, log_std at lso,
+// validated by the caller); `what` names the entry point in errors
+template <bool GAUSS>
+int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const agx_ppo_learn_args *x,
+                void *workspace, void *stream) {
     AGX_REQUIRE(x->params && x->exp_avg && x->exp_avg_sq && x->adam_step && x->lr && x->obs && x->actions &&
                     x->old_logp && x->adv && x->ret && x->old_value && x->perms,
-                "agx_ppo_learn_graph: null pointer");
+                "%s: null pointer", what);
     const int64_t P = x->P, S = x->S, epochs = x->epochs, batch = x->batch;
     AGX_REQUIRE(P > 0 && P <= 65535 && S > 0 && S < (1ll << 31) && epochs > 0 && batch > 0 && epochs * P <= 65535,
-                "agx_ppo_learn_graph: bad sizes P=%lld S=%lld epochs=%lld batch=%lld", (long long)P, (long long)S,
+                "%s: bad sizes P=%lld S=%lld epochs=%lld batch=%lld", what, (long long)P, (long long)S,
                 (long long)epochs, (long long)batch);
     const int64_t bb = batch < S ? batch : S;
-    const Split sp = graph_split(net, P, bb);
+    const Split sp = graph_split<GAUSS>(net, P, bb);
     const int K = sp.K, R = sp.R, Q = sp.Q;
     GArgs a{};
-    const int rc = plan_graph(net, K > 1 ? R : bb, a);
+    const int extra = GAUSS ? net->n_actions : 0, aw = GAUSS ? net->n_actions : 1;
+    const int rc = plan_graph(net, K > 1 ? R : bb, a, extra);
     if (rc != AGX_OK) return rc;
-    if (sp.few) AGX_REQUIRE(plan_few(net, a) == sp.dyn, "agx_ppo_learn_graph: few-row plan changed");
+    if (sp.few) AGX_REQUIRE(plan_few<GAUSS>(net, a) == sp.dyn, "%s: few-row plan changed", what);
+    a.lso = lso;
     char *ws = static_cast<char *>(workspace);
     hipStream_t s = as_stream(stream);
     size_t o_gobs, o_gact, o_gmask, o_grow;
@@ -1457,12 +1761,12 @@ extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn
     PartWs pw{};
     GraphWs w{};
     if (K > 1) {
-        pw = part_ws(a, P, S, epochs, K);
+        pw = part_ws(a, P, S, epochs, K, aw);
         o_gobs = pw.gobs, o_gact = pw.gact, o_gmask = pw.gmask, o_grow = pw.grow;
         counters = reinterpret_cast<unsigned *>(ws + pw.cnt);
         ncounters = (int)(pw.gobs / sizeof(unsigned));
     } else {
-        w = graph_ws(a, P, S, epochs);
+        w = graph_ws(a, P, S, epochs, aw);
         o_gobs = w.gobs, o_gact = w.gact, o_gmask = w.gmask, o_grow = w.grow;
     }
     float *gobs = reinterpret_cast<float *>(ws + o_gobs);
@@ -1470,12 +1774,19 @@ extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn
     unsigned *gmask = x->action_masks ? reinterpret_cast<unsigned *>(ws + o_gmask) : nullptr;
     float *grow = reinterpret_cast<float *>(ws + o_grow);
     dim3 ggrid((unsigned)ceil_div(S, 256), (unsigned)(epochs * P));
-    ppo_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
-                                            x->adv, x->ret, x->old_value, x->adv_stats,
-                                            reinterpret_cast<const long long *>(x->perms), x->action_masks, a.A, S,
-                                            a.D, (int)P, gobs, gact, gmask, grow, counters, ncounters,
-                                            x->epochs_per_agent, x->error_word);
-    const int rc2 = check_launch("agx_ppo_learn_graph gather");
+    if constexpr (GAUSS)
+        ppo_gauss_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const float *>(x->actions), x->old_logp,
+                                                      x->adv, x->ret, x->old_value, x->adv_stats,
+                                                      reinterpret_cast<const long long *>(x->perms), a.A, S, a.D,
+                                                      (int)P, gobs, reinterpret_cast<float *>(gact), grow, counters,
+                                                      ncounters, x->epochs_per_agent, x->error_word);
+    else
+        ppo_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
+                                                x->adv, x->ret, x->old_value, x->adv_stats,
+                                                reinterpret_cast<const long long *>(x->perms), x->action_masks, a.A,
+                                                S, a.D, (int)P, gobs, gact, gmask, grow, counters, ncounters,
+                                                x->epochs_per_agent, x->error_word);
+    const int rc2 = check_launch(what);
     if (rc2) return rc2;
     a.ws = reinterpret_cast<float *>(ws + (K > 1 ? pw.scratch : w.agents));
     a.params = x->params;
@@ -1525,13 +1836,58 @@ extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn
             const char *wt = getenv("AGX_LEARN_WRITETHROUGH");
             a.write_through = wt && atoi(wt) != 0;
         }
-        AGX_REQUIRE((int64_t)Q * K <= 65535, "agx_ppo_learn_graph: too many workgroups");
+        AGX_REQUIRE((int64_t)Q * K <= 65535, "%s: too many workgroups", what);
         if (sp.few)
-            ppo_learn_graph_part_kernel<true><<<(unsigned)(Q * K), kGT, sp.dyn, s>>>(a);
+            ppo_learn_graph_part_kernel<true, GAUSS><<<(unsigned)(Q * K), kGT, sp.dyn, s>>>(a);
         else
-            ppo_learn_graph_part_kernel<false><<<(unsigned)(Q * K), kGT, 0, s>>>(a);
+            ppo_learn_graph_part_kernel<false, GAUSS><<<(unsigned)(Q * K), kGT, 0, s>>>(a);
     } else {
-        ppo_learn_graph_kernel<<<(unsigned)P, kGT, 0, s>>>(a);
+        ppo_learn_graph_kernel<GAUSS><<<(unsigned)P, kGT, 0, s>>>(a);
     }
-    return check_launch("agx_ppo_learn_graph");
+    return check_launch(what);
+}
+
+}  // namespace
+}  // namespace agx
+
+using namespace agx;
+
+extern "C" int agx_debug_graph_stamps(int64_t *buf) {
+    g_graph_stamps() = reinterpret_cast<long long *>(buf);
+    return AGX_OK;
+}
+
+extern "C" int agx_ppo_graph_check(const agx_ppo_graph *net) {
+    GArgs a{};
+    return plan_graph(net, 1, a);
+}
+
+extern "C" size_t agx_ppo_learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S,
+                                                      int64_t epochs, int64_t batch) {
+    return learn_graph_workspace_bytes<false>(net, P, S, epochs, batch);
+}
+
+extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn_args *x, void *workspace,
+                                   void *stream) {
+    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_graph: null net / args / workspace");
+    return learn_graph<false>("agx_ppo_learn_graph", net, -1, x, workspace, stream);
+}
+
+extern "C" int agx_ppo_gauss_graph_check(const agx_ppo_graph *net, int64_t log_std_off) {
+    return gauss_check(net, log_std_off);
+}
+
+extern "C" size_t agx_ppo_learn_gauss_graph_workspace_bytes(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
+                                                            int64_t S, int64_t epochs, int64_t batch) {
+    if (gauss_check(net, log_std_off) != AGX_OK) return 0;
+    return learn_graph_workspace_bytes<true>(net, P, S, epochs, batch);
+}
+
+extern "C" int agx_ppo_learn_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, const agx_ppo_learn_args *x,
+                                         void *workspace, void *stream) {
+    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_gauss_graph: null net / args / workspace");
+    const int rc = gauss_check(net, log_std_off);
+    if (rc != AGX_OK) return rc;
+    AGX_REQUIRE(!x->action_masks, "agx_ppo_learn_gauss_graph: action masks do not apply to a Gaussian head");
+    return learn_graph<true>("agx_ppo_learn_gauss_graph", net, log_std_off, x, workspace, stream);
 }

@@ -70,6 +70,7 @@ struct GArgs {
     int *epochs_out;
     const unsigned *skip;
     int dbg;  // diagnostic phase skips (AGX_GRAPH_DEBUG; timing attribution only, results wrong)
+    long long lso;  // Gaussian head: the A log_std floats in the parameter row (gact: float [..][A])
 };
 
 // C[M x N] = A[M x K] . B[N x K]^T, both operands contiguous along k (the

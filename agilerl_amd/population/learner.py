@@ -1,7 +1,8 @@
 """Host side of the fused PPO learners: agx_ppo_learn (learner.hip, the
-compiled network shapes) and agx_ppo_learn_graph (graph_learner.hip, any MLP
+compiled network shapes), agx_ppo_learn_graph (graph_learner.hip, any MLP
 actor-critic as a runtime layer list: the shapes architecture mutations
-produce)."""
+produce) and agx_ppo_learn_gauss_graph (the same with a Gaussian head: Box
+action spaces)."""
 
 from __future__ import annotations
 
@@ -144,6 +145,7 @@ class AgxPPOLearnArgs(ctypes.Structure):
 
 class FusedLearner:
     batch_ws = None  # the graph learner's scratch is sized by the minibatch
+    name = "agx_ppo_learn"  # the entry point, for error messages
 
     def __init__(self, pop):
         self.desc = net_descriptor(pop.spec)
@@ -204,7 +206,7 @@ class FusedLearner:
         self.args.skip_if_set = skip_if_set
         rc = self.fn(self.dref, self.aref, self.ws.data_ptr(), _lib.stream())
         if rc != 0:
-            _lib.check(rc, "agx_ppo_learn")
+            _lib.check(rc, self.name)
         return self.loss
 
     def timed_out(self, pop) -> bool:
@@ -237,7 +239,31 @@ class GraphLearner(FusedLearner):
         return False  # one workgroup per agent: no partner hand-off to time out
 
 
+class GaussGraphLearner(GraphLearner):
+    """agx_ppo_learn_gauss_graph: GraphLearner for a Box-action population (the
+    actor output is the Gaussian mean, log_std at ``pop.spec.log_std``)."""
+
+    def __init__(self, pop):
+        self.desc = pop.gauss_learn_descriptor()
+        if self.desc is None:
+            raise _lib.AgxError("network outside the Gaussian graph learner's coverage")
+        lib = _lib.load()
+        self.batch_ws = pop.split_batch
+        self.log_std = int(pop.spec.log_std)
+        nbytes = lib.agx_ppo_learn_gauss_graph_workspace_bytes(ctypes.byref(self.desc), self.log_std, pop.P, pop.S,
+                                                               pop.update_epochs, self.batch_ws)
+        if nbytes == 0:
+            raise _lib.AgxError(f"agx_ppo_learn_gauss_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=pop.device)
+        self._outputs(pop)
+        gauss = lib.agx_ppo_learn_gauss_graph
+        self.fn = lambda desc, args, ws, stream: gauss(desc, self.log_std, args, ws, stream)
+        self.name = "agx_ppo_learn_gauss_graph"
+
+
 def make_learner(pop) -> FusedLearner:
+    if pop.gaussian:
+        return GaussGraphLearner(pop)
     return FusedLearner(pop) if pop.fused_descriptor() is not None else GraphLearner(pop)
 
 

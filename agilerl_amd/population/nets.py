@@ -274,6 +274,21 @@ class GaussianActorCriticSpec(ActorCriticSpec):
             return None
         return d
 
+    def gauss_learn_descriptor(self):
+        """agx_ppo_graph of the networks for agx_ppo_learn_gauss_graph (with
+        ``log_std`` as its log_std_off), or None when the fused Gaussian
+        learner does not take the layer list: then the autograd learner runs."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+
+        d = layer_list(self)
+        lib = _lib.load(require_gpu=False)  # pure host-side validation
+        if d is None or lib.agx_ppo_gauss_graph_check(ctypes.byref(d), self.log_std) != 0:
+            return None
+        return d
+
 
 def categorical(logits: torch.Tensor):
     """log-softmax and entropy as ``agilerl/utils/torch_utils.py:142-199``:

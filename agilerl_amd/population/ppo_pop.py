@@ -32,9 +32,11 @@ Two learner back ends share this state:
                     not cover.
 
 A Gaussian spec (Box actions, nets.GaussianActorCriticSpec) stores float
-actions (P, T, N, A), acts through agx_ppo_act_gauss_graph and learns on the
-``fused=False`` path with the fused Gaussian loss kernel
-(agx_ppo_gauss_loss_fwd_bwd); the categorical kernels never see it.
+actions (P, T, N, A), acts through agx_ppo_act_gauss_graph and learns through
+agx_ppo_learn_gauss_graph (the runtime-shape learner with a Gaussian head);
+with ``fused=False``, AGX_GAUSS_FUSED=0 or a layer list that learner does not
+take, on the autograd path with the fused Gaussian loss kernel
+(agx_ppo_gauss_loss_fwd_bwd).  The categorical kernels never see it.
 """
 
 from __future__ import annotations
@@ -176,6 +178,7 @@ class PPOPopulation:
         self._gdesc = None
         self._edesc = None
         self._gauss = None
+        self._glearn = None
         self._alloc_rollout()
         self.env_base_d = torch.tensor([i * self.N for i in self.agent_ids], dtype=torch.int64, device=self.device)
         self.learn_steps = 0
@@ -294,6 +297,21 @@ class PPOPopulation:
                                     _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
         return self._gauss
 
+    def gauss_learn_descriptor(self):
+        """agx_ppo_graph of a Gaussian population's networks for the fused
+        learner (agx_ppo_learn_gauss_graph, log_std at ``spec.log_std``); None:
+        not a Gaussian population, ``fused`` off, AGX_GAUSS_FUSED=0, or a layer
+        list agx_ppo_gauss_graph_check rejects — then the autograd learner runs."""
+        if not self.gaussian or not self.fused or os.environ.get("AGX_GAUSS_FUSED", "1") == "0":
+            return None
+        if self._glearn is None:
+            self._glearn = self.spec.gauss_learn_descriptor() or False
+        return self._glearn or None
+
+    def _fused_learner(self) -> bool:
+        """True when learn() runs a fused HIP learner (either head)."""
+        return self.learn_descriptor() is not None or self.gauss_learn_descriptor() is not None
+
     @torch.no_grad()
     def act_into(self, t: int, actions_flat: torch.Tensor | None = None) -> None:
         """Rollout policy step for slot t: reads obs[:, t], writes actions /
@@ -397,7 +415,7 @@ class PPOPopulation:
         learn's permutations right away (the pipelined runner passes False and
         prefetches after pacing the rollout instead)."""
         self.learn_steps += 1
-        if self.learn_descriptor() is not None:
+        if self._fused_learner():  # the categorical kernels, else the Gaussian graph learner
             from .learner import fused_learn
 
             loss = fused_learn(self, skip_if_set=skip_if_set)
@@ -557,7 +575,7 @@ class PPOPopulation:
         host pacing it, the device is waiting for this thread, so nothing
         there may wait for the device — and a hipMalloc / hipHostMalloc, or an
         event sync, can."""
-        if self.learn_descriptor() is not None:
+        if self._fused_learner():
             from .learner import learner_stale, make_learner
 
             if learner_stale(self):

@@ -49,6 +49,33 @@ int agx_ppo_act_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, int64
                             float *actions_flat, const float *clip_low, const float *clip_high,
                             const int64_t *agent_env_base, void *workspace, void *stream);
 
+/* PPO.learn for a Gaussian head: agx_ppo_learn_graph (agx_graph.h) with the
+ * actor output as the mean and the A log_std floats at log_std_off of every
+ * agent's row.  log_std belongs to the actor clip group and to no layer: the
+ * layers and [log_std_off, log_std_off + A) tile the row exactly, with
+ * log_std_off + A <= critic_start.
+ *
+ * agx_ppo_gauss_graph_check: host-only (no HIP call).  AGX_OK when the learner
+ * takes this net; AGX_EINVAL with the reason in agx_last_error otherwise (A
+ * outside 1..AGX_PPO_GRAPH_MAX_ACTIONS, log_std_off not the gap the layers
+ * leave, the gap outside [0, critic_start), anything agx_ppo_graph_check
+ * rejects).
+ *
+ * agx_ppo_learn_gauss_graph takes agx_ppo_learn_graph's argument block with
+ * args->actions float [P][S][A]; args->action_masks must be NULL (AGX_EINVAL).
+ * Per-agent batch / epochs / ent_coef, target_kl, skip_if_set, loss_out /
+ * kl_out / epochs_out, error_word and adam_step behave as there; so do the
+ * forms the call picks between (AGX_GRAPH_FEW, AGX_GRAPH_ROWS,
+ * AGX_GRAPH_SPLIT) and the fixed summation order: an agent's update does not
+ * depend on which other agents share the launch.  The per-row math is that of
+ * agx_ppo_gauss_loss_fwd_bwd below.  The workspace holds the gathered float
+ * actions (4 A bytes per row and epoch). */
+int agx_ppo_gauss_graph_check(const agx_ppo_graph *net, int64_t log_std_off);
+size_t agx_ppo_learn_gauss_graph_workspace_bytes(const agx_ppo_graph *net, int64_t log_std_off, int64_t P, int64_t S,
+                                                 int64_t epochs, int64_t batch);
+int agx_ppo_learn_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, const agx_ppo_learn_args *args,
+                              void *workspace, void *stream);
+
 /* The Gaussian twin of agx_ppo_loss_fwd_bwd (agx.h; ppo.py:868-902): num_minibatches
  * minibatches of `batch` rows, minibatch m with its own log_std row.
  *   mean [nmb batch][A], value [nmb batch], log_std [nmb][A]     (network outputs / parameters)

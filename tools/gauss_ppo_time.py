@@ -3,14 +3,19 @@
   1. agx_ppo_act_gauss_graph per vector step, 8 agents x 128 envs, A = 6,
      default networks, against the categorical agx_ppo_act_graph at the same
      shape (the same forward, the categorical head);
-  2. learn() of the Box population (S = 2048, batch 128, 4 epochs), against the
-     same learner with the Gaussian loss written in plain torch ops.
+  2. learn() of the Box population on the autograd learner (S = 2048, batch
+     128, 4 epochs), against the same learner with the Gaussian loss written
+     in plain torch ops;
+  3. learn() of the same population through the fused Gaussian learner
+     (agx_ppo_learn_gauss_graph) against (a) the autograd learner of 2. and
+     (b) the categorical agx_ppo_learn_graph on a Discrete population with the
+     same layer list and n_actions = A.
 
 Device-event timing after a warm-up; each figure is the median of REPEATS
 windows, the two versions of a pair alternating inside one process.  Not part
 of bench.py.
 
-Usage:  python tools/gauss_ppo_time.py [--out FILE.json]
+Usage:  python tools/gauss_ppo_time.py [--only policy,learn,fused] [--out FILE.json]
 """
 
 from __future__ import annotations
@@ -90,7 +95,7 @@ def learn(P=8, N=128, S=2048, A=6) -> dict:
     from agilerl_amd.population.ppo_pop import PPOPopulation
 
     pop = PPOPopulation(spec_from_net_config(Box(-np.inf, np.inf, (8,)), Box(-1.0, 1.0, (A,)), None), P, N,
-                        learn_step=S, batch_size=128, update_epochs=4)
+                        learn_step=S, batch_size=128, update_epochs=4, fused=False)  # the autograd learner
     pop.obs.normal_()
     for t in range(pop.T):
         pop.act_into(t)
@@ -133,14 +138,54 @@ def learn(P=8, N=128, S=2048, A=6) -> dict:
             f"({updates} minibatch updates)", "hip_loss": h, "torch_loss": t}
 
 
+def fused_learn(P=8, N=128, S=2048, A=6) -> dict:
+    from agilerl_amd.algorithms.ppo import spec_from_net_config
+    from agilerl_amd.envs import Box, Discrete
+    from agilerl_amd.population.learner import GaussGraphLearner, GraphLearner
+    from agilerl_amd.population.ppo_pop import PPOPopulation
+
+    obs_space = Box(-np.inf, np.inf, (8,))
+    kw = dict(learn_step=S, batch_size=128, update_epochs=4)
+    box = PPOPopulation(spec_from_net_config(obs_space, Box(-1.0, 1.0, (A,)), None), P, N, **kw)
+    cat = PPOPopulation(spec_from_net_config(obs_space, Discrete(A), None), P, N, **kw)
+    for pop in (box, cat):
+        pop.obs.normal_()
+        for t in range(pop.T):
+            pop.act_into(t)
+        pop.rewards.normal_()
+        pop.finish_rollout(torch.randn(P, N, 8, device="cuda"), torch.zeros(P, N, dtype=torch.uint8, device="cuda"))
+    # the default networks are a compiled shape of agx_ppo_learn: pin the runtime-shape learner
+    cat._fused = GraphLearner(cat)
+
+    def run_torch():
+        box.fused = False  # gauss_learn_descriptor() is None: _learn_torch
+        try:
+            box.learn()
+        finally:
+            box.fused = True
+
+    f, c = _pair(box.learn, cat.learn, calls=20, warmup=5)
+    assert isinstance(box._fused, GaussGraphLearner) and isinstance(cat._fused, GraphLearner)
+    f2, t = _pair(box.learn, run_torch, calls=3, warmup=2)
+    box.check_errors()
+    cat.check_errors()
+    updates = box.n_updates() // P
+    return {"what": "learn() through the fused Gaussian learner", "shape": f"{P} agents x {N} envs, S = {S}, batch "
+            f"128, 4 epochs ({updates} minibatch updates), A = {A}, default networks",
+            "agx_ppo_learn_gauss_graph": f, "agx_ppo_learn_graph_categorical": c,
+            "agx_ppo_learn_gauss_graph_beside_autograd": f2, "autograd_learner": t}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only", default="policy,learn,fused", help="comma-separated: policy, learn, fused")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/gauss_ppo_time.py needs the GPU: a CPU run says nothing about these times")
     np.random.seed(0)
-    res = [policy_step(), learn()]
+    parts = {"policy": policy_step, "learn": learn, "fused": fused_learn}
+    res = [parts[k]() for k in args.only.split(",")]
     for r in res:
         print(json.dumps(r))
     if args.out:
