@@ -64,6 +64,27 @@ namespace agx {
 #ifndef AGX_LEARN_RS2
 #define AGX_LEARN_RS2 0
 #endif
+// Second partner hand-off (per-wave partial norms + loss / approx_kl words):
+// 8-byte {tag, value} words that the consumers sweep (1, default), or plain
+// words behind a full partner barrier (0; A/B builds)
+#ifndef AGX_LEARN_B2_TAGGED
+#define AGX_LEARN_B2_TAGGED 1
+#endif
+// ... swept by one wave per workgroup, which hands the words to the other seven
+// through LDS (1, default), or by every wave for itself (0; A/B builds)
+#ifndef AGX_LEARN_B2_SWEEP1
+#define AGX_LEARN_B2_SWEEP1 1
+#endif
+// Partners publish each layer's bias / LN-affine gradients as soon as they are
+// final (1, default) or all of them at the end of the minibatch (0; A/B builds)
+#ifndef AGX_LEARN_VEC_EARLY
+#define AGX_LEARN_VEC_EARLY 1
+#endif
+// A partner with one sub-batch per update stores its per-wave column partials
+// (1, default) or zero-fills and accumulates them like any other (0; A/B builds)
+#ifndef AGX_LEARN_STORE1
+#define AGX_LEARN_STORE1 1
+#endif
 
 constexpr int kNT = 512;
 constexpr int kNW = kNT / kWave;  // 8 waves
@@ -73,6 +94,14 @@ constexpr int kMaxK = 16;         // partner workgroups per agent
 constexpr int kMaxPT = 32;        // LDS parameter slots per thread: 8 float4 chunks
 constexpr int kMaxA = 16;
 constexpr int kMaxBlk = 28;
+
+// Tagged words of the second partner hand-off, per agent and update parity: one
+// {tag, value} word per (partner, wave, clip group) + the reduced loss and
+// approx_kl.  They follow the learner's counters in the block at the workspace
+// start that ppo_gather_kernel zeroes on every launch (16-byte aligned).
+constexpr int kB2Words = 2 * kNW * kMaxK + 2;
+constexpr size_t b2_words_off(size_t P) { return ((4 + kMaxK) * P + 1 + 3) / 4 * 4; }  // in counter words
+typedef __attribute__((address_space(1))) unsigned long long gu64;
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
@@ -99,7 +128,7 @@ struct LearnPlan {
     int l_x0, ld_x0, l_xe[3], ld_xe[3], l_re[3], l_xh, ld_xh, l_rh;
     int l_s1, l_s2, ld_s;
     int l_lg, l_dlg, l_dvb, l_val, l_row;
-    int l_red, red_e[3], red_h, l_stat, l_stamp;
+    int l_red, red_e[3], red_h, l_stat, l_stamp, l_b2x;
     int l_grad;  // gradient image of [0, param_end) (aliases the activations)
     int lds_floats, act_floats;
     int slab;  // floats per cross-workgroup gradient slab (parameter image + loss)
@@ -216,6 +245,7 @@ constexpr LearnPlan make_plan(NetDims d) {
     pl.l_stat = off; off += 5 * kNW;
     off = rup(off, 2);
     pl.l_stamp = off; off += 2 * 80;  // diagnostic phase stamps (agx_debug_learn_stamps)
+    pl.l_b2x = off; off += 2 * kNW * kMaxK + 4;  // second hand-off: the sweeping wave's words for the others
     pl.lds_floats = off;
     if (pl.lds_floats * 4 > 160 * 1024) return pl;
     // + the loss / approx_kl chunk + the partners' per-wave partial gradient norms
@@ -671,8 +701,9 @@ struct LearnArgs {
     float *sums;           // [P][2][slab] reduce-scattered gradient sums (double-buffered)
     unsigned *cnt;         // [P] arrival counters, [P] timeout word, [P+1+p] second-barrier,
                            // [2P+1+p] setup-barrier counters, [3P+1 + p*kMaxK + kk] XCC ids,
-                           // [3P+1 + P*kMaxK + p] third-barrier (parameter hand-off) counters
-                           // (zeroed per call)
+                           // [3P+1 + P*kMaxK + p] third-barrier (parameter hand-off) counters,
+                           // [b2_words_off(P) ..) the tagged second-hand-off words, 8 bytes each:
+                           // [P][2][kB2Words] (zeroed per call)
     int debug_stall;       // test hook: partner 1 of agent 0 never arrives
     int write_through;     // 1: always sc1 stores (AGX_LEARN_WRITETHROUGH=1; tests the cross-XCD form)
     const unsigned *skip;  // non-null and nonzero when the learner starts: return untouched
@@ -897,6 +928,12 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
     unsigned *ctr1 = in_vgpr(g.cnt + p);
     unsigned *ctr2 = in_vgpr(g.cnt + g.P + 1 + p);
     unsigned *ctr3 = in_vgpr(g.cnt + 3 * g.P + 1 + (size_t)g.P * kMaxK + p);
+#if AGX_LEARN_B2_TAGGED
+    // this agent's tagged hand-off words: [update parity][kB2Words]
+    unsigned long long *b2_p =
+        in_vgpr(reinterpret_cast<unsigned long long *>(g.cnt + b2_words_off(g.P)) + (size_t)p * 2 * kB2Words);
+    (void)ctr2;
+#endif
     for (int e = 0; e < Ep; ++e) {
         for (int mb = 0; mb < nmb; ++mb) {
             const long long s0 = (long long)mb * Bp;
@@ -906,7 +943,14 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
             f4 acc[kMaxSlot];
 #pragma unroll
             for (int s = 0; s < kMaxSlot; ++s) acc[s] = f4{0.f, 0.f, 0.f, 0.f};
-            for (int i = tid; i < pl.l_stat - pl.l_red; i += kNT) sm[pl.l_red + i] = 0.f;
+            // this partner's first sub-batch of the update is also its last (the
+            // bench's split: K partners x SB rows = the whole minibatch): every
+            // per-wave column partial in l_red receives exactly one contribution,
+            // which the row passes then store (cs + 0.f, the bits of 0.f + cs)
+            // instead of zero-fill + load-add-store.  Workgroup-uniform.
+            const bool single = AGX_LEARN_STORE1 && kk * SB < bsz && kk * SB + g.K * SB >= bsz;
+            if (!single)
+                for (int i = tid; i < pl.l_stat - pl.l_red; i += kNT) sm[pl.l_red + i] = 0.f;
             float lsum = 0.f, klsum = 0.f;
             // this update's gradient slabs (double-buffered by update parity)
             const int upd = e * nmb + mb;
@@ -966,10 +1010,48 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                 if (local) emit_tiles(gc, put_l);
                 else emit_tiles(gc, put_w);
             };
+            // LN / bias vectors of layer L (pl.ne: the head) -> put(LDS-image offset,
+            // value): fixed-order sums of the per-wave partials
+            auto vdump = [&](auto Lc, auto put) {
+                constexpr int L = decltype(Lc)::value;
+                constexpr int F = L < pl.ne ? pl.eout[L < pl.ne ? L : 0] : pl.H;
+                constexpr int nv = (L < pl.ne && !pl.eaff[L < pl.ne ? L : 0]) ? 1 : 3;
+                constexpr int red = L < pl.ne ? pl.red_e[L < pl.ne ? L : 0] : pl.red_h;
+                const int tid = vtid();
+                // compile-time rounds; all kNW partial loads issued before the
+                // fixed-order sum (a load-add chain waited on every LDS round trip)
+#pragma unroll
+                for (int rnd = 0; rnd < (nv * F + kNT - 1) / kNT; ++rnd) {
+                    const int idx = tid + rnd * kNT;
+                    if (idx >= nv * F) break;
+                    const int k = idx / F, j = idx % F;
+                    float pv[kNW];
+#pragma unroll
+                    for (int w = 0; w < kNW; ++w) pv[w] = sm[pl.l_red + red + (k * kNW + w) * F + j];
+                    float x = 0.f;
+#pragma unroll
+                    for (int w = 0; w < kNW; ++w) x += pv[w];
+                    int l;
+                    if constexpr (L < pl.ne) {
+                        l = (k == 0 ? pl.l_eb[L < pl.ne ? L : 0] : (k == 1 ? pl.l_eg[L < pl.ne ? L : 0] : pl.l_ebe[L < pl.ne ? L : 0])) + j;
+                    } else {
+                        l = (k == 0 ? pl.l_hb : (k == 1 ? pl.l_hg : pl.l_hbe)) + j;
+                    }
+                    put(l, x);
+                }
+            };
+            // ... -> the slab, as soon as the layer's partials are final (partners,
+            // last sub-batch: the stores then fly under the rest of the backward
+            // pass instead of being the freshest ones at the first barrier's drain)
+            auto vdump_slab = [&](auto Lc) {
+                if (local) vdump(Lc, put_l);
+                else vdump(Lc, put_w);
+            };
             // this agent's summed-gradient slab (written by the reduce-scatter)
             const auto sum_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                 g.K > 1 ? to_sgpr(sum_p + (size_t)(upd & 1) * pl.slab) : nullptr, 0,
                 __builtin_amdgcn_readfirstlane(pl.slab * 4), 0x00020000);
+            (void)sum_rsrc;  // AGX_LEARN_B2_TAGGED: the tagged words replace the sum slab
             // Partner barrier (MI355X_MICROARCH visibility rules): every wave drains its
             // write-through (sc1) stores (vmcnt) -> workgroup barrier -> one relaxed
             // agent-scope ticket; relaxed poll with s_sleep -> barrier -> readers use
@@ -1008,6 +1090,8 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
             // group is final (last sub-batch), overlapping the stores with the rest of
             // the backward pass
             const bool direct = g.K > 1;
+            // ... and each layer's bias / LN-affine gradients likewise (vdump_slab)
+            const bool vec_early = AGX_LEARN_VEC_EARLY && direct;
 
             for (int sb = kk * SB; sb < bsz; sb += g.K * SB) {
                 const bool last_sb = sb + g.K * SB >= bsz;
@@ -1247,18 +1331,26 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                                     float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, cs[k][i])));
                     }
                     if (lane < W) {
+                        if (single) {  // the slot's only contribution (see `single`)
 #pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            float o[NC];
+                            for (int k = 0; k < 3; ++k)
 #pragma unroll
-                            for (int i = 0; i < NC; ++i) o[i] = rd[(k * kNW + wave) * F + sub + W * i];
+                                for (int i = 0; i < NC; ++i) rd[(k * kNW + wave) * F + sub + W * i] = cs[k][i] + 0.f;
+                        } else {
 #pragma unroll
-                            for (int i = 0; i < NC; ++i) rd[(k * kNW + wave) * F + sub + W * i] = o[i] + cs[k][i];
+                            for (int k = 0; k < 3; ++k) {
+                                float o[NC];
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) o[i] = rd[(k * kNW + wave) * F + sub + W * i];
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) rd[(k * kNW + wave) * F + sub + W * i] = o[i] + cs[k][i];
+                            }
                         }
                     }
                 }
                 __syncthreads();
                 AGX_STAMP(stb + 3);
+                if (vec_early && last_sb) vdump_slab(IC(pl.ne));  // the head's vectors are final
 
                 // backward row pass through LN(+affine)+ReLU of an encoder layer:
                 // dY (dyb, stride ldy) -> dZ (S2)
@@ -1330,13 +1422,20 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                                     float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, cs[k][i])));
                     }
                     if (lane < W) {
+                        if (single) {  // the slot's only contribution (see `single`)
 #pragma unroll
-                        for (int k = 0; k < NV; ++k) {
-                            float o[NC];
+                            for (int k = 0; k < NV; ++k)
 #pragma unroll
-                            for (int i = 0; i < NC; ++i) o[i] = rd[(k * kNW + wave) * F + sub + W * i];
+                                for (int i = 0; i < NC; ++i) rd[(k * kNW + wave) * F + sub + W * i] = cs[k][i] + 0.f;
+                        } else {
 #pragma unroll
-                            for (int i = 0; i < NC; ++i) rd[(k * kNW + wave) * F + sub + W * i] = o[i] + cs[k][i];
+                            for (int k = 0; k < NV; ++k) {
+                                float o[NC];
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) o[i] = rd[(k * kNW + wave) * F + sub + W * i];
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) rd[(k * kNW + wave) * F + sub + W * i] = o[i] + cs[k][i];
+                            }
                         }
                     }
                 };
@@ -1418,6 +1517,7 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                     ln_bwd(IC(fout), IC(dyb), IC(ldy), IC(pl.l_xe[L]), IC(pl.ld_xe[L]), IC(pl.l_re[L]), IC(pl.l_eg[L]),
                            IC(pl.l_ebe[L]), IC(pl.red_e[L]), BC(pl.eaff[L] != 0));
                     __syncthreads();
+                    if (vec_early && last_sb) vdump_slab(Lc);  // this layer's vectors are final
                     constexpr bool in_aff = L > 0 && pl.eaff[L > 0 ? L - 1 : 0];
                     constexpr int xb = L == 0 ? pl.l_x0 : pl.l_xe[L > 0 ? L - 1 : 0];
                     constexpr int ldx = L == 0 ? pl.ld_x0 : pl.ld_xe[L > 0 ? L - 1 : 0];
@@ -1482,44 +1582,19 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                 emit_slab(IC(pl.ne + 1));
                 emit_slab(IC(pl.ne + 2));
             }
-            // LN / bias vectors: fixed-order sums of the per-wave partials
-            auto vdump = [&](auto Lc, auto put) {
-                constexpr int L = decltype(Lc)::value;
-                constexpr int F = L < pl.ne ? pl.eout[L < pl.ne ? L : 0] : pl.H;
-                constexpr int nv = (L < pl.ne && !pl.eaff[L < pl.ne ? L : 0]) ? 1 : 3;
-                constexpr int red = L < pl.ne ? pl.red_e[L < pl.ne ? L : 0] : pl.red_h;
-                const int tid = vtid();
-                // compile-time rounds; all kNW partial loads issued before the
-                // fixed-order sum (a load-add chain waited on every LDS round trip)
-#pragma unroll
-                for (int rnd = 0; rnd < (nv * F + kNT - 1) / kNT; ++rnd) {
-                    const int idx = tid + rnd * kNT;
-                    if (idx >= nv * F) break;
-                    const int k = idx / F, j = idx % F;
-                    float pv[kNW];
-#pragma unroll
-                    for (int w = 0; w < kNW; ++w) pv[w] = sm[pl.l_red + red + (k * kNW + w) * F + j];
-                    float x = 0.f;
-#pragma unroll
-                    for (int w = 0; w < kNW; ++w) x += pv[w];
-                    int l;
-                    if constexpr (L < pl.ne) {
-                        l = (k == 0 ? pl.l_eb[L < pl.ne ? L : 0] : (k == 1 ? pl.l_eg[L < pl.ne ? L : 0] : pl.l_ebe[L < pl.ne ? L : 0])) + j;
-                    } else {
-                        l = (k == 0 ? pl.l_hb : (k == 1 ? pl.l_hg : pl.l_hbe)) + j;
-                    }
-                    put(l, x);
-                }
-            };
             auto vdump_all = [&](auto put) {
                 vdump(IC(0), put);
                 vdump(IC(1), put);
                 if constexpr (pl.ne == 3) vdump(IC(2), put);
                 vdump(IC(pl.ne), put);
             };
+            // partners with a last sub-batch published every layer's vectors from
+            // the backward pass; the others (K == 1, no sub-batch this update) here
             if (!direct) vdump_all(gput);
-            else if (local) vdump_all(put_l);
-            else vdump_all(put_w);
+            else if (!vec_early || kk * SB >= bsz) {
+                if (local) vdump_all(put_l);
+                else vdump_all(put_w);
+            }
             AGX_STAMP(64 + 9);
             __syncthreads();
             float lmb = lsum, klmb = klsum;
@@ -1540,11 +1615,58 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                     slab_put(pl.param_end + 1, klmb);
                 }
                 if (!partner_sync(ctr1, (unsigned)(g.K * (upd + 1)), 64 + 11, 64 + 12)) return;
+#if AGX_LEARN_B2_TAGGED
+                // Second hand-off (≈2 KB per agent): the data is the flag
+                // (cdna_hip_programming.md §6 G16 R2).  Every word is ONE aligned
+                // 8-byte {tag = upd + 1, value bits} relaxed atomic store by the lane
+                // that computed it — no drain, no ticket, no workgroup barrier on
+                // the producer side — and the consumers sweep the words until every
+                // tag matches.  Tags count updates within the launch and are never
+                // 0; the gather prologue zeroes the words on every launch.
+                // Reuse: the words are double-buffered by update parity, which is
+                // more than the protocol needs.  A word of parity u & 1 is stored
+                // again in update u + 2, after that update's first barrier; a
+                // partner arrives at the first barrier of update u + 1 only after
+                // its waves left the sweep of update u, so no sweep of update u can
+                // still be waiting when a word's tag moves on.  The barrier this
+                // replaces also ordered nothing else: before the third barrier a
+                // partner overwrites (with updated parameters) only its own chunk
+                // region of its own slab, which only that partner read in the
+                // reduce-scatter, and its loads had returned (their sums are the
+                // Adam inputs); the first and third barriers stay full barriers
+                // and keep the slabs' parity reuse as it was.
+                gu64 *const b2w = (gu64 *)(b2_p + (size_t)(upd & 1) * kB2Words);
+                const unsigned long long b2tag = (unsigned long long)(unsigned)(upd + 1) << 32;
+                // one word: a single aligned 8-byte store.  Partners on one XCD (see
+                // `local`) store it at workgroup scope (sc0: through this CU's L1, the
+                // line stays in their L2, where the sweep's L1-bypassing loads find
+                // it, like the slabs' plain stores); otherwise at agent scope (sc1,
+                // write-through).  An sc1 store drops the line from L2 and every
+                // sweep pass then pays the fabric round trip: with sc1 stores on
+                // one XCD the hand-off was slower than the barrier it replaces
+                // (1.13 against 1.06 ms per learn()).
+                auto b2_store = [&](gu64 *w, unsigned v) {
+                    if (local) __hip_atomic_store(w, b2tag | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    else __hip_atomic_store(w, b2tag | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                };
+                auto put_loss = [&](f4 t) {
+                    // (copies: __builtin_bit_cast of a vector-element lvalue reads element 0)
+                    const float lw = t[0], kw = t[1];
+                    b2_store(b2w + 2 * kNW * kMaxK, __builtin_bit_cast(unsigned, lw));
+                    b2_store(b2w + 2 * kNW * kMaxK + 1, __builtin_bit_cast(unsigned, kw));
+                };
+#else
+                auto put_loss = [&](f4 t) {
+                    // the loss / approx_kl chunk of the sum slab: every partner reads it
+                    if (local) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), sum_rsrc, n4 * 16, 0, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), sum_rsrc, n4 * 16, 0, 16);
+                };
+#endif
                 // ---- reduce-scatter: partner kk sums its own float4 chunks [oc0, oc1)
                 // of the parameter image (+ the chunk holding the loss / approx_kl
                 // words) over the K slabs in partner order; the sums stay in its
-                // registers (it alone runs Adam on them), only the loss chunk and the
-                // per-wave partial gradient norms go to the agent's sum slab
+                // registers (it alone runs Adam on them), only the loss words and the
+                // per-wave partial gradient norms go to the second hand-off
                 {
                     const int tid = vtid();
                     // one buffer descriptor over the K consecutive slabs
@@ -1579,10 +1701,7 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                             __syncthreads();
                             if (!h) {
                                 t += xch[tid];
-                                if (c == n4) {  // the loss / approx_kl chunk: every partner reads it
-                                    if (local) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), sum_rsrc, c * 16, 0, 0);
-                                    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), sum_rsrc, c * 16, 0, 16);
-                                }
+                                if (c == n4) put_loss(t);  // the loss / approx_kl chunk: every partner reads it
                             }
 #pragma unroll
                             for (int cc = 0; cc < 4; ++cc) gr[cc] = (!h && c < pc1) ? t[cc] : 0.f;
@@ -1611,10 +1730,7 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
 #pragma unroll
                             for (int q = 1; q < KM; ++q)
                                 if (q < g.K) t += x[q];
-                            if (c == n4) {  // the loss / approx_kl chunk: every partner reads it
-                                if (local) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), sum_rsrc, c * 16, 0, 0);
-                                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), sum_rsrc, c * 16, 0, 16);
-                            }
+                            if (c == n4) put_loss(t);  // the loss / approx_kl chunk: every partner reads it
                         }
 #pragma unroll
                         for (int cc = 0; cc < 4; ++cc) gr[4 * j + cc] = c < pc1 ? t[cc] : 0.f;
@@ -1635,13 +1751,104 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                     const float r0 = row_sum(n0), r1 = row_sum(n1);
                     const float w0 = readlane_f(r0, 0) + readlane_f(r0, 16) + readlane_f(r0, 32) + readlane_f(r0, 48);
                     const float w1 = readlane_f(r1, 0) + readlane_f(r1, 16) + readlane_f(r1, 32) + readlane_f(r1, 48);
+#if AGX_LEARN_B2_TAGGED
+                    AGX_STAMP(64 + 13);
+                    if (lane < 2)  // word [partner][wave][group]
+                        b2_store(b2w + (kk * kNW + wave) * 2 + lane, __builtin_bit_cast(unsigned, lane ? w1 : w0));
+                    AGX_STAMP(64 + 8);  // words stored
+#else
                     if (lane < 2) {
                         const float w = lane ? w1 : w0;
                         const int o = (pl.param_end + 4 + (kk * kNW + wave) * 2 + lane) * 4;
                         if (local) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, w), sum_rsrc, o, 0, 0);
                         else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, w), sum_rsrc, o, 0, 16);
                     }
+#endif
                 }
+#if AGX_LEARN_B2_TAGGED
+                // Sweep: the sweeping wave reloads every word on every pass (relaxed
+                // agent-scope 8-byte loads, global address space: they bypass this
+                // CU's L1) until every tag equals upd + 1; every wave then reduces in
+                // the fixed order below.  The area always holds kMaxK partners'
+                // words; words past this split's are never stored and are masked.
+                // Lane l holds words l + 64 q ([partner][wave][group]) and loss word
+                // l & 1.
+                // Who sweeps: wave 0 alone, which hands the words to the other seven
+                // through LDS behind one workgroup barrier (AGX_LEARN_B2_SWEEP1 = 1,
+                // default), or every wave for itself (0).  Eight sweeping waves per
+                // workgroup cost more than the barrier (1.08 against 1.06 ms per
+                // learn(): 128 workgroups x 8 waves polling the same few lines).
+                // Liveness: the spin is bounded like the barriers'; on time-out the
+                // time-out word and AGX_LEARN_ERR_TIMEOUT are set.  One sweeping
+                // wave: it reports through LDS and the whole workgroup returns
+                // behind the barrier, as at the full barriers, so no wave is left at
+                // a later __syncthreads.  Eight sweeping waves: a wave that gives up
+                // ends; every wave waits for the same words, and a word that has its
+                // tag keeps it until this workgroup itself has arrived at a later
+                // first barrier, so normally all eight give up together; should one
+                // see the last word just after another gave up, it is still not
+                // left waiting, because a workgroup barrier counts only the waves
+                // that have not ended, every later wait is a bounded spin as well,
+                // and the sticky error word makes the host discard the learn.
+                {
+                    const int lane = vlane();
+                    const int np = 2 * kNW * g.K;  // <= 256
+                    const unsigned tag = (unsigned)(upd + 1);
+                    unsigned lo[NQ], ll = 0u;
+#if AGX_LEARN_B2_SWEEP1
+                    // one sweeping wave + an LDS hand-over to the other seven
+                    unsigned *b2x = reinterpret_cast<unsigned *>(sm + pl.l_b2x);
+                    bool swept = true;
+                    if (swave() == 0) {
+#endif
+                    for (unsigned spins = 0;;) {
+                        unsigned long long x[NQ];
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q)
+                            x[q] = __hip_atomic_load(b2w + 64 * q + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const unsigned long long xl =
+                            __hip_atomic_load(b2w + 2 * kNW * kMaxK + (lane & 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        unsigned bad = (unsigned)(xl >> 32) ^ tag;  // branch-free: any tag bit off
+                        ll = (unsigned)xl;
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q) {
+                            bad |= lane + 64 * q < np ? (unsigned)(x[q] >> 32) ^ tag : 0u;
+                            lo[q] = (unsigned)x[q];
+                        }
+                        if (__all(bad == 0u)) break;
+                        __builtin_amdgcn_s_sleep(1);
+                        if (++spins > kSpinMax) {  // wave-uniform
+                            __hip_atomic_store(tmo_v, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (err_v) __hip_atomic_fetch_or(err_v, AGX_LEARN_ERR_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if AGX_LEARN_B2_SWEEP1
+                            swept = false;
+                            break;
+#else
+                            return;
+#endif
+                        }
+                    }
+#if AGX_LEARN_B2_SWEEP1
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q) b2x[lane + 64 * q] = lo[q];
+                        if (lane < 2) b2x[2 * kNW * kMaxK + lane] = ll;
+                        if (lane == 0) stat[4 * kNW] = swept ? 1.f : 0.f;
+                    }
+                    __syncthreads();
+                    if (stat[4 * kNW] == 0.f) return;  // the whole workgroup takes the time-out exit
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) lo[q] = b2x[lane + 64 * q];
+                    ll = b2x[2 * kNW * kMaxK + (lane & 1)];
+#endif
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) vq[q] = lane + 64 * q < np ? __builtin_bit_cast(float, lo[q]) : 0.f;
+                    // the minibatch loss and approx_kl: partner-order sums of the K words
+                    // (uniform: the early-stop branch depends on it)
+                    lmb = __builtin_bit_cast(float, __builtin_amdgcn_readlane(ll, 0));
+                    klmb = __builtin_bit_cast(float, __builtin_amdgcn_readlane(ll, 1));
+                }
+                AGX_STAMP(64 + 15);  // sweep matched
+#else
                 AGX_STAMP(64 + 13);
                 if (!partner_sync(ctr2, (unsigned)(g.K * (upd + 1)), 64 + 8, 64 + 15)) return;
                 // ONE round trip for everything the second barrier published: the
@@ -1664,6 +1871,7 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
                 const unsigned kw = __builtin_amdgcn_raw_buffer_load_b32(sum_rsrc, (pl.param_end + 1) * 4, 0, 16);
                 lmb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(lw));
                 klmb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(kw));
+#endif
             }
 
             // ---- P10: two-group norm, Adam from registers -------------------------
@@ -1889,9 +2097,11 @@ __global__ void ppo_gather_kernel(const float *__restrict__ obs, const long long
     const int p = ep % P;
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     // the learner's arrival counters + timeout word (stream-ordered before it;
-    // replaces a separate memset launch)
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int i = threadIdx.x; i < ncounters; i += blockDim.x) counters[i] = 0u;
+    // replaces a separate memset launch) and its tagged hand-off words, spread
+    // over the blocks of the first (epoch, agent) row
+    if (blockIdx.y == 0)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncounters; i += gridDim.x * blockDim.x)
+            counters[i] = 0u;
     if (j >= S) return;
     // epochs beyond an agent's own update_epochs: the learner never reads
     // them, and their perms rows are not part of the contract (agx.h)
@@ -2245,7 +2455,9 @@ static LearnWs learn_ws(const LearnPlan &pl, int64_t P, int64_t S, int64_t epoch
     const size_t per = (size_t)epochs * P * S;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     w.cnt = 0;
-    w.gobs = up(((size_t)(4 + kMaxK) * P + 1) * 4);  // barrier counters, timeout word, XCC ids
+    // barrier counters, timeout word, XCC ids, then the tagged hand-off words:
+    // one block, zeroed by the gather prologue on every launch
+    w.gobs = up(b2_words_off((size_t)P) * 4 + (AGX_LEARN_B2_TAGGED ? (size_t)P * 2 * kB2Words * 8 : 0));
     w.gact = w.gobs + up(per * pl.D * 4);
     w.gmask = w.gact + up(per * 4);
     w.grow = w.gmask + up(per * 4);

@@ -4,8 +4,11 @@ Slots (learner.hip AGX_STAMP): sub-batch k of agent 0's first minibatch at
 k*16 + {0 start, 4 sub-batch committed to LDS, 5 next prefetch issued,
 1 barrier passed, 2 forward trunk, 3 head row pass (LN fwd + output layers +
 loss + LN bwd), 6 output-layer + head dW / dX, 7 encoder bwd}; 64+9 gradients dumped, 64+10 Adam done;
-partners: 64+11/12 first barrier ticket/passed, 64+13 reduce-scatter done,
-64+8/15 second barrier ticket/passed, 64+14 norm done."""
+partners: 64+11/12 first barrier ticket/passed, 64+3 reduce-scatter loads
+summed, 64+13 partial norms done, 64+8 tagged hand-off words stored, 64+15 sweep
+matched (every tag seen), 64+14 norm done (with AGX_LEARN_B2_TAGGED=0: 64+8/15
+second barrier ticket/passed); with partners the per-layer vector gradients
+leave during the backward pass, so "dump" is what is left at the end."""
 import os
 import sys
 import time
@@ -57,8 +60,8 @@ last = max(v for v in st[:64] if v)
 if st[64 + 1]:  # partners: reduce-scatter + distributed Adam (three barriers)
     print("dump", st[64 + 9] - last, "| publish", st[64 + 11] - st[64 + 9], "wait", st[64 + 12] - st[64 + 11],
           "| RS loads+sum", st[64 + 3] - st[64 + 12], "norm partials", st[64 + 13] - st[64 + 3],
-          "| B2 drain + ticket", st[64 + 8] - st[64 + 13], "wait", st[64 + 15] - st[64 + 8],
-          "| norm read", st[64 + 14] - st[64 + 15], "adam + publish + B3 drain/ticket", st[64 + 0] - st[64 + 14],
+          "| B2 words stored", st[64 + 8] - st[64 + 13], "sweep matched", st[64 + 15] - st[64 + 8],
+          "| norm sum", st[64 + 14] - st[64 + 15], "adam + publish + B3 drain/ticket", st[64 + 0] - st[64 + 14],
           "B3 wait", st[64 + 1] - st[64 + 0], "param read", st[64 + 2] - st[64 + 1],
           "sync", st[64 + 10] - st[64 + 2], "| minibatch total cycles", st[64 + 10] - st[0])
 elif st[64 + 15]:  # partners: reduce-scatter exchange (two barriers)
