@@ -23,7 +23,13 @@ _F = ctypes.c_float
 _INT = ctypes.c_int
 _SZ = ctypes.c_size_t
 
-# name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h) one-to-one
+
+class AgxMultiHead(ctypes.Structure):
+    """agx_multi_head (include/agx_multi.h): a MultiDiscrete space's nvec, passed by value."""
+    _fields_ = [("K", ctypes.c_int32), ("nvec", ctypes.c_int32 * 32)]
+
+
+# name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -63,6 +69,11 @@ SIGNATURES = {
     "agx_ppo_gauss_graph_check": (_INT, [_P, _I]),
     "agx_ppo_learn_gauss_graph_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I, _I]),
     "agx_ppo_learn_gauss_graph": (_INT, [_P, _I, _P, _P, _P]),
+    # include/agx_multi.h: PPO for MultiDiscrete actions
+    "agx_ppo_act_multi_graph_workspace_bytes": (_SZ, [_P, _I, _I]),
+    "agx_ppo_act_multi_graph": (_INT, [_P, AgxMultiHead, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64,
+                                       ctypes.c_uint64, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "agx_ppo_multi_loss_fwd_bwd": (_INT, [_P, _P, AgxMultiHead] + [_P] * 7 + [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
     "agx_ppo_learn": (_INT, [_P, _P, _P, _P]),
     "agx_ppo_act": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                            _I, _P, _P, _P]),

@@ -9,7 +9,8 @@ tensors, numbers, strings, lists and dicts), so it is written by
 ``torch.save`` and read back with ``torch.load(weights_only=True)`` — nothing
 in a checkpoint is executed on load.  Spaces are stored as
 ``{"obs_shape", "n_actions"}`` (a Box action space: ``{"obs_shape",
-"action_low", "action_high"}``, its bounds as flat lists) for ``load``.
+"action_low", "action_high"}``, its bounds as flat lists; a MultiDiscrete
+one: ``{"obs_shape", "nvec"}``) for ``load``.
 
 Checkpoints the reference itself wrote (dill-pickled agents, spaces and
 registries) are read by ``refckpt.read_reference`` — the same weights-only
@@ -49,7 +50,9 @@ def checkpoint_dict(agent, modules: dict[str, dict[str, torch.Tensor]], optimize
     out["agilerl_version"] = "agx"
     if spaces:
         out["spaces"] = {"obs_shape": list(agent.observation_space.shape)}
-        if hasattr(agent.action_space, "n"):
+        if hasattr(agent.action_space, "nvec"):  # MultiDiscrete actions (1-D)
+            out["spaces"]["nvec"] = [int(n) for n in agent.action_space.nvec]
+        elif hasattr(agent.action_space, "n"):
             out["spaces"]["n_actions"] = int(agent.action_space.n)
         else:  # Box actions (1-D)
             out["spaces"]["action_low"] = [float(x) for x in agent.action_space.low]
@@ -94,10 +97,12 @@ def restore_attributes(agent, ckpt: dict) -> None:
 
 
 def spaces(ckpt: dict):
-    from ..envs import Box, Discrete
+    from ..envs import Box, Discrete, MultiDiscrete
 
     s = ckpt["spaces"]
     obs = Box(-float("inf"), float("inf"), tuple(s["obs_shape"]))
+    if "nvec" in s:
+        return obs, MultiDiscrete(s["nvec"])
     if "n_actions" not in s:
         act = Box(0.0, 0.0, (len(s["action_low"]),))
         act.low[:], act.high[:] = s["action_low"], s["action_high"]

@@ -1,5 +1,5 @@
 """Drop-in ``PPO`` (agilerl/algorithms/ppo.py:108-1290) for MLP actor-critics
-over Discrete or Box action spaces, backed by the HBM population engine.
+over Discrete, MultiDiscrete or Box action spaces, backed by the HBM population engine.
 
 A ``PPO`` object is a *view* of one row of a :class:`PPOPopulation` (its
 parameters, Adam state and rollout SoA live in HBM, stacked with the other
@@ -10,7 +10,10 @@ population of one.
 
 Supported: Discrete action spaces (and 1-D Box action spaces of up to 32
 dimensions with vector observations: a diagonal Gaussian with a learned
-``log_std`` started at ``action_std_init``), Box observations, ``net_config`` with
+``log_std`` started at ``action_std_init``; and 1-D MultiDiscrete action
+spaces of up to 32 logits in all with vector observations: one categorical
+per component, int64 actions [.., K], flat legal-action masks [.., sum(nvec)]),
+Box observations, ``net_config`` with
 ``encoder_config`` / ``head_config`` MLP ``hidden_size`` lists and
 ``latent_dim`` (the reference's defaults: encoder [64, 64] -> latent 32,
 actor head [32], critic head [16] unless ``head_config`` is given,
@@ -105,11 +108,30 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
     8 / 128 (networks/base.py:191-194); no head_config -> actor head
     MlpNetConfig [32] (networks/actors.py:300-303), critic head [16]
     (ppo.py:292-300)."""
-    box = _box_action_space(action_space)
-    if not hasattr(action_space, "n") and not box:
-        raise NotImplementedError("agx PPO supports Discrete and Box action spaces")
+    if type(action_space).__name__ == "MultiBinary":
+        raise NotImplementedError("agx PPO: MultiBinary action spaces are not supported")
+    multi = hasattr(action_space, "nvec")
+    box = not multi and _box_action_space(action_space)
+    if not hasattr(action_space, "n") and not box and not multi:
+        raise NotImplementedError("agx PPO supports Discrete, MultiDiscrete and Box action spaces")
     net_config = dict(net_config or {})
     from ..networks.base import is_image_space
+
+    nvec = None
+    if multi:
+        # StochasticActor over a MultiDiscrete space (networks/actors.py:268): sum(nvec) logits
+        nv = np.asarray(action_space.nvec)
+        if nv.ndim != 1 or nv.size < 1:
+            raise NotImplementedError(f"agx PPO: MultiDiscrete action spaces are 1-D (got nvec of shape "
+                                      f"{tuple(nv.shape)})")
+        nvec = tuple(int(x) for x in nv)
+        if min(nvec) < 1:
+            raise ValueError(f"MultiDiscrete nvec must be positive (got {nvec})")
+        if sum(nvec) > 32:
+            raise NotImplementedError(f"agx PPO: MultiDiscrete actions of at most 32 logits in all (got "
+                                      f"sum(nvec) = {sum(nvec)})")
+        if is_image_space(observation_space):
+            raise NotImplementedError("agx PPO: MultiDiscrete action spaces with image observations")
 
     if box:
         # StochasticActor over a Box space (networks/actors.py:296-336): the head's
@@ -151,6 +173,10 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
         return GaussianActorCriticSpec(n_actions=A, action_std_init=float(action_std_init),
                                        action_low=tuple(float(x) for x in low),
                                        action_high=tuple(float(x) for x in high), **kw)
+    if multi:
+        from ..population.nets import MultiDiscreteActorCriticSpec
+
+        return MultiDiscreteActorCriticSpec(n_actions=sum(nvec), nvec=nvec, **kw)
     return ActorCriticSpec(n_actions=int(action_space.n), **kw)
 
 
@@ -443,6 +469,8 @@ class PPO:
             mask = (mask != 0).to(torch.uint8).contiguous()
         if pop.gaussian:
             return self._get_action_gauss(o, action_mask)
+        if pop.multidiscrete:
+            return self._get_action_multi(o, mask)
         out = dict(actions=torch.empty(n, dtype=torch.int64, device=self.device),
                    log_probs=torch.empty(n, device=self.device), values=torch.empty(n, device=self.device),
                    entropy=torch.empty(n, device=self.device))
@@ -507,6 +535,27 @@ class PPO:
         a = env_copy if env_copy is not None else actions
         return tuple(t.cpu().numpy() for t in (a, logp, ent, value))
 
+    def _get_action_multi(self, o: torch.Tensor, mask):
+        """get_action of a MultiDiscrete policy: one agx_ppo_act_multi_graph
+        launch on this agent's row -> int64 actions [n, K]; ``mask``: the flat
+        uint8 mask [n, L] or None."""
+        from ..kernels import ppo_act_multi_graph
+
+        pop = self.population
+        n, K = o.shape[0], len(pop.spec.nvec)
+        gdesc = pop.multi_descriptor()
+        self._counter += 1
+        ws = getattr(self, "_act_graph_ws", None)
+        if ws is None or ws[0] is not gdesc or ws[1] < n:
+            nbytes = _lib.load().agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(gdesc), 1, n)
+            ws = self._act_graph_ws = (gdesc, n, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
+        actions = torch.empty(n, K, dtype=torch.int64, device=self.device)
+        logp, value, ent = (torch.empty(n, device=self.device) for _ in range(3))
+        ppo_act_multi_graph(gdesc, pop.multi_head(), 1, n, pop.params.data[self.row], o, 0, ws[2], sample=True,
+                            seed=pop.act_seed + 7919 * pop.agent_ids[self.row], counter=(1 << 40) + self._counter,
+                            mask=mask, actions=actions, log_probs=logp, values=value, entropy=ent)
+        return tuple(t.cpu().numpy() for t in (actions, logp, ent, value))
+
     @property
     def rollout_buffer(self) -> "AgentRolloutBuffer":
         """The reference's ``agent.rollout_buffer`` (RolloutBuffer API: reset /
@@ -543,7 +592,7 @@ class PPO:
         and Adam (agx_clip_adam on this agent's row); target_kl checked after
         each epoch on the last minibatch's approx_kl.  -> mean_loss /
         (num_samples * update_epochs)."""
-        from ..population.nets import categorical, gaussian
+        from ..population.nets import categorical, gaussian, multi_categorical
 
         if not experiences:
             raise ValueError("Experiences must be provided when use_rollout_buffer is False")
@@ -581,7 +630,9 @@ class PPO:
                 adv[t] = last = delta + self.gamma * self.gae_lambda * nnt * last
             returns = adv + values
         obs_f = obs.reshape(-1, spec.obs_dim)
-        act_f = actions.reshape(-1, spec.n_actions) if gauss else actions.reshape(-1)
+        multi = pop.multidiscrete  # int64 actions [.., K]
+        act_f = (actions.reshape(-1, spec.n_actions) if gauss else actions.reshape(-1, len(spec.nvec)) if multi
+                 else actions.reshape(-1))
         lp_f, adv_f = log_probs.reshape(-1), adv.reshape(-1)
         ret_f, val_f = returns.reshape(-1), values.reshape(-1)
         n = obs_f.shape[0]
@@ -602,6 +653,8 @@ class PPO:
                 logits, value = spec.forward(w, obs_f[sel].unsqueeze(0))
                 if gauss:
                     logp, entropy = gaussian(logits[0], spec.log_std_view(w), act_f[sel])
+                elif multi:
+                    logp, entropy = multi_categorical(logits[0], spec.nvec, act_f[sel])
                 else:
                     logp_all, entropy = categorical(logits[0])
                     logp = logp_all.gather(-1, act_f[sel].unsqueeze(-1)).squeeze(-1)
@@ -699,6 +752,9 @@ class AgentRolloutBuffer:
                   else done.to(torch.uint8))
         self._put(p.values[self.row, t], value)
         self._put(p.log_probs[self.row, t], log_prob)
+        mask = _kw.get("action_mask")
+        if mask is not None and p.multidiscrete and p.action_masks is not None:  # the flat mask [N, L]
+            self._put(p.action_masks[self.row, t], np.asarray(mask) != 0)
         self.pos += 1
         self.full = self.pos == self.capacity
 

@@ -151,6 +151,11 @@ def _space_shapes(ck: dict) -> dict | None:
     n = act.attr("n")
     if shape is None:
         return None
+    nvec = act.attr("nvec")
+    if nvec is not None:  # a MultiDiscrete action space (1-D)
+        if np.ndim(nvec) != 1:
+            return None
+        return {"obs_shape": [int(s) for s in shape], "nvec": [int(x) for x in nvec]}
     if n is None:  # a Box action space: its bounds
         low, high = act.attr("low"), act.attr("high")
         if low is None or high is None or np.ndim(low) != 1:

@@ -37,6 +37,19 @@ class Box:
         return np.random.uniform(self.low, self.high).astype(self.dtype)
 
 
+class MultiDiscrete:
+    """One categorical per component: ``nvec[k]`` choices for component k
+    (gymnasium's ``spaces.MultiDiscrete``, 1-D)."""
+
+    def __init__(self, nvec):
+        self.nvec = np.asarray(nvec, dtype=np.int64)
+        self.shape = tuple(self.nvec.shape)
+        self.dtype = np.int64
+
+    def sample(self):
+        return (np.random.random_sample(self.nvec.shape) * self.nvec).astype(self.dtype)
+
+
 class Dict:
     """Mapping of named spaces; a plain dict is key-sorted like gymnasium's
     ``spaces.Dict``."""
@@ -71,18 +84,22 @@ class SyntheticVecEnv:
     ``max_episode_steps`` truncates episodes like gymnasium's TimeLimit
     (LunarLander: 1000); None never truncates (the bench's default).
     ``action_dim`` (None: the Discrete env) makes it a continuous-control
-    stand-in: actions are ``Box(action_low, action_high, (action_dim,))``."""
+    stand-in: actions are ``Box(action_low, action_high, (action_dim,))``.
+    ``nvec`` (None: today's env) makes it a factored-control stand-in: actions
+    are ``MultiDiscrete(nvec)``, one row [K] per env."""
 
     #: the step never touches the GPU (PopulationRunner may pace a persistent rollout)
     agx_device_free = True
 
     def __init__(self, num_envs: int, obs_dim: int = 8, n_actions: int = 4, p_done: float = 1 / 200,
                  seed: int = 0, ring: int = 97, max_episode_steps: int | None = None, action_dim: int | None = None,
-                 action_low: float = -1.0, action_high: float = 1.0):
+                 action_low: float = -1.0, action_high: float = 1.0, nvec=None):
         self.num_envs = int(num_envs)
         self.single_observation_space = Box(-np.inf, np.inf, (obs_dim,))
-        self.single_action_space = Discrete(n_actions) if action_dim is None else \
-            Box(action_low, action_high, (int(action_dim),))
+        if nvec is not None and action_dim is not None:
+            raise ValueError("SyntheticVecEnv: nvec (MultiDiscrete) or action_dim (Box), not both")
+        self.single_action_space = MultiDiscrete(nvec) if nvec is not None else \
+            Discrete(n_actions) if action_dim is None else Box(action_low, action_high, (int(action_dim),))
         self.observation_space = self.single_observation_space
         self.action_space = self.single_action_space
         self._obs_dim, self._p_done, self._ring, self.seed = obs_dim, p_done, ring, seed

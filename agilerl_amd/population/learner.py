@@ -345,3 +345,33 @@ def policy_step_gauss(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_strid
               _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy), out_agent_stride,
               _lib.ptr(actions_flat), _lib.ptr(lo), _lib.ptr(hi), pop.env_base_d.data_ptr(), ws[1].data_ptr(),
               _lib.stream())
+
+
+def multi_act_workspace(pop, desc: AgxPPOGraph):
+    """(desc, scratch) of agx_ppo_act_multi_graph for this population, as
+    graph_act_workspace."""
+    ws = getattr(pop, "_act_ws", None)
+    if ws is None or ws[0] is not desc:
+        lib = _lib.load()
+        nbytes = lib.agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
+        if nbytes == 0:
+            raise _lib.AgxError(f"agx_ppo_act_multi_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+        ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
+    return ws
+
+
+def policy_step_multi(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
+                      counter: int, actions=None, log_probs=None, values=None, entropy=None,
+                      out_agent_stride: int = 0, actions_flat=None, action_mask=None,
+                      mask_agent_stride: int = 0) -> None:
+    """agx_ppo_act_multi_graph over all P agents x N envs: the policy step of a
+    MultiDiscrete population (one launch), the agents' own Philox streams;
+    int64 actions [.., K], a flat mask [.., L]."""
+    from ..kernels import ppo_act_multi_graph
+
+    ws = multi_act_workspace(pop, desc)
+    ppo_act_multi_graph(desc, pop.multi_head(), pop.P, pop.N, pop.params.data, obs, obs_agent_stride, ws[1],
+                        sample=sample, seed=pop.act_seed, counter=counter, mask=action_mask,
+                        mask_agent_stride=mask_agent_stride, actions=actions, log_probs=log_probs, values=values,
+                        entropy=entropy, out_agent_stride=out_agent_stride, actions_flat=actions_flat,
+                        agent_env_base=pop.env_base_d)

@@ -290,6 +290,74 @@ class GaussianActorCriticSpec(ActorCriticSpec):
         return d
 
 
+@dataclass
+class MultiDiscreteActorCriticSpec(ActorCriticSpec):
+    """The actor-critic of a MultiDiscrete action space (networks/actors.py:268
+    with networks/distributions.py:193-199): one categorical per component over
+    slices of the actor's L = sum(nvec) logits.  ``n_actions`` is L, so the
+    layer list, the parameter order and the initial draws are those of the
+    categorical spec with n = L; there are no extra parameters.  The categorical
+    kernels (agx_ppo_learn, agx_ppo_learn_graph, agx_ppo_act, the persistent
+    rollout and evaluation) never see this spec, K = 1 included: the policy
+    step is agx_ppo_act_multi_graph over ``multi_descriptor()``."""
+
+    nvec: tuple = ()
+
+    head = "multidiscrete"
+
+    def __post_init__(self) -> None:
+        self.nvec = tuple(int(n) for n in self.nvec)
+        if not self.nvec or min(self.nvec) < 1 or sum(self.nvec) != self.n_actions:
+            raise ValueError(f"nvec {self.nvec} must hold K >= 1 positive sizes that sum to n_actions "
+                             f"({self.n_actions})")
+        super().__post_init__()
+
+    @property
+    def n_components(self) -> int:
+        return len(self.nvec)
+
+    def shape_key(self) -> tuple:
+        return super().shape_key() + (self.head, self.nvec)
+
+    def multi_head(self):
+        """agx_multi_head (include/agx_multi.h) of nvec, passed by value."""
+        from ..kernels import multi_head
+
+        return multi_head(self.nvec)
+
+    def multi_descriptor(self):
+        """agx_ppo_graph of the networks for agx_ppo_act_multi_graph, or None
+        when the layer list is outside what the kernel takes."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+
+        d = layer_list(self)
+        lib = _lib.load(require_gpu=False)  # pure host-side validation
+        if d is None or lib.agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
+            return None
+        return d
+
+
+def multi_categorical(logits: torch.Tensor, nvec, action: torch.Tensor, mask: torch.Tensor | None = None):
+    """log-prob of ``action`` [..., K] and entropy of the K categoricals over
+    slices of ``logits`` [..., L] as ``agilerl/utils/torch_utils.py:284-333``
+    (illegal logits -> -1e8 first, distributions.py:16-28); both summed over
+    the components in ascending order.  -> (logp [...], entropy [...])."""
+    if mask is not None:
+        logits = torch.where(mask.bool(), logits, torch.full_like(logits, -1e8))
+    logp = ent = None
+    off = 0
+    for k, n in enumerate(nvec):
+        logp_all, h = categorical(logits[..., off:off + n])
+        lp = logp_all.gather(-1, action[..., k:k + 1]).squeeze(-1)
+        logp = lp if logp is None else logp + lp
+        ent = h if ent is None else ent + h
+        off += n
+    return logp, ent
+
+
 def categorical(logits: torch.Tensor):
     """log-softmax and entropy as ``agilerl/utils/torch_utils.py:142-199``:
     H = -sum p * log(p + 1e-8)."""

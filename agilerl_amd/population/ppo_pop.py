@@ -37,6 +37,12 @@ agx_ppo_learn_gauss_graph (the runtime-shape learner with a Gaussian head);
 with ``fused=False``, AGX_GAUSS_FUSED=0 or a layer list that learner does not
 take, on the autograd path with the fused Gaussian loss kernel
 (agx_ppo_gauss_loss_fwd_bwd).  The categorical kernels never see it.
+
+A MultiDiscrete spec (nets.MultiDiscreteActorCriticSpec) stores int64 actions
+(P, T, N, K) and flat masks (P, T, N, L), acts through agx_ppo_act_multi_graph
+and learns on the ``fused=False`` path with the fused multi-categorical loss
+kernel (agx_ppo_multi_loss_fwd_bwd); the categorical kernels never see it
+either, K = 1 included.
 """
 
 from __future__ import annotations
@@ -97,6 +103,30 @@ class _PPOGaussLossFn(torch.autograd.Function):
         return (g1.view(sm) * gl, g2.view(sv) * gl, g3.view(sl) * gl) + (None,) * 10
 
 
+class _PPOMultiLossFn(torch.autograd.Function):
+    """_PPOLossFn for a multi-categorical head (agx_ppo_multi_loss_fwd_bwd):
+    the masked per-component log-softmax, the log-prob of the stored actions
+    [rows, K], the entropy and the loss in one launch; ``logits`` are the raw
+    network output, and a masked logit gets gradient 0."""
+
+    @staticmethod
+    def forward(ctx, logits, value, head, actions, masks, old_logp, adv, ret, old_v, gidx, b, clip, vf, ent):
+        L = logits.shape[-1]
+        g1, g2, stats = K.ppo_multi_loss_fwd_bwd(
+            logits.contiguous().view(-1, L), value.contiguous().view(-1), head, actions, old_logp, adv, ret, old_v,
+            b, clip, vf, ent, index=gidx, mask=masks)
+        ctx.save_for_backward(g1, g2)
+        ctx.shapes = (logits.shape, value.shape)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum(), stats
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        g1, g2 = ctx.saved_tensors
+        sl, sv = ctx.shapes
+        return (g1.view(sl) * gl, g2.view(sv) * gl) + (None,) * 12
+
+
 class PPOPopulation:
     def __init__(self, spec: ActorCriticSpec, pop_size: int, num_envs: int, *, learn_step=2048,
                  batch_size=128, lr=1e-3, gamma=0.99, gae_lambda=0.95, clip_coef=0.2, ent_coef=0.01,
@@ -108,6 +138,9 @@ class PPOPopulation:
         self.gaussian = getattr(spec, "head", "categorical") == "gaussian"
         if self.gaussian and action_masks:
             raise ValueError("action masks apply to Discrete action spaces, not to a Gaussian policy")
+        # a MultiDiscrete action space: int64 actions [.., K], flat masks [.., L], the
+        # multi-categorical policy step and loss (agx_multi.h); K = 1 included
+        self.multidiscrete = getattr(spec, "head", "categorical") == "multidiscrete"
         self.P, self.N = int(pop_size), int(num_envs)
         # a shard of a population spread over ranks: these P agents are global
         # agents agent_offset .. agent_offset + P of global_pop_size (their
@@ -179,6 +212,8 @@ class PPOPopulation:
         self._edesc = None
         self._gauss = None
         self._glearn = None
+        self._multi = None
+        self._mhead = None
         self._alloc_rollout()
         self.env_base_d = torch.tensor([i * self.N for i in self.agent_ids], dtype=torch.int64, device=self.device)
         self.learn_steps = 0
@@ -194,7 +229,8 @@ class PPOPopulation:
         # image specs keep uint8 frames (normalised inside the first conv's load)
         self.obs = torch.zeros(P, T, N, D, dtype=getattr(self.spec, "obs_dtype", torch.float32), device=dev)
         self.actions = (torch.zeros(P, T, N, self.spec.n_actions, dtype=torch.float32, device=dev) if self.gaussian
-                        else torch.zeros(P, T, N, dtype=torch.int64, device=dev))
+                        else torch.zeros(P, T, N, len(self.spec.nvec), dtype=torch.int64, device=dev)
+                        if self.multidiscrete else torch.zeros(P, T, N, dtype=torch.int64, device=dev))
         self.rewards = torch.zeros(P, T, N, **f32)
         self.dones = torch.zeros(P, T, N, dtype=torch.uint8, device=dev)
         self.values = torch.zeros(P, T, N, **f32)
@@ -230,6 +266,11 @@ class PPOPopulation:
                               counter=int(counter), actions=action, log_probs=logp, values=value, entropy=ent,
                               out_agent_stride=N)
             return action, logp, ent, value
+        if self.multidiscrete:  # one agx_ppo_act_multi_graph launch, int64 actions [P, N, K]
+            if counter is None:
+                self.act_counter += 1
+                counter = self.act_counter
+            return self._multi_step(obs, sample=True, counter=int(counter))
         logits, value = self.spec.forward(self.params.data, obs)
         logp_all, ent = categorical(logits)
         if counter is None:
@@ -248,7 +289,7 @@ class PPOPopulation:
     def fused_descriptor(self):
         """agx_ppo_net for this architecture, or None when the fused kernels do
         not cover it (then the plain-PyTorch forward / learner run)."""
-        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian:
+        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian or self.multidiscrete:
             return None  # the fused kernels take the categorical MLP actor-critic shapes only
         if self._desc is None:
             from .learner import net_descriptor
@@ -261,7 +302,8 @@ class PPOPopulation:
         shapes, else agx_ppo_graph (agx_ppo_learn_graph: any MLP actor-critic
         an architecture mutation produces); None: the plain-PyTorch learner."""
         desc = self.fused_descriptor()
-        if desc is not None or not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian:
+        if (desc is not None or not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian
+                or self.multidiscrete):
             return desc
         if self._gdesc is None:
             from .learner import graph_descriptor
@@ -274,7 +316,7 @@ class PPOPopulation:
         actor-critic, the compiled shapes included, so that a population's
         agents are evaluated together in one launch whatever kernels they train
         on (agx_ppo_eval_multi_persistent).  None: the PyTorch policy step."""
-        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian:
+        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian or self.multidiscrete:
             return None
         if self.fused_descriptor() is None:
             return self.learn_descriptor()  # already the runtime layer list
@@ -296,6 +338,39 @@ class PPOPopulation:
                 raise _lib.AgxError("agx_ppo_act_gauss_graph does not take this network: " +
                                     _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
         return self._gauss
+
+    def multi_descriptor(self):
+        """agx_ppo_graph of a MultiDiscrete population's networks for
+        agx_ppo_act_multi_graph.  There is no other policy step for such a
+        population: a layer list the kernel does not take is an error."""
+        if not self.multidiscrete:
+            return None
+        if self._multi is None:
+            self._multi = self.spec.multi_descriptor()
+            if self._multi is None:
+                raise _lib.AgxError("agx_ppo_act_multi_graph does not take this network: " +
+                                    _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
+        return self._multi
+
+    def multi_head(self):
+        """agx_multi_head of the spec's nvec (made once)."""
+        if self._mhead is None:
+            self._mhead = self.spec.multi_head()
+        return self._mhead
+
+    @torch.no_grad()
+    def _multi_step(self, obs: torch.Tensor, *, sample: bool, counter: int, action_mask=None):
+        """obs [P, N, D] -> (actions int64 [P, N, K], log_prob, entropy, value
+        [P, N]) of a MultiDiscrete population; action_mask uint8 [P, N, L]."""
+        from .learner import policy_step_multi
+
+        P, N, L = self.P, self.N, self.spec.n_actions
+        action = torch.empty(P, N, len(self.spec.nvec), dtype=torch.int64, device=self.device)
+        logp, ent, value = (torch.empty(P, N, dtype=torch.float32, device=self.device) for _ in range(3))
+        policy_step_multi(self, self.multi_descriptor(), obs.contiguous(), N * self.spec.obs_dim, sample=sample,
+                          counter=counter, actions=action, log_probs=logp, values=value, entropy=ent,
+                          out_agent_stride=N, action_mask=action_mask, mask_agent_stride=N * L)
+        return action, logp, ent, value
 
     def gauss_learn_descriptor(self):
         """agx_ppo_graph of a Gaussian population's networks for the fused
@@ -325,6 +400,18 @@ class PPOPopulation:
             policy_step_gauss(self, self.gauss_descriptor(), self.obs[:, t], TN * self.spec.obs_dim, sample=True,
                               counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
                               values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat)
+            return
+        if self.multidiscrete:  # int64 [P*N*K] staging; slot t's stored masks, when the population keeps them
+            from .learner import policy_step_multi
+
+            self.act_counter += 1
+            TN = self.T * self.N
+            masks = self.action_masks
+            policy_step_multi(self, self.multi_descriptor(), self.obs[:, t], TN * self.spec.obs_dim, sample=True,
+                              counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
+                              values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat,
+                              action_mask=None if masks is None else masks[:, t],
+                              mask_agent_stride=TN * self.spec.n_actions)
             return
         desc = self.fused_descriptor()
         if desc is None and self.learn_descriptor() is not None:  # a mutated shape: the runtime-shape kernel
@@ -367,7 +454,7 @@ class PPOPopulation:
         """Bootstrap value + GAE (+ per-agent advantage statistics).  The fused
         runner computes last_value in its final rollout-step launch."""
         self.rollout_id += 1
-        if last_value is None and self.gaussian:
+        if last_value is None and (self.gaussian or self.multidiscrete):
             last_value = self.values_of(last_obs)
         elif last_value is None:
             with torch.no_grad():
@@ -400,10 +487,14 @@ class PPOPopulation:
     @torch.no_grad()
     def values_of(self, obs: torch.Tensor) -> torch.Tensor:
         """The critic's values [P, N] of obs [P, N, D] from a Gaussian
-        population's policy-step kernel (sample = 0, values only)."""
-        from .learner import policy_step_gauss
+        (or MultiDiscrete) population's policy-step kernel (sample = 0, values only)."""
+        from .learner import policy_step_gauss, policy_step_multi
 
         value = torch.empty(self.P, self.N, dtype=torch.float32, device=self.device)
+        if self.multidiscrete:
+            policy_step_multi(self, self.multi_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim,
+                              sample=False, counter=0, values=value, out_agent_stride=self.N)
+            return value
         policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim, sample=False,
                           counter=0, values=value, out_agent_stride=self.N)
         return value
@@ -639,8 +730,9 @@ class PPOPopulation:
         P, S, D = self.P, self.S, self.spec.obs_dim
         image = not isinstance(self.spec, ActorCriticSpec)
         obs = self.obs.view(P, S, D)
-        act = self.actions.view(P * S, -1) if self.gaussian else self.actions.view(P, S)
+        act = (self.actions.view(P * S, -1) if self.gaussian or self.multidiscrete else self.actions.view(P, S))
         masks = None if self.action_masks is None else self.action_masks.view(P, S, -1)
+        flat_masks = None if masks is None else masks.view(P * S, -1)  # the multi-categorical loss gathers them
         old_logp = self.log_probs.view(-1)
         adv = self.advantages.view(-1)
         ret = self.returns.view(-1)
@@ -666,6 +758,11 @@ class PPOPopulation:
                     mean, value = self.spec.forward(self.params, ob)
                     loss, stats = _PPOGaussLossFn.apply(mean, value, self.spec.log_std_view(self.params), act,
                                                         old_logp, adv, ret, old_v, gidx, s1 - s0, self.clip_coef,
+                                                        self.vf_coef, ent_coef)
+                elif self.multidiscrete:  # the loss kernel gathers the int64 actions [.., K] and the masks
+                    logits, value = self.spec.forward(self.params, ob)
+                    loss, stats = _PPOMultiLossFn.apply(logits, value, self.multi_head(), act, flat_masks, old_logp,
+                                                        adv, ret, old_v, gidx, s1 - s0, self.clip_coef,
                                                         self.vf_coef, ent_coef)
                 else:
                     loss, stats = self._categorical_loss(ob, torch.gather(act, 1, idx), masks, idx, rows, image,
@@ -702,6 +799,8 @@ class PPOPopulation:
             policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim,
                               sample=False, counter=0, actions=action, out_agent_stride=self.N)
             return action
+        if self.multidiscrete:  # the first arg-max of every component, [P, N, K]
+            return self._multi_step(obs, sample=False, counter=0)[0]
         logits, _ = self.spec.forward(self.params.data, obs)
         return torch.argmax(logits, dim=-1)
 

@@ -40,7 +40,9 @@ Architectures outside the fused kernels use the plain-PyTorch policy step
 with per-field copies (``_collect_torch``).  A Gaussian (Box-action)
 population takes the same per-step path with its own HIP policy step
 (agx_ppo_act_gauss_graph, one launch per vector step): float32 action staging
-of P*N*A, the env is handed [P*N, A].
+of P*N*A, the env is handed [P*N, A].  A MultiDiscrete population does the
+same through agx_ppo_act_multi_graph: int64 staging of P*N*K, the env is
+handed [P*N, K].
 """
 
 from __future__ import annotations
@@ -216,11 +218,14 @@ class PopulationRunner:
         self.stats_event = None
 
     def _action_staging(self, **kw) -> torch.Tensor:
-        """The env's actions of one vector step: int64 [P*N], or float32
-        [P*N*A] for a Gaussian (Box-action) population."""
+        """The env's actions of one vector step: int64 [P*N], float32
+        [P*N*A] for a Gaussian (Box-action) population, or int64 [P*N*K] for a
+        MultiDiscrete one."""
         pop = self.pop
         if pop.gaussian:
             return torch.zeros(pop.P * pop.N * pop.spec.n_actions, dtype=torch.float32, **kw)
+        if pop.multidiscrete:
+            return torch.zeros(pop.P * pop.N * len(pop.spec.nvec), dtype=torch.int64, **kw)
         return torch.zeros(pop.P * pop.N, dtype=torch.int64, **kw)
 
     def _ctl_bytes(self) -> int:
@@ -282,7 +287,7 @@ class PopulationRunner:
         # numpy views of the staging made once (Tensor.numpy() costs ~1-3 us a call)
         if self._np is None:
             act = self.act_h.numpy()
-            if self.pop.gaussian:  # a Box env takes [P*N, A]
+            if self.pop.gaussian or self.pop.multidiscrete:  # the env takes [P*N, A] floats / [P*N, K] choices
                 act = act.reshape(self.pop.P * self.pop.N, -1)
             self._np = (act, self.obs_h.numpy(), self.rew_h.numpy(), self.done_h.numpy(),
                         self.term_h.numpy())
@@ -436,6 +441,12 @@ class PopulationRunner:
             from .learner import policy_step_gauss
 
             policy_step_gauss(pop, pop.gauss_descriptor(), self.last_obs, N * pop.spec.obs_dim, sample=False,
+                              counter=0, values=self.last_value, out_agent_stride=N)
+            self.last_value_valid = True
+        elif pop.multidiscrete:  # ... or from the multi-categorical one
+            from .learner import policy_step_multi
+
+            policy_step_multi(pop, pop.multi_descriptor(), self.last_obs, N * pop.spec.obs_dim, sample=False,
                               counter=0, values=self.last_value, out_agent_stride=N)
             self.last_value_valid = True
         elif gdesc is not None:  # a mutated shape: the bootstrap value from the runtime-shape kernel too
@@ -749,6 +760,10 @@ class _EvalDriver:
             from .learner import gauss_act_workspace
 
             gauss_act_workspace(pop, pop.gauss_descriptor())
+        elif pop.multidiscrete:
+            from .learner import multi_act_workspace
+
+            multi_act_workspace(pop, pop.multi_descriptor())
         self.obs = None
         self.stream = None  # a dedicated non-blocking stream, assigned by run_lockstep
         self._pipelined = False
@@ -828,6 +843,11 @@ class _EvalDriver:
 
             policy_step_gauss(pop, pop.gauss_descriptor(), self.obs_d, N * D, sample=True, counter=counter,
                               out_agent_stride=N, actions_flat=self.act_d, clip=pop.action_clip())
+        elif pop.multidiscrete:  # a MultiDiscrete population: int64 [P*N*K] staging
+            from .learner import policy_step_multi
+
+            policy_step_multi(pop, pop.multi_descriptor(), self.obs_d, N * D, sample=True, counter=counter,
+                              out_agent_stride=N, actions_flat=self.act_d)
         elif self.edescs is not None:  # the evaluation layer list (as the multi launch samples)
             from .learner import policy_step_graph
 
@@ -878,8 +898,8 @@ class _EvalDriver:
             reward = rew_n
         else:
             act = self.act_h.numpy().copy()
-            self.obs, reward, term, trunc, _ = self.env.step(act.reshape(self.P * self.N, -1) if self.pop.gaussian
-                                                             else act)
+            vec = self.pop.gaussian or self.pop.multidiscrete  # [P*N, A] floats / [P*N, K] choices
+            self.obs, reward, term, trunc, _ = self.env.step(act.reshape(self.P * self.N, -1) if vec else act)
         self.step += 1
         self.scores += np.asarray(reward).reshape(-1)
         done = np.asarray(term, dtype=bool).reshape(-1)

@@ -1,0 +1,85 @@
+/* PPO for MultiDiscrete action spaces: the multi-categorical policy step and loss.
+ *
+ * A MultiDiscrete space with nvec = (n_0 .. n_{K-1}) has L = sum n_k logits:
+ * the actor's output layer has width L (no output activation), and component k
+ * owns the flat logit indices [off_k, off_k + n_k), off_k = n_0 + .. + n_{k-1}
+ * (the reference's StochasticActor, agilerl/networks/actors.py:268, with
+ * networks/distributions.py:193-199 and utils/torch_utils.py:260-333).
+ * Limits: K >= 1, every n_k >= 1, L <= AGX_PPO_GRAPH_MAX_ACTIONS.
+ *
+ * Per row:
+ *   mask      an optional flat mask [.., L] (uint8, 1 = legal) sets an illegal
+ *             logit to -1e8 before anything else (distributions.py:16-28)
+ *   lse_k     = m_k + log sum_j exp(lg_j - m_k), m_k the component's maximum
+ *   p_j       = exp(lg_j - lse_k)
+ *   log_prob  = sum_k (lg[off_k + a_k] - lse_k)
+ *   entropy   = sum_k -sum_j p_j log(p_j + 1e-8)
+ * Both sums over k run in ascending k in float32; within a component a sum is
+ * a fixed-order reduction: equal bits on every launch, whatever other agents
+ * share it.
+ *
+ * Sampling is Gumbel-max per component.  The score of flat logit index j of
+ * the row whose stream env is `env` (agx_ppo_act: agent_env_base[p] + n, or
+ * p N + n) is agx_ppo_act's score of action j,
+ *   lg_j - log(-log u_j),  u_j = ((word (j & 3) >> 8) + 0.5) 2^-24
+ * of the Philox4x32-10 block with counter words (env lo, env hi, counter lo,
+ * counter hi ^ ((j >> 2) << 24)) and key words (seed lo, seed hi): keyed by
+ * the flat index, so K = 1 draws agx_ppo_act_graph's stream and makes its
+ * choice.  The choice of a component is its first maximum (lowest index);
+ * sample 0: the first arg-max of the (masked) logits. */
+#ifndef AGX_MULTI_H
+#define AGX_MULTI_H
+
+#include "agx_graph.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* nvec by value: the host packs it into the kernel arguments (no device table) */
+typedef struct agx_multi_head {
+    int32_t K;
+    int32_t nvec[AGX_PPO_GRAPH_MAX_ACTIONS];
+} agx_multi_head;
+
+/* The policy step of PPO.get_action (agilerl/algorithms/ppo.py:567-633) for a
+ * runtime layer list whose actor output is the L logits of `head`
+ * (net->n_actions = L).  One workgroup per (agent, 16-row block), forward as
+ * agx_ppo_act_graph (same workspace size rule, same AGX_GRAPH_FEW switch).
+ * action_mask [P][..][L] (device, uint8) with agent stride mask_agent_stride
+ * bytes (row n of agent p at p mask_agent_stride + n L), or NULL.
+ * actions int64 [P][..][K], row n of agent p at (p out_agent_stride + n) K:
+ * component k's choice in [0, n_k).  log_probs / values / entropy with agent
+ * stride out_agent_stride; each may be NULL.  actions_flat int64 [P N K] (the
+ * env staging, system-scope stores) or NULL. */
+size_t agx_ppo_act_multi_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t N);
+int agx_ppo_act_multi_graph(const agx_ppo_graph *net, agx_multi_head head, int64_t P, int64_t N, const float *params,
+                            const float *obs, int64_t obs_agent_stride, const uint8_t *action_mask,
+                            int64_t mask_agent_stride, int sample, uint64_t seed, uint64_t counter, int64_t *actions,
+                            float *log_probs, float *values, float *entropy, int64_t out_agent_stride,
+                            int64_t *actions_flat, const int64_t *agent_env_base, void *workspace, void *stream);
+
+/* The multi-categorical twin of agx_ppo_loss_fwd_bwd (agx.h; ppo.py:868-902):
+ * num_minibatches minibatches of `batch` rows.
+ *   logits [nmb batch][L], value [nmb batch]                    (network outputs, raw)
+ *   actions int64 [rows][K], mask uint8 [rows][L] or NULL,
+ *   old_logp / adv / ret / old_value [rows]                     (the rollout)
+ *   index [nmb batch] int64 rollout row of each sample, or NULL (sample i is row i)
+ * -> g_logits [nmb batch][L], g_value [nmb batch], stats [nmb][8] (the layout
+ * of agx_ppo_loss_fwd_bwd; may be NULL).  With gl = d loss / d log_prob and
+ * g_h = -ent_coef / batch:
+ *   g_logit_j = gl (1[j == off_k + a_k] - p_j) + g_h dH_k/dlg_j
+ *   dH_k/dlg_j = -p_j (t_j - sum_i p_i t_i),  t_i = log(p_i + 1e-8) + p_i / (p_i + 1e-8)
+ * and exactly 0 for a masked logit.  An action outside [0, n_k) is clamped
+ * into it.  No atomics: equal bits every run. */
+int agx_ppo_multi_loss_fwd_bwd(const float *logits, const float *value, agx_multi_head head, const int64_t *actions,
+                               const uint8_t *mask, const float *old_logp, const float *adv, const float *ret,
+                               const float *old_value, const int64_t *index, int64_t batch, int64_t num_minibatches,
+                               float clip_coef, float vf_coef, float ent_coef, float *g_logits, float *g_value,
+                               float *stats, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif
