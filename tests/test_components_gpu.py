@@ -142,6 +142,44 @@ def test_prioritized_replay_buffer_matches_oracle(max_size, batches, B):
         assert buf.max_priority == ref.max_priority
 
 
+def test_prioritized_replay_buffer_large_batches_match_oracle():
+    """A 70 000 ring (cap 2^17) filled in chunks, the last an add of 1500 rows
+    across the ring end, then 1500 sampled indices updated: the batches above
+    1024 that take the multi-launch kernels, through the buffer's own API."""
+    from agilerl_amd.components.replay_buffer import PrioritizedReplayBuffer
+
+    max_size, B = 70_000, 1500
+    rng = np.random.default_rng(max_size)
+    buf = PrioritizedReplayBuffer(max_size, alpha=0.6)
+    ref = oper.PER(max_size, alpha=0.6)
+    for n in (20_000, 20_000, 20_000, 9_500, 1_500):
+        buf.add({"obs": rng.standard_normal((n, 4)).astype(np.float32), "reward": np.zeros(n, np.float32)})
+        ref.add(n)
+    assert len(buf) == max_size == ref.size and buf.tree_ptr == ref.tree_ptr == 1000
+
+    def same_trees():
+        for dev, want in ((buf.sum_tree, ref.sum_tree), (buf.min_tree, ref.min_tree)):
+            np.testing.assert_array_equal(dev.tree.cpu().numpy().view(np.uint64)[1:],
+                                          np.asarray(want.tree).view(np.uint64)[1:])
+
+    same_trees()
+    for step, beta in enumerate((0.4, 0.5)):
+        torch.manual_seed(step)
+        u = torch.rand(B).numpy()
+        torch.manual_seed(step)
+        s = buf.sample(B, beta=beta)
+        want_idx = ref.sample_indices(u)
+        np.testing.assert_array_equal(s["idxs"].view(-1).cpu().numpy(), want_idx)
+        np.testing.assert_allclose(s["weights"].view(-1).cpu().numpy(), ref.weights(want_idx, beta), rtol=2e-7)
+        if step == 0:
+            pri = np.abs(rng.standard_normal(B)).astype(np.float32) * 3
+            pri[:3] = 0.0  # floor 1e-5
+            buf.update_priorities(s["idxs"], torch.as_tensor(pri))
+            ref.update_priorities(want_idx, pri)
+            same_trees()
+            assert buf.max_priority == ref.max_priority > 1.0
+
+
 def test_replay_buffer_circular_and_uniform_sample():
     from agilerl_amd.components.replay_buffer import ReplayBuffer
 

@@ -205,7 +205,10 @@ def test_per_golden_indices_bit_exact(golden, case):
 
 
 def test_per_large_batches_vs_c_oracle():
-    """Multi-launch path (batches > 1024) incl. duplicates, cap 2^17."""
+    """Batches > 1024 incl. duplicates at cap 2^17: 20 000 updates are a dense
+    batch (20 000 * 32 >= 2^17), so the rebuild is one band of 6 levels and
+    the top block — not the per-level launches, which
+    tests/test_per_paths_gpu.py reaches."""
     rng = np.random.default_rng(5)
     ms, alpha, beta = 100_000, 0.6, 0.4
     cap = oper.tree_capacity(ms)
@@ -296,6 +299,21 @@ def test_libm_pow_bit_exact():
     assert off.any()  # the set exists ...
     assert np.array_equal(got[:4000][off], want[:4000][off])  # ... and the device matches libm on it
     assert float(K().debug_pow(T(np.array([1.1696802377700806])), T(np.array([0.6]))).cpu()[0]) == 1.0986017625035922
+    # the legal settings alpha, beta = 0 and 1 and further exponents, on float64
+    # bases and on what priorities really are: float32 values widened to float64
+    edge = np.array([1e-5, float(np.float32(1e-5)), 1.0, float(np.nextafter(np.float32(1), np.float32(0))),
+                     float(np.nextafter(np.float32(1), np.float32(2))), 2.0, 0.5])
+    x32 = np.concatenate([(np.abs(rng.standard_normal(n // 4)) + 1e-5).astype(np.float32),
+                          np.exp(rng.uniform(np.log(1e-5), np.log(1e3), n // 4)).astype(np.float32)]).astype(np.float64)
+    x2 = np.concatenate([edge, x32, x[:n // 2]])
+    ys = [0.0, 1.0, 2.0, 0.3, 0.8, -0.0, 0.6, 0.4, -0.4, -1.0]
+    y2 = rng.choice(ys, size=x2.size)
+    y2[:edge.size * len(ys)] = np.repeat(ys, edge.size)  # every edge base at every exponent ...
+    x2[:edge.size * len(ys)] = np.tile(edge, len(ys))
+    got2 = K().debug_pow(T(x2), T(y2)).cpu().numpy()
+    want2 = cref.libm_pow(x2, y2)
+    bad2 = np.flatnonzero(got2.view(np.uint64) != want2.view(np.uint64))
+    assert bad2.size == 0, (bad2.size, x2[bad2[:3]], y2[bad2[:3]], got2[bad2[:3]], want2[bad2[:3]])
 
 
 # --------------------------------------------------------------------------- #
