@@ -74,6 +74,9 @@ SIGNATURES = {
     "agx_ppo_act_multi_graph": (_INT, [_P, AgxMultiHead, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64,
                                        ctypes.c_uint64, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "agx_ppo_multi_loss_fwd_bwd": (_INT, [_P, _P, AgxMultiHead] + [_P] * 7 + [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "agx_ppo_multi_graph_check": (_INT, [_P, AgxMultiHead]),
+    "agx_ppo_learn_multi_graph_workspace_bytes": (_SZ, [_P, AgxMultiHead, _I, _I, _I, _I]),
+    "agx_ppo_learn_multi_graph": (_INT, [_P, AgxMultiHead, _P, _P, _P]),
     "agx_ppo_learn": (_INT, [_P, _P, _P, _P]),
     "agx_ppo_act": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                            _I, _P, _P, _P]),

@@ -30,13 +30,27 @@
 // (shared with the policy step, graph_rollout.hip); this unit is the backward,
 // the learn kernels and their host side.
 //
-// GAUSS (a compile-time parameter of the three kernels): the diagonal-Gaussian
+// HEAD (a compile-time parameter of the three kernels): kCat, the categorical
+// head of a Discrete action space; kGauss and kMulti below.
+//
+// kGauss: the diagonal-Gaussian
 // head of a Box action space (include/agx_gauss.h).  The actor's output is the
 // mean, the stored actions are float [A] per row, and the A log_std floats at
 // GArgs::lso are parameters no layer owns: the loss row pass computes their
 // gradient (a column sum over the rows, as the output-layer bias gradients),
 // the clip counts them in the actor group and Adam steps them with the row.
+//
+// kMulti: the multi-categorical head of a MultiDiscrete action space
+// (include/agx_multi.h).  The network is the categorical one at n_actions =
+// L = sum nvec, so forward, backward, exchange, clip and Adam are the
+// categorical instantiation's; the gather packs a row's K stored actions into
+// one target word (bit off_k + a_k per component, gact as the categorical
+// index: 4 bytes per row) and the loss row pass walks the K components
+// (GArgs::mk / mn, by value in the kernel arguments) with the lanes outside the
+// component neutral in row_max / row_sum, as multi_policy.hip's multi_step.
+// For K = 1 the pass runs the categorical pass's float operations in its order.
 #include "../../include/agx_gauss.h"
+#include "../../include/agx_multi.h"
 #include "gauss_head.h"
 #include "graph_net.h"
 #include "ppo_loss_sample.h"
@@ -217,8 +231,10 @@ __device__ __forceinline__ void bwd_rows(const GLay &L, float *base, const float
 
 // words per wave of the output layers' column partials (colo): 32 logits /
 // means and the value; the Gaussian head adds its 32 log_std (and a pad word)
-template <bool GAUSS>
-constexpr int kColo = GAUSS ? 66 : 33;
+// the head of the three learner kernels and their helpers (a compile-time parameter)
+enum Head : int { kCat = 0, kGauss = 1, kMulti = 2 };
+template <Head HEAD>
+constexpr int kColo = HEAD == kGauss ? 66 : 33;
 
 // loss_sample's coefficients for a minibatch of 1 / inv_b rows
 __device__ __forceinline__ LossCoef loss_coef(const GArgs &g, float inv_b, float entp) {
@@ -330,12 +346,213 @@ __device__ __forceinline__ void gauss_loss_rows(const GArgs &g, float *base, con
     gs1 += __shfl_xor(gs1, 16, 64);
     gs1 += __shfl_xor(gs1, 32, 64);
     if (rq == 0) {
-        float *co = colo + wave * kColo<true>;
+        float *co = colo + wave * kColo<kGauss>;
         co[a0] = cb0;
         co[a1] = cb1;
         if (sub == 0) co[32] = cbv;
         co[33 + a0] = gs0;
         co[33 + a1] = gs1;
+    }
+}
+
+// ---- the multi-categorical head (include/agx_multi.h) ---------------------
+constexpr float kSegOut = -3.0e38f;  // a lane outside the component (or past L) in a maximum
+
+// component k's size n_k (wave-uniform: the head is a kernel argument)
+__device__ __forceinline__ int multi_n(const GArgs &g, int k) {
+    return (int)((g.mn[k >> 2] >> (8 * (k & 3))) & 0xffu);
+}
+
+// What the component walk leaves of a row.  Every lane of the row: its
+// log-prob and entropy, summed over the components in ascending k.  Of the
+// lane's two logits (each in exactly one component): p, gh = -(log(p + 1e-8) +
+// p / (p + 1e-8)) and pg = sum p gh over the logit's own component.
+struct MultiRow {
+    float lp = 0.f, H = 0.f;
+    float p0 = 0.f, p1 = 0.f, gh0 = 0.f, gh1 = 0.f, pg0 = 0.f, pg1 = 0.f;
+};
+
+// Component k of a row: in0 / in1, the lane's logits (masked: -1e8) inside the
+// component; t0 / t1, the logit is the stored choice.  The categorical pass's
+// float operations in its order, with the lanes outside the component neutral
+// (multi_policy.hip's seg_lse); the chosen logit comes from a row maximum over
+// the one lane holding it (exact) in place of the categorical pass's bpermute.
+__device__ __forceinline__ void multi_component(int k, bool in0, bool in1, float lg0, float lg1, bool t0, bool t1,
+                                                MultiRow &r) {
+    const float mx = row_max(fmaxf(in0 ? lg0 : kSegOut, in1 ? lg1 : kSegOut));
+    const float ex0 = in0 ? expf(lg0 - mx) : 0.f, ex1 = in1 ? expf(lg1 - mx) : 0.f;
+    const float lse = mx + logf(row_sum(ex0 + ex1));
+    const float p0 = in0 ? expf(lg0 - lse) : 0.f, p1 = in1 ? expf(lg1 - lse) : 0.f;
+    const float lpe0 = logf(p0 + 1e-8f), lpe1 = logf(p1 + 1e-8f);
+    const float Hk = -row_sum((in0 ? p0 * lpe0 : 0.f) + (in1 ? p1 * lpe1 : 0.f));
+    const float gh0 = -(lpe0 + p0 / (p0 + 1e-8f)), gh1 = -(lpe1 + p1 / (p1 + 1e-8f));
+    const float pg = row_sum((in0 ? p0 * gh0 : 0.f) + (in1 ? p1 * gh1 : 0.f));
+    const float lga = row_max(fmaxf((in0 && t0) ? lg0 : kSegOut, (in1 && t1) ? lg1 : kSegOut));
+    const float lpk = lga - lse;
+    r.lp = k == 0 ? lpk : r.lp + lpk;  // ascending k
+    r.H = k == 0 ? Hk : r.H + Hk;
+    if (in0) {
+        r.p0 = p0;
+        r.gh0 = gh0;
+        r.pg0 = pg;
+    }
+    if (in1) {
+        r.p1 = p1;
+        r.gh1 = gh1;
+        r.pg1 = pg;
+    }
+}
+
+// component k's results c (multi_component from a fresh MultiRow) into the row's
+__device__ __forceinline__ void multi_merge(int k, bool in0, bool in1, const MultiRow &c, MultiRow &r) {
+    r.lp = k == 0 ? c.lp : r.lp + c.lp;  // ascending k
+    r.H = k == 0 ? c.H : r.H + c.H;
+    if (in0) {
+        r.p0 = c.p0;
+        r.gh0 = c.gh0;
+        r.pg0 = c.pg0;
+    }
+    if (in1) {
+        r.p1 = c.p1;
+        r.gh1 = c.gh1;
+        r.pg1 = c.pg1;
+    }
+}
+
+// The row's clipped surrogate, value loss and approx-KL from its log-prob and
+// entropy, and the gradients of the lane's two logits and of the value: the
+// categorical pass's operations (tie and closed-interval rules included).
+struct MultiOut {
+    float dl0, dl1, dvv, loss, kl;
+};
+__device__ __forceinline__ MultiOut multi_row_loss(const GArgs &g, const MultiRow &r, bool t0, bool t1, float olp,
+                                                   float Ad, float Rt, float ov, float v, float inv_b, float entp) {
+    const float logp = r.lp, Hs = r.H;
+    const float lo = 1.f - g.clip, hi = 1.f + g.clip;
+    const float lrt = logp - olp;
+    const float ratio = expf(lrt);
+    const float rcl = fminf(fmaxf(ratio, lo), hi);
+    const float q1 = -Ad * ratio, q2 = -Ad * rcl;
+    const float g1 = q1 > q2 ? 1.f : (q1 == q2 ? 0.5f : 0.f);
+    const float g2 = q2 > q1 ? 1.f : (q1 == q2 ? 0.5f : 0.f);
+    const float inr = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
+    const float g_logp = ((g1 * -Ad + g2 * -Ad * inr) * inv_b) * ratio;
+    const float dv = v - ov;
+    const float vcl = ov + fminf(fmaxf(dv, -g.clip), g.clip);
+    const float eu = v - Rt, ec = vcl - Rt;
+    const float lu = eu * eu, lc = ec * ec;
+    const float gu = lu > lc ? 1.f : (lu == lc ? 0.5f : 0.f);
+    const float gc = lc > lu ? 1.f : (lu == lc ? 0.5f : 0.f);
+    const float inv = (dv >= -g.clip && dv <= g.clip) ? 1.f : 0.f;
+    const float g_H = -entp * inv_b;
+    MultiOut o;
+    o.dl0 = g_logp * ((t0 ? 1.f : 0.f) - r.p0) + g_H * r.p0 * (r.gh0 - r.pg0);
+    o.dl1 = g_logp * ((t1 ? 1.f : 0.f) - r.p1) + g_H * r.p1 * (r.gh1 - r.pg1);
+    o.dvv = g.vf * 0.5f * inv_b * (gu * 2.f * eu + gc * 2.f * ec * inv);
+    o.loss = (fmaxf(q1, q2) + g.vf * 0.5f * fmaxf(lu, lc) - entp * Hs) * inv_b;
+    o.kl = ((ratio - 1.f) - lrt) * inv_b;  // approx_kl (ppo.py:899-902)
+    return o;
+}
+
+// The multi-categorical head's loss row pass over `bsz` rows of the general
+// form: the categorical pass's geometry in minibatch_grads (16 lanes per row,
+// flat logits sub and sub + 16 per lane, four rows per lane group in flight)
+// and its outputs (d(logits) in both layouts, d(value), the output-layer bias
+// column partials in colo, [kGW][33]).  tgt_e: the rows' target words.
+__device__ __forceinline__ void multi_loss_rows(const GArgs &g, float *base, const unsigned *tgt_e,
+                                                const unsigned *gmask_e, const float *grow_e, long long s0, int bsz,
+                                                float inv_b, float entp, float *colo, float &lsum, float &klsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, rq = lane >> 4;
+    const int bp = g.bp, A = g.A, K = g.mk;
+    const long long S = g.S;
+    const GLay &La = g.L[g.aout];
+    const GLay &Lc = g.L[g.cout];
+    const float *lgp = base + La.yr;
+    const float *vp = base + Lc.yr;
+    float *dla = base + La.dy;
+    float *dlac = base + La.dyc;
+    float *dlv = base + Lc.dy;
+    const int a0 = sub, a1 = sub + 16;
+    float cb0 = 0.f, cb1 = 0.f, cbv = 0.f;  // output-layer bias gradients (column partials)
+    constexpr int R = 4;
+    for (int rb = 0; rb < bsz; rb += R * 4 * kGW) {
+        unsigned pbits[R], ptgt[R];
+        float plg0[R], plg1[R], polp[R], pad[R], pret[R], pov[R], pv[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row0 = rb + 4 * wave + rq + 4 * kGW * u;
+            const int row = row0 < bsz ? row0 : 0;
+            pbits[u] = gmask_e ? gmask_e[s0 + row] : 0xffffffffu;
+            plg0[u] = lgp[(size_t)row * A + (a0 < A ? a0 : 0)];
+            plg1[u] = lgp[(size_t)row * A + (a1 < A ? a1 : 0)];
+            ptgt[u] = tgt_e[s0 + row];
+            polp[u] = grow_e[s0 + row];
+            pad[u] = grow_e[S + s0 + row];
+            pret[u] = grow_e[2 * S + s0 + row];
+            pov[u] = grow_e[3 * S + s0 + row];
+            pv[u] = vp[row];
+        }
+        float lg0[R], lg1[R];
+        bool t0[R], t1[R];
+        MultiRow mr[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const bool ok0 = (pbits[u] >> a0) & 1u, ok1 = (pbits[u] >> a1) & 1u;
+            lg0[u] = a0 < A ? (ok0 ? plg0[u] : -1.0e8f) : kSegOut;
+            lg1[u] = a1 < A ? (ok1 ? plg1[u] : -1.0e8f) : kSegOut;
+            t0[u] = (ptgt[u] >> a0) & 1u;
+            t1[u] = (ptgt[u] >> a1) & 1u;
+        }
+        int off = 0;
+        for (int k = 0; k < K; ++k) {  // wave-uniform: K and the sizes are kernel arguments
+            const int n = multi_n(g, k);
+            const bool in0 = a0 >= off && a0 < off + n, in1 = a1 >= off && a1 < off + n;
+#pragma unroll
+            for (int u = 0; u < R; ++u) multi_component(k, in0, in1, lg0[u], lg1[u], t0[u], t1[u], mr[u]);
+            off += n;
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row0 = rb + 4 * wave + rq + 4 * kGW * u;
+            const bool live = row0 < bsz;
+            const int row = live ? row0 : 0;
+            const bool ok0 = (pbits[u] >> a0) & 1u, ok1 = (pbits[u] >> a1) & 1u;
+            const MultiOut o =
+                multi_row_loss(g, mr[u], t0[u], t1[u], polp[u], pad[u], pret[u], pov[u], pv[u], inv_b, entp);
+            if (live) {
+                const float d0 = ok0 ? o.dl0 : 0.f, d1 = ok1 ? o.dl1 : 0.f;
+                if (a0 < A) {
+                    dla[(size_t)row * A + a0] = d0;
+                    dlac[(size_t)a0 * bp + row] = d0;
+                    cb0 += d0;
+                }
+                if (a1 < A) {
+                    dla[(size_t)row * A + a1] = d1;
+                    dlac[(size_t)a1 * bp + row] = d1;
+                    cb1 += d1;
+                }
+                if (sub == 0) {
+                    dlv[row] = o.dvv;
+                    cbv += o.dvv;
+                    lsum += o.loss;
+                    klsum += o.kl;
+                }
+            }
+        }
+    }
+    // bias gradients of the output layers: the wave's four row groups, then
+    // per wave into LDS (the caller sums the waves in order)
+    cb0 += __shfl_xor(cb0, 16, 64);
+    cb0 += __shfl_xor(cb0, 32, 64);
+    cb1 += __shfl_xor(cb1, 16, 64);
+    cb1 += __shfl_xor(cb1, 32, 64);
+    cbv += __shfl_xor(cbv, 16, 64);
+    cbv += __shfl_xor(cbv, 32, 64);
+    if (rq == 0) {
+        colo[wave * 33 + a0] = cb0;
+        colo[wave * 33 + a1] = cb1;
+        if (sub == 0) colo[wave * 33 + 32] = cbv;
     }
 }
 
@@ -347,8 +564,9 @@ __device__ __forceinline__ void gauss_loss_rows(const GArgs &g, float *base, con
 // it).  base: this workgroup's activation scratch; wb: where the transposed
 // weights live (wb + L.wt).  Shared by the one-workgroup-per-agent learner and
 // the partnered one (each partner over its slice of the rows).
-// GAUSS: gact_e holds the rows' float actions [A]; colo has kColo<GAUSS> words per wave.
-template <bool GAUSS>
+// kGauss: gact_e holds the rows' float actions [A]; kMulti: the rows' target words
+// (multi_loss_rows); colo has kColo<HEAD> words per wave.
+template <Head HEAD>
 __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, const float *wb, const float *pr, float *G,
                                                 const float *xobs, const int *gact_e, const unsigned *gmask_e,
                                                 const float *grow_e, long long s0, int bsz, float inv_b, float entp,
@@ -370,10 +588,14 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
     forward_layers(g.L, g.nl, xobs, bsz, base, pr, bp, lds, g.dbg, st);
 
     // ---- loss row pass: logits / value -> d(logits), d(value) (ppo.py:876-908)
-    if constexpr (GAUSS) {
+    if constexpr (HEAD == kGauss) {
         if (!(g.dbg & 8))
             gauss_loss_rows(g, base, pr, reinterpret_cast<const float *>(gact_e), grow_e, s0, bsz, inv_b, entp, colo,
                             lsum, klsum);
+    } else if constexpr (HEAD == kMulti) {
+        if (!(g.dbg & 8))
+            multi_loss_rows(g, base, reinterpret_cast<const unsigned *>(gact_e), gmask_e, grow_e, s0, bsz, inv_b, entp,
+                            colo, lsum, klsum);
     } else if (!(g.dbg & 8)) {
         const GLay &La = g.L[g.aout];
         const GLay &Lc = g.L[g.cout];
@@ -486,15 +708,15 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
     __syncthreads();
     if (!(g.dbg & 8) && tid <= A) {
         float sb = 0.f;
-        for (int w = 0; w < kGW; ++w) sb += colo[w * kColo<GAUSS> + (tid < A ? tid : 32)];
+        for (int w = 0; w < kGW; ++w) sb += colo[w * kColo<HEAD> + (tid < A ? tid : 32)];
         G[tid < A ? g.L[g.aout].b + tid : g.L[g.cout].b] = sb;
     }
-    if constexpr (GAUSS) {
+    if constexpr (HEAD == kGauss) {
         // d(log_std): the waves' partials in order, and the entropy's -ent_coef / b per row of the slice
         const int d = tid - kWave;
         if (!(g.dbg & 8) && d >= 0 && d < A) {
             float sg = 0.f;
-            for (int w = 0; w < kGW; ++w) sg += colo[w * kColo<GAUSS> + 33 + d];
+            for (int w = 0; w < kGW; ++w) sg += colo[w * kColo<HEAD> + 33 + d];
             G[g.lso + d] = sg + (-entp * inv_b) * (float)bsz;
         }
     }
@@ -598,12 +820,12 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
 
 }
 
-template <bool GAUSS>
+template <Head HEAD>
 __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
     __shared__ float red[2 * kGW];
     __shared__ __attribute__((aligned(16))) float lds[kGemmLds];
     __shared__ float colp[2 * 3 * kGW * 128];  // per-wave bias / LN-affine column partials (F <= 128), by layer parity
-    __shared__ float colo[kGW * kColo<GAUSS>];  // per-wave output-layer partials (32 logits + the value; + log_std)
+    __shared__ float colo[kGW * kColo<HEAD>];  // per-wave output-layer partials (32 logits + the value; + log_std)
     if (g.skip && __hip_atomic_load(g.skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;
     const int p = blockIdx.x;
     const int tid = threadIdx.x;
@@ -642,7 +864,7 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
     for (int e = 0; e < Ep; ++e) {
         const size_t ge = (size_t)e * g.P + p;
         const float *gobs_e = g.gobs + ge * S * D;
-        const int *gact_e = g.gact + ge * S * (GAUSS ? g.A : 1);
+        const int *gact_e = g.gact + ge * S * (HEAD == kGauss ? g.A : 1);
         const unsigned *gmask_e = g.gmask ? g.gmask + ge * S : nullptr;
         const float *grow_e = g.grow + ge * 4 * S;
         for (int mb = 0; mb < nmb; ++mb) {
@@ -652,7 +874,7 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
             const float *xobs = gobs_e + s0 * D;
 
             float lsum = 0.f, klsum = 0.f;
-            minibatch_grads<GAUSS>(g, base, base, pr, G, xobs, gact_e, gmask_e, grow_e, s0, bsz, inv_b, entp, lds,
+            minibatch_grads<HEAD>(g, base, base, pr, G, xobs, gact_e, gmask_e, grow_e, s0, bsz, inv_b, entp, lds,
                                    colp, colo, lsum, klsum);
             // ---- loss / kl, clip, Adam ------------------------------------------
             block_sum2(lsum, klsum, red);
@@ -718,7 +940,7 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_kernel(const GArgs g) {
                 adam_region(f0, kind == 0 ? L.fout * L.fin : L.fout, kind == 0 ? L.wt : -1, kind == 0 ? L.fin : 1,
                             kind == 0 ? L.fout : 1);
             }
-            if constexpr (GAUSS) {  // log_std: owned by no layer, no transposed copy
+            if constexpr (HEAD == kGauss) {  // log_std: owned by no layer, no transposed copy
                 if (!(g.dbg & 32)) adam_region((int)g.lso, g.A, -1, 1, 1);
             }
             __syncthreads();
@@ -959,12 +1181,70 @@ __device__ __forceinline__ void few_gauss_loss_rows(const GArgs &g, float *S, co
     }
 }
 
+// The multi-categorical head's loss row pass of the few-row form: the lane
+// group's row (4 wave + rq) of the partner's rk <= 16 rows, multi_loss_rows'
+// math per element, the categorical few-row pass's outputs (d(logits) /
+// d(value) to the output layers' dY tiles, zero past the slice).
+__device__ __forceinline__ void few_multi_loss_rows(const GArgs &g, float *S, const unsigned *tgt_e,
+                                                    const unsigned *gmask_e, const float *grow_e, long long s0, int rk,
+                                                    float inv_b, float entp, float &lsum, float &klsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, rq = lane >> 4;
+    const int row = 4 * wave + rq;
+    const int A = g.A, K = g.mk;
+    const long long S_ = g.S;
+    const GLay &La = g.L[g.aout];
+    const GLay &Lc = g.L[g.cout];
+    const float *lgp = S + La.yr + row * La.ld;
+    float *dla = S + La.dy + row * La.ld;
+    const bool live = row < rk;
+    const int rr = live ? row : 0;
+    const int a0 = sub, a1 = sub + 16;
+    const unsigned bits = gmask_e ? gmask_e[s0 + rr] : 0xffffffffu;
+    const float plg0 = lgp[a0 < A ? a0 : 0], plg1 = lgp[a1 < A ? a1 : 0];
+    const unsigned tgt = tgt_e[s0 + rr];
+    const float olp = grow_e[s0 + rr], Ad = grow_e[S_ + s0 + rr];
+    const float Rt = grow_e[2 * S_ + s0 + rr], ov = grow_e[3 * S_ + s0 + rr];
+    const float v = S[Lc.yr + row * Lc.ld];
+    const bool ok0 = (bits >> a0) & 1u, ok1 = (bits >> a1) & 1u;
+    const float lg0 = a0 < A ? (ok0 ? plg0 : -1.0e8f) : kSegOut;
+    const float lg1 = a1 < A ? (ok1 ? plg1 : -1.0e8f) : kSegOut;
+    const bool t0 = (tgt >> a0) & 1u, t1 = (tgt >> a1) & 1u;
+    MultiRow mr;
+    int off = 0;
+    // two components per pass: their reduction chains are independent, so one
+    // hides the other's latency; the sums still add in ascending k
+    for (int k = 0; k < K; k += 2) {  // wave-uniform: K and the sizes are kernel arguments
+        const bool two = k + 1 < K;
+        const int n = multi_n(g, k), n2 = two ? multi_n(g, k + 1) : 0;
+        const int off2 = off + n;
+        MultiRow ra, rb;
+        multi_component(0, a0 >= off && a0 < off + n, a1 >= off && a1 < off + n, lg0, lg1, t0, t1, ra);
+        multi_component(0, a0 >= off2 && a0 < off2 + n2, a1 >= off2 && a1 < off2 + n2, lg0, lg1, t0, t1, rb);
+        multi_merge(k, a0 >= off && a0 < off + n, a1 >= off && a1 < off + n, ra, mr);
+        if (two) multi_merge(k + 1, a0 >= off2 && a0 < off2 + n2, a1 >= off2 && a1 < off2 + n2, rb, mr);
+        off = off2 + n2;
+    }
+    const MultiOut o = multi_row_loss(g, mr, t0, t1, olp, Ad, Rt, ov, v, inv_b, entp);
+    // rows past the slice: a zero gradient (their tiles hold the last minibatch's rows)
+    if (a0 < A) dla[a0] = (live && ok0) ? o.dl0 : 0.f;
+    if (a1 < A) dla[a1] = (live && ok1) ? o.dl1 : 0.f;
+    if (sub == 0) {
+        S[Lc.dy + row * Lc.ld] = live ? o.dvv : 0.f;
+        if (live) {
+            lsum += o.loss;
+            klsum += o.kl;
+        }
+    }
+}
+
 // One update's gradient of a partner's rows (rk <= 16 of them, observations
 // at xobs, rollout rows s0 ..) into the gradient row G, plus the loss /
 // approx_kl partial sums: the few-row counterpart of minibatch_grads, same
 // float operations per element.  S: the LDS tiles (plan_few).
-// GAUSS: gact_e holds the rows' float actions [A] (few_gauss_loss_rows).
-template <bool GAUSS>
+// kGauss: gact_e holds the rows' float actions [A] (few_gauss_loss_rows); kMulti:
+// the rows' target words (few_multi_loss_rows).
+template <Head HEAD>
 __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float *pr, const float *wb, float *G,
                                           const float *xobs, const int *gact_e, const unsigned *gmask_e,
                                           const float *grow_e, long long s0, int rk, float inv_b, float entp,
@@ -993,9 +1273,12 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
     few_forward(g.L, g.nl, S, pr, prs, g.oc, g.ld0, st);
 
     // ---- PPO loss row pass: logits / value -> d(logits), d(value) (ppo.py:876-908)
-    if constexpr (GAUSS) {
+    if constexpr (HEAD == kGauss) {
         few_gauss_loss_rows(g, S, pr, reinterpret_cast<const float *>(gact_e), grow_e, s0, rk, inv_b, entp, lsum,
                             klsum);
+    } else if constexpr (HEAD == kMulti) {
+        few_multi_loss_rows(g, S, reinterpret_cast<const unsigned *>(gact_e), gmask_e, grow_e, s0, rk, inv_b, entp,
+                            lsum, klsum);
     } else {
         const GLay &La = g.L[g.aout];
         const GLay &Lc = g.L[g.cout];
@@ -1056,7 +1339,7 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
         }
     }
     __syncthreads();
-    if constexpr (GAUSS) {
+    if constexpr (HEAD == kGauss) {
         // d(log_std): the 16 rows' terms (left in the mean tile) in row order, and
         // the entropy's -ent_coef / b per row of the slice
         if (wave == kGW - 1 && lane < A) {
@@ -1157,12 +1440,12 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
 
 // FEW: the few-row form (few_grads, activations in dynamic LDS); else the
 // general form (minibatch_grads over the partner's global scratch)
-template <bool FEW, bool GAUSS>
+template <bool FEW, Head HEAD>
 __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g) {
     __shared__ float red[2 * kGW];
     __shared__ __attribute__((aligned(16))) float lds[kGemmLds];
     __shared__ float colp[2 * 3 * kGW * 128];
-    __shared__ float colo[kGW * kColo<GAUSS>];
+    __shared__ float colo[kGW * kColo<HEAD>];
     __shared__ int s_ok;
     __shared__ long long s_st[16 + kGStampsIn];  // phase stamps (agent 0, partner 0, update 1), then per layer
     if (g.skip && __hip_atomic_load(g.skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;
@@ -1237,7 +1520,7 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g
     for (int e = 0; e < Ep; ++e) {
         const size_t ge = (size_t)e * P + p;
         const float *gobs_e = g.gobs + ge * S * D;
-        const int *gact_e = g.gact + ge * S * (GAUSS ? g.A : 1);
+        const int *gact_e = g.gact + ge * S * (HEAD == kGauss ? g.A : 1);
         const unsigned *gmask_e = g.gmask ? g.gmask + ge * S : nullptr;
         const float *grow_e = g.grow + ge * 4 * S;
         for (int mb = 0; mb < nmb; ++mb) {
@@ -1258,10 +1541,10 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g
             float lsum = 0.f, klsum = 0.f;
             if (rk > 0) {
                 if constexpr (FEW)
-                    few_grads<GAUSS>(g, base, pr, wb, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e, s0 + r0, rk,
+                    few_grads<HEAD>(g, base, pr, wb, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e, s0 + r0, rk,
                                      inv_b, entp, lsum, klsum, stamp ? s_st + 16 : nullptr);
                 else
-                    minibatch_grads<GAUSS>(g, base, wb, pr, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e,
+                    minibatch_grads<HEAD>(g, base, wb, pr, G, gobs_e + (s0 + r0) * D, gact_e, gmask_e, grow_e,
                                            s0 + r0, rk, inv_b, entp, lds, colp, colo, lsum, klsum,
                                            stamp ? s_st + 16 : nullptr);
             } else {  // no rows this minibatch (a short last minibatch): publish zeros
@@ -1490,13 +1773,13 @@ GraphWs graph_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int aw) {
     return w;
 }
 
-template <bool FEW, bool GAUSS>
+template <bool FEW, Head HEAD>
 int part_occupancy(size_t dyn) {  // co-resident partner workgroups per CU with dyn bytes of dynamic LDS
     static size_t last = (size_t)-1;
     static int n = 1;
     if (dyn != last) {
         int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, ppo_learn_graph_part_kernel<FEW, GAUSS>, kGT, dyn) != hipSuccess)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, ppo_learn_graph_part_kernel<FEW, HEAD>, kGT, dyn) != hipSuccess)
             v = 1;
         n = v < 1 ? 1 : v;
         last = dyn;
@@ -1505,16 +1788,16 @@ int part_occupancy(size_t dyn) {  // co-resident partner workgroups per CU with 
 }
 // dynamic LDS the few-row form may take: the CU's 160 KB less the kernel's
 // static LDS (queried once per head)
-template <bool GAUSS>
+template <Head HEAD>
 size_t few_lds_budget() {
     static size_t b = 0;
     if (!b) {
         hipFuncAttributes fa{};
-        const size_t st = hipFuncGetAttributes(&fa, (const void *)ppo_learn_graph_part_kernel<true, GAUSS>) == hipSuccess
+        const size_t st = hipFuncGetAttributes(&fa, (const void *)ppo_learn_graph_part_kernel<true, HEAD>) == hipSuccess
                               ? fa.sharedSizeBytes
                               : 8 * 1024;
         b = st < kLdsMax ? kLdsMax - st : 1;
-        (void)hipFuncSetAttribute((const void *)ppo_learn_graph_part_kernel<true, GAUSS>,
+        (void)hipFuncSetAttribute((const void *)ppo_learn_graph_part_kernel<true, HEAD>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
     }
     return b;
@@ -1524,9 +1807,9 @@ size_t few_lds_budget() {
 // LDS: per layer Y, xhat + rstd (LayerNorm), dY, each [16][ld]; the
 // observation tile; one dY' tile for the LN-affine gradients.  -> LDS bytes
 // (0: the plan does not fit, or the graph is invalid)
-template <bool GAUSS>
+template <Head HEAD>
 size_t plan_few(const agx_ppo_graph *net, GArgs &a) {
-    if (plan_graph(net, kFR, a, GAUSS ? net->n_actions : 0) != AGX_OK) return 0;
+    if (plan_graph(net, kFR, a, HEAD == kGauss ? net->n_actions : 0) != AGX_OK) return 0;
     auto ldof = [](int w) { return (w + 15) / 16 * 16 + 4; };
     long long off = 0;
     int ldmax = 0;
@@ -1563,7 +1846,7 @@ size_t plan_few(const agx_ppo_graph *net, GArgs &a) {
     a.lds_floats = (off + 3) & ~3ll;
     a.ws_part = 0;  // no global activation scratch
     const size_t bytes = (size_t)a.lds_floats * 4;
-    return bytes <= few_lds_budget<GAUSS>() ? bytes : 0;
+    return bytes <= few_lds_budget<HEAD>() ? bytes : 0;
 }
 // How a learn() runs, chosen per call (the workspace query makes the same
 // choice): the few-row partnered form when a minibatch splits into at most
@@ -1577,7 +1860,7 @@ struct Split {
     bool few = false;
     size_t dyn = 0;  // dynamic LDS bytes (few-row form)
 };
-template <bool GAUSS>
+template <Head HEAD>
 Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
     Split sp;
     int rows = 16;
@@ -1592,8 +1875,8 @@ Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
     if (k > cap) k = cap;
     if (few_ok && k > 1 && (batch + k - 1) / k <= kFR) {
         GArgs a{};
-        const size_t dyn = plan_few<GAUSS>(net, a);
-        if (dyn && (int64_t)sp.Q * k <= (int64_t)part_occupancy<true, GAUSS>(dyn) * cus) {
+        const size_t dyn = plan_few<HEAD>(net, a);
+        if (dyn && (int64_t)sp.Q * k <= (int64_t)part_occupancy<true, HEAD>(dyn) * cus) {
             sp.few = true;
             sp.dyn = dyn;
             sp.K = k;
@@ -1601,8 +1884,8 @@ Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
             return sp;
         }
     }
-    while (k > 1 && (int64_t)sp.Q * k > (int64_t)part_occupancy<false, GAUSS>(0) * cus) --k;
-    if (k > 1 && (int64_t)P * k > (int64_t)part_occupancy<false, GAUSS>(0) * cus) k = 1;
+    while (k > 1 && (int64_t)sp.Q * k > (int64_t)part_occupancy<false, HEAD>(0) * cus) --k;
+    if (k > 1 && (int64_t)P * k > (int64_t)part_occupancy<false, HEAD>(0) * cus) k = 1;
     sp.K = k < 1 ? 1 : k;
     sp.R = (int)((batch + sp.K - 1) / sp.K);
     return sp;
@@ -1665,6 +1948,88 @@ __global__ void ppo_gauss_gather_kernel(const float *__restrict__ obs, const flo
     gr[3 * S + j] = old_v[sp];
 }
 
+// ppo_gather_kernel (learner.hip) for a multi-categorical head: the rollout's
+// int64 actions [P][S][K] packed into one target word per row (bit off_k + a_k
+// set for every component, a_k clamped into [0, n_k): never a bit outside the
+// component) and the flat masks [P][S][L] into the categorical gather's word
+// (bit j = logit j legal), both in minibatch order; the observations, the
+// advantage normalisation, the rollout rows, the counters and the permutation
+// check as there.
+__global__ void ppo_multi_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
+                                        const float *__restrict__ old_logp, const float *__restrict__ adv,
+                                        const float *__restrict__ ret, const float *__restrict__ old_v,
+                                        const double *__restrict__ adv_stats, const long long *__restrict__ perms,
+                                        const unsigned char *__restrict__ masks, const agx_multi_head head, int L,
+                                        long long S, int D, int P, float *__restrict__ gobs,
+                                        unsigned *__restrict__ gtgt, unsigned *__restrict__ gmask,
+                                        float *__restrict__ grow, unsigned *__restrict__ counters, int ncounters,
+                                        const int *__restrict__ epochs_p, unsigned *__restrict__ err) {
+    const int ep = blockIdx.y;  // e * P + p
+    const int p = ep % P;
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.y == 0)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncounters; i += gridDim.x * blockDim.x)
+            counters[i] = 0u;
+    if (j >= S) return;
+    if (epochs_p && ep / P >= epochs_p[p]) return;
+    long long src = perms[(size_t)ep * S + j];
+    if (src < 0 || src >= S) {
+        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        src = 0;
+    }
+    const size_t sp = (size_t)p * S + src, dst = (size_t)ep * S + j;
+    for (int d = 0; d < D; ++d) gobs[dst * D + d] = obs[sp * D + d];
+    const int K = head.K;
+    unsigned tgt = 0;
+    int off = 0;
+    for (int k = 0; k < K; ++k) {
+        const int n = head.nvec[k];
+        long long a = act[sp * K + k];
+        a = a < 0 ? 0 : (a >= n ? n - 1 : a);
+        tgt |= 1u << (off + (int)a);
+        off += n;
+    }
+    gtgt[dst] = tgt;
+    if (masks) {  // [P][S][L] u8 -> one bit per logit
+        unsigned bits = 0;
+        for (int a = 0; a < L; ++a) bits |= (masks[sp * L + a] != 0 ? 1u : 0u) << a;
+        gmask[dst] = bits;
+    }
+    float *gr = grow + (size_t)ep * 4 * S;
+    double a = adv[sp];
+    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
+    gr[j] = old_logp[sp];
+    gr[S + j] = (float)a;
+    gr[2 * S + j] = ret[sp];
+    gr[3 * S + j] = old_v[sp];
+}
+
+// A head the multi-categorical learner takes: a layer list agx_ppo_graph_check
+// admits, K >= 1 components of n_k >= 1 choices, sum n_k == net->n_actions.
+// -> the head with the components past K zeroed (the kernels never read them)
+int multi_check(const char *who, const agx_ppo_graph *net, const agx_multi_head &h, agx_multi_head *out = nullptr) {
+    GArgs a{};
+    AGX_REQUIRE(net, "%s: null graph", who);
+    const int rc = plan_graph(net, 1, a);
+    if (rc != AGX_OK) return rc;
+    AGX_REQUIRE(h.K >= 1 && h.K <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d components (1..%d)", who, h.K,
+                AGX_PPO_GRAPH_MAX_ACTIONS);
+    int L = 0;
+    for (int k = 0; k < h.K; ++k) {
+        AGX_REQUIRE(h.nvec[k] >= 1 && h.nvec[k] <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: component %d has %d choices (1..%d)",
+                    who, k, h.nvec[k], AGX_PPO_GRAPH_MAX_ACTIONS);
+        L += h.nvec[k];
+    }
+    AGX_REQUIRE(L <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d logits (1..%d)", who, L, AGX_PPO_GRAPH_MAX_ACTIONS);
+    AGX_REQUIRE(L == net->n_actions, "%s: nvec sums to %d, the actor's output has %d logits", who, L, net->n_actions);
+    if (out) {
+        *out = agx_multi_head{};
+        out->K = h.K;
+        for (int k = 0; k < h.K; ++k) out->nvec[k] = h.nvec[k];
+    }
+    return AGX_OK;
+}
+
 // The layers and the A log_std floats at lso tile the parameter row exactly,
 // and log_std lies in the actor clip group [0, critic_start).
 int gauss_check(const agx_ppo_graph *net, int64_t lso) {
@@ -1709,18 +2074,18 @@ int gauss_check(const agx_ppo_graph *net, int64_t lso) {
     return AGX_OK;
 }
 
-template <bool GAUSS>
+template <Head HEAD>
 size_t learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S, int64_t epochs, int64_t batch) {
     GArgs a{};
     if (P <= 0 || S <= 0 || epochs <= 0 || batch <= 0) return 0;
     const int64_t bb = batch < S ? batch : S;
-    const int extra = GAUSS ? net->n_actions : 0, aw = GAUSS ? net->n_actions : 1;
+    const int extra = HEAD == kGauss ? net->n_actions : 0, aw = HEAD == kGauss ? net->n_actions : 1;
     if (plan_graph(net, bb, a, extra) != AGX_OK) return 0;
     size_t total = graph_ws(a, P, S, epochs, aw).total;
-    const Split sp = graph_split<GAUSS>(net, P, bb);
+    const Split sp = graph_split<HEAD>(net, P, bb);
     if (sp.K > 1) {  // room for either kernel: the split may change with the call's batch
         GArgs ap{};
-        if (sp.few ? !plan_few<GAUSS>(net, ap) : plan_graph(net, sp.R, ap, extra) != AGX_OK) return 0;
+        if (sp.few ? !plan_few<HEAD>(net, ap) : plan_graph(net, sp.R, ap, extra) != AGX_OK) return 0;
         const size_t t = part_ws(ap, P, S, epochs, sp.K, aw).total;
         total = t > total ? t : total;
     }
@@ -1732,11 +2097,12 @@ long long *&g_graph_stamps() {
     return p;
 }
 
-// agx_ppo_learn_graph (GAUSS: agx_ppo_learn_gauss_graph, log_std at lso,
-// validated by the caller); `what` names the entry point in errors
-template <bool GAUSS>
+// agx_ppo_learn_graph (kGauss: agx_ppo_learn_gauss_graph, log_std at lso;
+// kMulti: agx_ppo_learn_multi_graph, the components of `head`; both validated
+// by the caller); `what` names the entry point in errors
+template <Head HEAD>
 int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const agx_ppo_learn_args *x,
-                void *workspace, void *stream) {
+                void *workspace, void *stream, const agx_multi_head *head = nullptr) {
     AGX_REQUIRE(x->params && x->exp_avg && x->exp_avg_sq && x->adam_step && x->lr && x->obs && x->actions &&
                     x->old_logp && x->adv && x->ret && x->old_value && x->perms,
                 "%s: null pointer", what);
@@ -1745,14 +2111,18 @@ int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const
                 "%s: bad sizes P=%lld S=%lld epochs=%lld batch=%lld", what, (long long)P, (long long)S,
                 (long long)epochs, (long long)batch);
     const int64_t bb = batch < S ? batch : S;
-    const Split sp = graph_split<GAUSS>(net, P, bb);
+    const Split sp = graph_split<HEAD>(net, P, bb);
     const int K = sp.K, R = sp.R, Q = sp.Q;
     GArgs a{};
-    const int extra = GAUSS ? net->n_actions : 0, aw = GAUSS ? net->n_actions : 1;
+    const int extra = HEAD == kGauss ? net->n_actions : 0, aw = HEAD == kGauss ? net->n_actions : 1;
     const int rc = plan_graph(net, K > 1 ? R : bb, a, extra);
     if (rc != AGX_OK) return rc;
-    if (sp.few) AGX_REQUIRE(plan_few<GAUSS>(net, a) == sp.dyn, "%s: few-row plan changed", what);
+    if (sp.few) AGX_REQUIRE(plan_few<HEAD>(net, a) == sp.dyn, "%s: few-row plan changed", what);
     a.lso = lso;
+    if constexpr (HEAD == kMulti) {
+        a.mk = head->K;
+        for (int k = 0; k < head->K; ++k) a.mn[k >> 2] |= (unsigned)head->nvec[k] << (8 * (k & 3));
+    }
     char *ws = static_cast<char *>(workspace);
     hipStream_t s = as_stream(stream);
     size_t o_gobs, o_gact, o_gmask, o_grow;
@@ -1774,11 +2144,18 @@ int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const
     unsigned *gmask = x->action_masks ? reinterpret_cast<unsigned *>(ws + o_gmask) : nullptr;
     float *grow = reinterpret_cast<float *>(ws + o_grow);
     dim3 ggrid((unsigned)ceil_div(S, 256), (unsigned)(epochs * P));
-    if constexpr (GAUSS)
+    if constexpr (HEAD == kGauss)
         ppo_gauss_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const float *>(x->actions), x->old_logp,
                                                       x->adv, x->ret, x->old_value, x->adv_stats,
                                                       reinterpret_cast<const long long *>(x->perms), a.A, S, a.D,
                                                       (int)P, gobs, reinterpret_cast<float *>(gact), grow, counters,
+                                                      ncounters, x->epochs_per_agent, x->error_word);
+    else if constexpr (HEAD == kMulti)
+        ppo_multi_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
+                                                      x->adv, x->ret, x->old_value, x->adv_stats,
+                                                      reinterpret_cast<const long long *>(x->perms), x->action_masks,
+                                                      *head, a.A, S, a.D, (int)P, gobs,
+                                                      reinterpret_cast<unsigned *>(gact), gmask, grow, counters,
                                                       ncounters, x->epochs_per_agent, x->error_word);
     else
         ppo_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
@@ -1838,11 +2215,11 @@ int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const
         }
         AGX_REQUIRE((int64_t)Q * K <= 65535, "%s: too many workgroups", what);
         if (sp.few)
-            ppo_learn_graph_part_kernel<true, GAUSS><<<(unsigned)(Q * K), kGT, sp.dyn, s>>>(a);
+            ppo_learn_graph_part_kernel<true, HEAD><<<(unsigned)(Q * K), kGT, sp.dyn, s>>>(a);
         else
-            ppo_learn_graph_part_kernel<false, GAUSS><<<(unsigned)(Q * K), kGT, 0, s>>>(a);
+            ppo_learn_graph_part_kernel<false, HEAD><<<(unsigned)(Q * K), kGT, 0, s>>>(a);
     } else {
-        ppo_learn_graph_kernel<GAUSS><<<(unsigned)P, kGT, 0, s>>>(a);
+        ppo_learn_graph_kernel<HEAD><<<(unsigned)P, kGT, 0, s>>>(a);
     }
     return check_launch(what);
 }
@@ -1864,13 +2241,13 @@ extern "C" int agx_ppo_graph_check(const agx_ppo_graph *net) {
 
 extern "C" size_t agx_ppo_learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S,
                                                       int64_t epochs, int64_t batch) {
-    return learn_graph_workspace_bytes<false>(net, P, S, epochs, batch);
+    return learn_graph_workspace_bytes<kCat>(net, P, S, epochs, batch);
 }
 
 extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn_args *x, void *workspace,
                                    void *stream) {
     AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_graph: null net / args / workspace");
-    return learn_graph<false>("agx_ppo_learn_graph", net, -1, x, workspace, stream);
+    return learn_graph<kCat>("agx_ppo_learn_graph", net, -1, x, workspace, stream);
 }
 
 extern "C" int agx_ppo_gauss_graph_check(const agx_ppo_graph *net, int64_t log_std_off) {
@@ -1880,7 +2257,7 @@ extern "C" int agx_ppo_gauss_graph_check(const agx_ppo_graph *net, int64_t log_s
 extern "C" size_t agx_ppo_learn_gauss_graph_workspace_bytes(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
                                                             int64_t S, int64_t epochs, int64_t batch) {
     if (gauss_check(net, log_std_off) != AGX_OK) return 0;
-    return learn_graph_workspace_bytes<true>(net, P, S, epochs, batch);
+    return learn_graph_workspace_bytes<kGauss>(net, P, S, epochs, batch);
 }
 
 extern "C" int agx_ppo_learn_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, const agx_ppo_learn_args *x,
@@ -1889,5 +2266,24 @@ extern "C" int agx_ppo_learn_gauss_graph(const agx_ppo_graph *net, int64_t log_s
     const int rc = gauss_check(net, log_std_off);
     if (rc != AGX_OK) return rc;
     AGX_REQUIRE(!x->action_masks, "agx_ppo_learn_gauss_graph: action masks do not apply to a Gaussian head");
-    return learn_graph<true>("agx_ppo_learn_gauss_graph", net, log_std_off, x, workspace, stream);
+    return learn_graph<kGauss>("agx_ppo_learn_gauss_graph", net, log_std_off, x, workspace, stream);
+}
+
+extern "C" int agx_ppo_multi_graph_check(const agx_ppo_graph *net, agx_multi_head head) {
+    return multi_check("agx_ppo_multi_graph_check", net, head);
+}
+
+extern "C" size_t agx_ppo_learn_multi_graph_workspace_bytes(const agx_ppo_graph *net, agx_multi_head head, int64_t P,
+                                                            int64_t S, int64_t epochs, int64_t batch) {
+    if (multi_check("agx_ppo_learn_multi_graph_workspace_bytes", net, head) != AGX_OK) return 0;
+    return learn_graph_workspace_bytes<kMulti>(net, P, S, epochs, batch);
+}
+
+extern "C" int agx_ppo_learn_multi_graph(const agx_ppo_graph *net, agx_multi_head head, const agx_ppo_learn_args *x,
+                                         void *workspace, void *stream) {
+    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_multi_graph: null net / args / workspace");
+    agx_multi_head hd;
+    const int rc = multi_check("agx_ppo_learn_multi_graph", net, head, &hd);
+    if (rc != AGX_OK) return rc;
+    return learn_graph<kMulti>("agx_ppo_learn_multi_graph", net, -1, x, workspace, stream, &hd);
 }

@@ -71,6 +71,10 @@ struct GArgs {
     const unsigned *skip;
     int dbg;  // diagnostic phase skips (AGX_GRAPH_DEBUG; timing attribution only, results wrong)
     long long lso;  // Gaussian head: the A log_std floats in the parameter row (gact: float [..][A])
+    // multi-categorical head (agx_multi.h): mk components, component k's size in byte k & 3 of
+    // mn[k >> 2] (gact: one target word per row, bit off_k + a_k set for every component)
+    int mk;
+    unsigned mn[AGX_PPO_GRAPH_MAX_ACTIONS / 4];
 };
 
 // C[M x N] = A[M x K] . B[N x K]^T, both operands contiguous along k (the

@@ -589,7 +589,8 @@ class PopulationEngine:
                                 update_epochs=max(s.update_epochs for s in st), target_kl=t.target_kl,
                                 device=self.device, fused=t.fused, perm_source=t.perm_source,
                                 action_masks=t.use_action_masks, global_pop_size=t.global_P, seed_base=t.seed_base,
-                                agent_ids=[self.rank * self.P + j for j in slots], init_params=False)
+                                agent_ids=[self.rank * self.P + j for j in slots], init_params=False,
+                                multi_fused=t.multi_fused)
             n = spec.n_params
             with torch.no_grad():
                 for r, s in enumerate(st):

@@ -1,8 +1,9 @@
 """Host side of the fused PPO learners: agx_ppo_learn (learner.hip, the
 compiled network shapes), agx_ppo_learn_graph (graph_learner.hip, any MLP
 actor-critic as a runtime layer list: the shapes architecture mutations
-produce) and agx_ppo_learn_gauss_graph (the same with a Gaussian head: Box
-action spaces)."""
+produce), agx_ppo_learn_gauss_graph (the same with a Gaussian head: Box
+action spaces) and agx_ppo_learn_multi_graph (the same with a multi-categorical
+head: MultiDiscrete action spaces)."""
 
 from __future__ import annotations
 
@@ -261,9 +262,34 @@ class GaussGraphLearner(GraphLearner):
         self.name = "agx_ppo_learn_gauss_graph"
 
 
+class MultiGraphLearner(GraphLearner):
+    """agx_ppo_learn_multi_graph: GraphLearner for a MultiDiscrete population
+    (the actor output is the L = sum(nvec) logits, ``pop.multi_head()`` passed
+    by value; int64 actions [.., K], flat masks [.., L])."""
+
+    def __init__(self, pop):
+        self.desc = pop.multi_learn_descriptor()
+        if self.desc is None:
+            raise _lib.AgxError("network outside the multi-categorical graph learner's coverage")
+        lib = _lib.load()
+        self.batch_ws = pop.split_batch
+        self.head = pop.multi_head()
+        nbytes = lib.agx_ppo_learn_multi_graph_workspace_bytes(ctypes.byref(self.desc), self.head, pop.P, pop.S,
+                                                               pop.update_epochs, self.batch_ws)
+        if nbytes == 0:
+            raise _lib.AgxError(f"agx_ppo_learn_multi_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=pop.device)
+        self._outputs(pop)
+        multi = lib.agx_ppo_learn_multi_graph
+        self.fn = lambda desc, args, ws, stream: multi(desc, self.head, args, ws, stream)
+        self.name = "agx_ppo_learn_multi_graph"
+
+
 def make_learner(pop) -> FusedLearner:
     if pop.gaussian:
         return GaussGraphLearner(pop)
+    if pop.multidiscrete:
+        return MultiGraphLearner(pop)
     return FusedLearner(pop) if pop.fused_descriptor() is not None else GraphLearner(pop)
 
 

@@ -299,7 +299,8 @@ class MultiDiscreteActorCriticSpec(ActorCriticSpec):
     categorical spec with n = L; there are no extra parameters.  The categorical
     kernels (agx_ppo_learn, agx_ppo_learn_graph, agx_ppo_act, the persistent
     rollout and evaluation) never see this spec, K = 1 included: the policy
-    step is agx_ppo_act_multi_graph over ``multi_descriptor()``."""
+    step is agx_ppo_act_multi_graph over ``multi_descriptor()`` and the fused
+    learner agx_ppo_learn_multi_graph over ``multi_learn_descriptor()``."""
 
     nvec: tuple = ()
 
@@ -336,6 +337,22 @@ class MultiDiscreteActorCriticSpec(ActorCriticSpec):
         d = layer_list(self)
         lib = _lib.load(require_gpu=False)  # pure host-side validation
         if d is None or lib.agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
+            return None
+        return d
+
+    def multi_learn_descriptor(self):
+        """agx_ppo_graph of the networks for agx_ppo_learn_multi_graph (with
+        ``multi_head()`` as its head), or None when the fused
+        multi-categorical learner does not take the layer list: then the
+        autograd learner runs."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+
+        d = layer_list(self)
+        lib = _lib.load(require_gpu=False)  # pure host-side validation
+        if d is None or lib.agx_ppo_multi_graph_check(ctypes.byref(d), self.multi_head()) != 0:
             return None
         return d
 

@@ -39,10 +39,15 @@ take, on the autograd path with the fused Gaussian loss kernel
 (agx_ppo_gauss_loss_fwd_bwd).  The categorical kernels never see it.
 
 A MultiDiscrete spec (nets.MultiDiscreteActorCriticSpec) stores int64 actions
-(P, T, N, K) and flat masks (P, T, N, L), acts through agx_ppo_act_multi_graph
-and learns on the ``fused=False`` path with the fused multi-categorical loss
-kernel (agx_ppo_multi_loss_fwd_bwd); the categorical kernels never see it
-either, K = 1 included.
+(P, T, N, K) and flat masks (P, T, N, L) and acts through
+agx_ppo_act_multi_graph; the categorical kernels never see it either, K = 1
+included.  By default it learns on the autograd path with the fused
+multi-categorical loss kernel (agx_ppo_multi_loss_fwd_bwd).  Built with
+``multi_fused=True``, or with AGX_MULTI_FUSED=1 in the environment, it learns
+through agx_ppo_learn_multi_graph (the runtime-shape learner with a
+multi-categorical head) instead; ``fused=False`` or a layer list that learner
+does not take keeps the autograd path whatever the switch says.  The switch is
+opt-in for now: the default build of such a population behaves as before.
 """
 
 from __future__ import annotations
@@ -132,7 +137,7 @@ class PPOPopulation:
                  batch_size=128, lr=1e-3, gamma=0.99, gae_lambda=0.95, clip_coef=0.2, ent_coef=0.01,
                  vf_coef=0.5, max_grad_norm=0.5, update_epochs=4, target_kl=None, seeds=None,
                  device="cuda", fused=True, perm_source="numpy", action_masks=False, agent_offset=0,
-                 global_pop_size=None, seed_base=None, agent_ids=None, init_params=True):
+                 global_pop_size=None, seed_base=None, agent_ids=None, init_params=True, multi_fused=False):
         self.spec = spec
         # a Box action space: float actions [.., A], the Gaussian policy step and loss (agx_gauss.h)
         self.gaussian = getattr(spec, "head", "categorical") == "gaussian"
@@ -201,6 +206,9 @@ class PPOPopulation:
         self.hp_ent_d = torch.full((self.P,), self.ent_coef, dtype=torch.float32, device=self.device)
         self._hetero = False
         self.fused = fused
+        # a MultiDiscrete population learns on agx_ppo_learn_multi_graph only when asked to
+        # (this keyword, or AGX_MULTI_FUSED=1 when the descriptor is first wanted)
+        self.multi_fused = bool(multi_fused)
         self.act_seed = (seed_base * 0x9E3779B97F4A7C15 + 0x5851F42D) & 0xFFFFFFFFFFFFFFFF
         # every global agent's update_epochs (the shuffles each draws; ranks
         # refresh the other shards' entries after a mutation)
@@ -212,6 +220,7 @@ class PPOPopulation:
         self._edesc = None
         self._gauss = None
         self._glearn = None
+        self._mlearn = None
         self._multi = None
         self._mhead = None
         self._alloc_rollout()
@@ -383,9 +392,23 @@ class PPOPopulation:
             self._glearn = self.spec.gauss_learn_descriptor() or False
         return self._glearn or None
 
+    def multi_learn_descriptor(self):
+        """agx_ppo_graph of a MultiDiscrete population's networks for the
+        fused learner (agx_ppo_learn_multi_graph, ``multi_head()`` by value);
+        None: not a MultiDiscrete population, ``fused`` off, the switch off
+        (neither ``multi_fused=True`` nor AGX_MULTI_FUSED=1), or a layer list
+        agx_ppo_multi_graph_check rejects — then the autograd learner runs."""
+        if (not self.multidiscrete or not self.fused
+                or not (self.multi_fused or os.environ.get("AGX_MULTI_FUSED", "0") == "1")):
+            return None
+        if self._mlearn is None:
+            self._mlearn = self.spec.multi_learn_descriptor() or False
+        return self._mlearn or None
+
     def _fused_learner(self) -> bool:
-        """True when learn() runs a fused HIP learner (either head)."""
-        return self.learn_descriptor() is not None or self.gauss_learn_descriptor() is not None
+        """True when learn() runs a fused HIP learner (any head)."""
+        return (self.learn_descriptor() is not None or self.gauss_learn_descriptor() is not None
+                or self.multi_learn_descriptor() is not None)
 
     @torch.no_grad()
     def act_into(self, t: int, actions_flat: torch.Tensor | None = None) -> None:
@@ -506,7 +529,9 @@ class PPOPopulation:
         learn's permutations right away (the pipelined runner passes False and
         prefetches after pacing the rollout instead)."""
         self.learn_steps += 1
-        if self._fused_learner():  # the categorical kernels, else the Gaussian graph learner
+        # the categorical kernels, else the Gaussian graph learner, else (when switched on)
+        # the multi-categorical graph learner
+        if self._fused_learner():
             from .learner import fused_learn
 
             loss = fused_learn(self, skip_if_set=skip_if_set)
@@ -665,7 +690,8 @@ class PPOPopulation:
         before launching a persistent rollout: between that launch and the
         host pacing it, the device is waiting for this thread, so nothing
         there may wait for the device — and a hipMalloc / hipHostMalloc, or an
-        event sync, can."""
+        event sync, can.  Any fused learner: the categorical kernels, the
+        Gaussian and the multi-categorical graph learner."""
         if self._fused_learner():
             from .learner import learner_stale, make_learner
 

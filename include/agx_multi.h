@@ -1,4 +1,5 @@
-/* PPO for MultiDiscrete action spaces: the multi-categorical policy step and loss.
+/* PPO for MultiDiscrete action spaces: the multi-categorical policy step, loss
+ * and fused learner.
  *
  * A MultiDiscrete space with nvec = (n_0 .. n_{K-1}) has L = sum n_k logits:
  * the actor's output layer has width L (no output activation), and component k
@@ -77,6 +78,38 @@ int agx_ppo_multi_loss_fwd_bwd(const float *logits, const float *value, agx_mult
                                const float *old_value, const int64_t *index, int64_t batch, int64_t num_minibatches,
                                float clip_coef, float vf_coef, float ent_coef, float *g_logits, float *g_value,
                                float *stats, void *stream);
+
+/* PPO.learn for a multi-categorical head: agx_ppo_learn_graph (agx_graph.h)
+ * over the layer list of the categorical network with n_actions = L, the
+ * per-row math that of agx_ppo_multi_loss_fwd_bwd above.
+ *
+ * agx_ppo_multi_graph_check: host-only (no HIP call).  AGX_OK when the learner
+ * takes this net and head; AGX_EINVAL with the reason in agx_last_error
+ * otherwise (anything agx_ppo_graph_check rejects, K < 1, an n_k < 1, sum n_k
+ * != net->n_actions or > AGX_PPO_GRAPH_MAX_ACTIONS).  The workspace query
+ * returns 0 and the learn call returns AGX_EINVAL without a launch on such a
+ * head.
+ *
+ * agx_ppo_learn_multi_graph takes agx_ppo_learn_graph's argument block with
+ * args->actions int64 [P][S][K] and args->action_masks uint8 [P][S][L] or NULL.
+ * The gather packs a row's actions into one 32-bit target word (bit off_k + a_k
+ * for every k) and its mask into one (bit j: logit j legal), so the workspace
+ * is agx_ppo_learn_graph's.  An action outside [0, n_k) is clamped into its
+ * component (defined behaviour, as in the loss kernel above): the learn equals
+ * the learn of the clamped rollout bit for bit and sets no error.  Per-agent
+ * batch / epochs / ent_coef, target_kl, skip_if_set, loss_out / kl_out /
+ * epochs_out, error_word (AGX_LEARN_ERR_PERM included) and adam_step behave as
+ * in agx_ppo_learn_graph; so do the forms the call picks between
+ * (AGX_GRAPH_FEW, AGX_GRAPH_ROWS, AGX_GRAPH_SPLIT), AGX_GRAPH_DEBUG and the
+ * fixed summation order: no atomics in the gradient path, equal bits on every
+ * run, and an agent's update does not depend on which other agents share the
+ * launch.  With K = 1 the result equals agx_ppo_learn_graph's at n_actions =
+ * n_0 bit for bit. */
+int agx_ppo_multi_graph_check(const agx_ppo_graph *net, agx_multi_head head);
+size_t agx_ppo_learn_multi_graph_workspace_bytes(const agx_ppo_graph *net, agx_multi_head head, int64_t P, int64_t S,
+                                                 int64_t epochs, int64_t batch);
+int agx_ppo_learn_multi_graph(const agx_ppo_graph *net, agx_multi_head head, const agx_ppo_learn_args *args,
+                              void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,13 +7,18 @@
   2. learn() of a MultiDiscrete population on the autograd learner (S = 2048,
      batch 128, 4 epochs) with the fused loss kernel
      (agx_ppo_multi_loss_fwd_bwd), against the same learner with the
-     multi-categorical loss written in plain torch ops.
+     multi-categorical loss written in plain torch ops;
+  3. learn() through the fused multi-categorical learner
+     (agx_ppo_learn_multi_graph, ``multi_fused=True``) at the same shape for
+     nvec = [3, 3] and [2] * 16, against (a) the autograd learner on the same
+     population and (b) agx_ppo_learn_graph on a Discrete population with the
+     same layer list and n_actions = L.
 
 Device-event timing after a warm-up; each figure is the median of REPEATS
 windows, the two versions of a pair alternating inside one process.  Not part
 of bench.py.
 
-Usage:  python tools/multidisc_ppo_time.py [--only policy,learn] [--out FILE.json]
+Usage:  python tools/multidisc_ppo_time.py [--only policy,learn,fused] [--out FILE.json]
 """
 
 from __future__ import annotations
@@ -140,10 +145,51 @@ def learn(P=8, N=128, S=2048, nvec=(3, 3)) -> dict:
             f"({updates} minibatch updates), nvec = {list(nvec)}", "hip_loss": h, "torch_loss": t}
 
 
+def fused_learn(nvec, P=8, N=128, S=2048) -> dict:
+    from agilerl_amd.algorithms.ppo import spec_from_net_config
+    from agilerl_amd.envs import Box, Discrete, MultiDiscrete
+    from agilerl_amd.population.learner import GraphLearner, MultiGraphLearner
+    from agilerl_amd.population.ppo_pop import PPOPopulation
+
+    obs_space = Box(-np.inf, np.inf, (8,))
+    L = int(sum(nvec))
+    kw = dict(learn_step=S, batch_size=128, update_epochs=4)
+    multi = PPOPopulation(spec_from_net_config(obs_space, MultiDiscrete(nvec), None), P, N, multi_fused=True, **kw)
+    cat = PPOPopulation(spec_from_net_config(obs_space, Discrete(L), None), P, N, **kw)
+    for pop in (multi, cat):
+        pop.obs.normal_()
+        for t in range(pop.T):
+            pop.act_into(t)
+        pop.rewards.normal_()
+        pop.finish_rollout(torch.randn(P, N, 8, device="cuda"), torch.zeros(P, N, dtype=torch.uint8, device="cuda"))
+    # the default networks are a compiled shape of agx_ppo_learn: pin the runtime-shape learner
+    cat._fused = GraphLearner(cat)
+
+    def run_torch():
+        multi.fused = False  # multi_learn_descriptor() is None: _learn_torch
+        try:
+            multi.learn()
+        finally:
+            multi.fused = True
+
+    f, c = _pair(multi.learn, cat.learn, calls=20, warmup=5)
+    assert isinstance(multi._fused, MultiGraphLearner) and isinstance(cat._fused, GraphLearner)
+    f2, t = _pair(multi.learn, run_torch, calls=3, warmup=2)
+    multi.check_errors()
+    cat.check_errors()
+    updates = multi.n_updates() // P
+    return {"what": "learn() through the fused multi-categorical learner", "shape": f"{P} agents x {N} envs, S = {S}, "
+            f"batch 128, 4 epochs ({updates} minibatch updates), nvec = {list(nvec)} (K = {len(nvec)}, L = {L}), "
+            "default networks", "agx_ppo_learn_multi_graph": f, "agx_ppo_learn_graph_categorical": c,
+            "ratio_to_categorical": {"of_medians": f["median_ms"] / c["median_ms"],
+                                     "min": f["min_ms"] / c["max_ms"], "max": f["max_ms"] / c["min_ms"]},
+            "agx_ppo_learn_multi_graph_beside_autograd": f2, "autograd_learner": t}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default="policy,learn", help="comma-separated: policy, learn")
+    ap.add_argument("--only", default="policy,learn,fused", help="comma-separated: policy, learn, fused")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/multidisc_ppo_time.py needs the GPU: a CPU run says nothing about these times")
@@ -154,6 +200,8 @@ def main() -> None:
             res += [policy_step(nvec) for nvec in NVECS]
         elif k == "learn":
             res.append(learn())
+        elif k == "fused":
+            res += [fused_learn(nvec) for nvec in ((3, 3), (2,) * 16)]
         else:
             raise SystemExit(f"unknown part {k!r}")
     for r in res:
