@@ -29,7 +29,8 @@ class AgxMultiHead(ctypes.Structure):
     _fields_ = [("K", ctypes.c_int32), ("nvec", ctypes.c_int32 * 32)]
 
 
-# name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h) one-to-one
+# name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
+# agx_bernoulli.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -77,6 +78,14 @@ SIGNATURES = {
     "agx_ppo_multi_graph_check": (_INT, [_P, AgxMultiHead]),
     "agx_ppo_learn_multi_graph_workspace_bytes": (_SZ, [_P, AgxMultiHead, _I, _I, _I, _I]),
     "agx_ppo_learn_multi_graph": (_INT, [_P, AgxMultiHead, _P, _P, _P]),
+    # include/agx_bernoulli.h: PPO for MultiBinary actions
+    "agx_ppo_act_bern_graph_workspace_bytes": (_SZ, [_P, _I, _I]),
+    "agx_ppo_act_bern_graph": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P,
+                                      _P, _P, _I, _P, _P, _P, _P]),
+    "agx_ppo_bern_loss_fwd_bwd": (_INT, [_P, _P, ctypes.c_int32] + [_P] * 7 + [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "agx_ppo_bern_graph_check": (_INT, [_P]),
+    "agx_ppo_learn_bern_graph_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
+    "agx_ppo_learn_bern_graph": (_INT, [_P, _P, _P, _P]),
     "agx_ppo_learn": (_INT, [_P, _P, _P, _P]),
     "agx_ppo_act": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                            _I, _P, _P, _P]),

@@ -10,7 +10,8 @@ tensors, numbers, strings, lists and dicts), so it is written by
 in a checkpoint is executed on load.  Spaces are stored as
 ``{"obs_shape", "n_actions"}`` (a Box action space: ``{"obs_shape",
 "action_low", "action_high"}``, its bounds as flat lists; a MultiDiscrete
-one: ``{"obs_shape", "nvec"}``) for ``load``.
+one: ``{"obs_shape", "nvec"}``; a MultiBinary one: ``{"obs_shape", "n_binary"}``)
+for ``load``.
 
 Checkpoints the reference itself wrote (dill-pickled agents, spaces and
 registries) are read by ``refckpt.read_reference`` — the same weights-only
@@ -52,6 +53,8 @@ def checkpoint_dict(agent, modules: dict[str, dict[str, torch.Tensor]], optimize
         out["spaces"] = {"obs_shape": list(agent.observation_space.shape)}
         if hasattr(agent.action_space, "nvec"):  # MultiDiscrete actions (1-D)
             out["spaces"]["nvec"] = [int(n) for n in agent.action_space.nvec]
+        elif type(agent.action_space).__name__ == "MultiBinary":  # n independent switches (1-D)
+            out["spaces"]["n_binary"] = int(agent.action_space.n)
         elif hasattr(agent.action_space, "n"):
             out["spaces"]["n_actions"] = int(agent.action_space.n)
         else:  # Box actions (1-D)
@@ -97,12 +100,14 @@ def restore_attributes(agent, ckpt: dict) -> None:
 
 
 def spaces(ckpt: dict):
-    from ..envs import Box, Discrete, MultiDiscrete
+    from ..envs import Box, Discrete, MultiBinary, MultiDiscrete
 
     s = ckpt["spaces"]
     obs = Box(-float("inf"), float("inf"), tuple(s["obs_shape"]))
     if "nvec" in s:
         return obs, MultiDiscrete(s["nvec"])
+    if "n_binary" in s:
+        return obs, MultiBinary(s["n_binary"])
     if "n_actions" not in s:
         act = Box(0.0, 0.0, (len(s["action_low"]),))
         act.low[:], act.high[:] = s["action_low"], s["action_high"]

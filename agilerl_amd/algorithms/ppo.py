@@ -1,5 +1,6 @@
 """Drop-in ``PPO`` (agilerl/algorithms/ppo.py:108-1290) for MLP actor-critics
-over Discrete, MultiDiscrete or Box action spaces, backed by the HBM population engine.
+over Discrete, MultiDiscrete, MultiBinary or Box action spaces, backed by the
+HBM population engine.
 
 A ``PPO`` object is a *view* of one row of a :class:`PPOPopulation` (its
 parameters, Adam state and rollout SoA live in HBM, stacked with the other
@@ -12,7 +13,10 @@ Supported: Discrete action spaces (and 1-D Box action spaces of up to 32
 dimensions with vector observations: a diagonal Gaussian with a learned
 ``log_std`` started at ``action_std_init``; and 1-D MultiDiscrete action
 spaces of up to 32 logits in all with vector observations: one categorical
-per component, int64 actions [.., K], flat legal-action masks [.., sum(nvec)]),
+per component, int64 actions [.., K], flat legal-action masks [.., sum(nvec)];
+and 1-D MultiBinary action spaces of up to 32 bits with vector observations:
+one Bernoulli per logit, 0 / 1 actions [.., n] handed to the env and returned
+by ``get_action`` in the space's dtype, flat masks [.., n]),
 Box observations, ``net_config`` with
 ``encoder_config`` / ``head_config`` MLP ``hidden_size`` lists and
 ``latent_dim`` (the reference's defaults: encoder [64, 64] -> latent 32,
@@ -108,15 +112,28 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
     8 / 128 (networks/base.py:191-194); no head_config -> actor head
     MlpNetConfig [32] (networks/actors.py:300-303), critic head [16]
     (ppo.py:292-300)."""
-    if type(action_space).__name__ == "MultiBinary":
-        raise NotImplementedError("agx PPO: MultiBinary action spaces are not supported")
-    multi = hasattr(action_space, "nvec")
-    box = not multi and _box_action_space(action_space)
-    if not hasattr(action_space, "n") and not box and not multi:
-        raise NotImplementedError("agx PPO supports Discrete, MultiDiscrete and Box action spaces")
+    binary = type(action_space).__name__ == "MultiBinary"
+    multi = not binary and hasattr(action_space, "nvec")
+    box = not binary and not multi and _box_action_space(action_space)
+    if not hasattr(action_space, "n") and not box and not multi and not binary:
+        raise NotImplementedError("agx PPO supports Discrete, MultiDiscrete, MultiBinary and Box action spaces")
     net_config = dict(net_config or {})
     from ..networks.base import is_image_space
 
+    if binary:
+        # StochasticActor over a MultiBinary space (networks/actors.py:268): n Bernoulli logits.
+        # Duck-typed as the other spaces: an integer n, shape == (n,) and a dtype (what the env
+        # is handed its 0 / 1 actions in)
+        nb = getattr(action_space, "n", None)
+        if (isinstance(nb, bool) or not isinstance(nb, (int, np.integer))
+                or tuple(getattr(action_space, "shape", ())) != (int(nb),)
+                or getattr(action_space, "dtype", None) is None):
+            raise NotImplementedError("agx PPO: MultiBinary action spaces are 1-D: an integer n, shape (n,) and a "
+                                      f"dtype (got n = {nb!r})")
+        if not 1 <= int(nb) <= 32:
+            raise NotImplementedError(f"agx PPO: MultiBinary actions of 1..32 bits (got n = {int(nb)})")
+        if is_image_space(observation_space):
+            raise NotImplementedError("agx PPO: MultiBinary action spaces with image observations")
     nvec = None
     if multi:
         # StochasticActor over a MultiDiscrete space (networks/actors.py:268): sum(nvec) logits
@@ -177,6 +194,11 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
         from ..population.nets import MultiDiscreteActorCriticSpec
 
         return MultiDiscreteActorCriticSpec(n_actions=sum(nvec), nvec=nvec, **kw)
+    if binary:
+        from ..population.nets import MultiBinaryActorCriticSpec
+
+        return MultiBinaryActorCriticSpec(n_actions=int(action_space.n),
+                                          action_dtype=np.dtype(action_space.dtype).name, **kw)
     return ActorCriticSpec(n_actions=int(action_space.n), **kw)
 
 
@@ -471,6 +493,8 @@ class PPO:
             return self._get_action_gauss(o, action_mask)
         if pop.multidiscrete:
             return self._get_action_multi(o, mask)
+        if pop.multibinary:
+            return self._get_action_bern(o, mask)
         out = dict(actions=torch.empty(n, dtype=torch.int64, device=self.device),
                    log_probs=torch.empty(n, device=self.device), values=torch.empty(n, device=self.device),
                    entropy=torch.empty(n, device=self.device))
@@ -556,6 +580,28 @@ class PPO:
                             mask=mask, actions=actions, log_probs=logp, values=value, entropy=ent)
         return tuple(t.cpu().numpy() for t in (actions, logp, ent, value))
 
+    def _get_action_bern(self, o: torch.Tensor, mask):
+        """get_action of a MultiBinary policy: one agx_ppo_act_bern_graph
+        launch on this agent's row -> 0 / 1 actions [n, bits] in the space's
+        dtype; ``mask``: the flat uint8 mask [n, bits] or None."""
+        from ..kernels import ppo_act_bern_graph
+
+        pop = self.population
+        n, nb = o.shape[0], pop.spec.n_actions
+        gdesc = pop.bern_descriptor()
+        self._counter += 1
+        ws = getattr(self, "_act_graph_ws", None)
+        if ws is None or ws[0] is not gdesc or ws[1] < n:
+            nbytes = _lib.load().agx_ppo_act_bern_graph_workspace_bytes(ctypes.byref(gdesc), 1, n)
+            ws = self._act_graph_ws = (gdesc, n, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
+        actions = torch.empty(n, nb, dtype=torch.int64, device=self.device)
+        logp, value, ent = (torch.empty(n, device=self.device) for _ in range(3))
+        ppo_act_bern_graph(gdesc, 1, n, pop.params.data[self.row], o, 0, ws[2], sample=True,
+                           seed=pop.act_seed + 7919 * pop.agent_ids[self.row], counter=(1 << 40) + self._counter,
+                           mask=mask, actions=actions, log_probs=logp, values=value, entropy=ent)
+        a = actions.cpu().numpy().astype(pop.spec.action_dtype)
+        return (a,) + tuple(t.cpu().numpy() for t in (logp, ent, value))
+
     @property
     def rollout_buffer(self) -> "AgentRolloutBuffer":
         """The reference's ``agent.rollout_buffer`` (RolloutBuffer API: reset /
@@ -592,7 +638,7 @@ class PPO:
         and Adam (agx_clip_adam on this agent's row); target_kl checked after
         each epoch on the last minibatch's approx_kl.  -> mean_loss /
         (num_samples * update_epochs)."""
-        from ..population.nets import categorical, gaussian, multi_categorical
+        from ..population.nets import bernoulli_head, categorical, gaussian, multi_categorical
 
         if not experiences:
             raise ValueError("Experiences must be provided when use_rollout_buffer is False")
@@ -631,8 +677,9 @@ class PPO:
             returns = adv + values
         obs_f = obs.reshape(-1, spec.obs_dim)
         multi = pop.multidiscrete  # int64 actions [.., K]
-        act_f = (actions.reshape(-1, spec.n_actions) if gauss else actions.reshape(-1, len(spec.nvec)) if multi
-                 else actions.reshape(-1))
+        binary = pop.multibinary  # int64 0 / 1 actions [.., n]
+        act_f = (actions.reshape(-1, spec.n_actions) if gauss else actions.reshape(-1, pop.act_width)
+                 if multi or binary else actions.reshape(-1))
         lp_f, adv_f = log_probs.reshape(-1), adv.reshape(-1)
         ret_f, val_f = returns.reshape(-1), values.reshape(-1)
         n = obs_f.shape[0]
@@ -655,6 +702,8 @@ class PPO:
                     logp, entropy = gaussian(logits[0], spec.log_std_view(w), act_f[sel])
                 elif multi:
                     logp, entropy = multi_categorical(logits[0], spec.nvec, act_f[sel])
+                elif binary:
+                    logp, entropy = bernoulli_head(logits[0], act_f[sel])
                 else:
                     logp_all, entropy = categorical(logits[0])
                     logp = logp_all.gather(-1, act_f[sel].unsqueeze(-1)).squeeze(-1)
@@ -753,7 +802,7 @@ class AgentRolloutBuffer:
         self._put(p.values[self.row, t], value)
         self._put(p.log_probs[self.row, t], log_prob)
         mask = _kw.get("action_mask")
-        if mask is not None and p.multidiscrete and p.action_masks is not None:  # the flat mask [N, L]
+        if mask is not None and p.vector_int and p.action_masks is not None:  # the flat mask [N, L]
             self._put(p.action_masks[self.row, t], np.asarray(mask) != 0)
         self.pos += 1
         self.full = self.pos == self.capacity

@@ -156,6 +156,10 @@ def _space_shapes(ck: dict) -> dict | None:
         if np.ndim(nvec) != 1:
             return None
         return {"obs_shape": [int(s) for s in shape], "nvec": [int(x) for x in nvec]}
+    if type(act).__name__ == "MultiBinary":  # gymnasium.spaces.MultiBinary: n switches (1-D)
+        if n is None or np.ndim(n) != 0:
+            return None
+        return {"obs_shape": [int(s) for s in shape], "n_binary": int(n)}
     if n is None:  # a Box action space: its bounds
         low, high = act.attr("low"), act.attr("high")
         if low is None or high is None or np.ndim(low) != 1:

@@ -49,8 +49,16 @@
 // (GArgs::mk / mn, by value in the kernel arguments) with the lanes outside the
 // component neutral in row_max / row_sum, as multi_policy.hip's multi_step.
 // For K = 1 the pass runs the categorical pass's float operations in its order.
+//
+// kBern: the Bernoulli head of a MultiBinary action space
+// (include/agx_bernoulli.h).  Again the categorical network at n_actions = n;
+// the gather packs a row's n stored bits into one target word (bit j = a_j != 0)
+// and the loss row pass is elementwise per lane (bern_head.h) with two row sums
+// per row: no component walk, no kernel argument of its own.
+#include "../../include/agx_bernoulli.h"
 #include "../../include/agx_gauss.h"
 #include "../../include/agx_multi.h"
+#include "bern_head.h"
 #include "gauss_head.h"
 #include "graph_net.h"
 #include "ppo_loss_sample.h"
@@ -232,7 +240,7 @@ __device__ __forceinline__ void bwd_rows(const GLay &L, float *base, const float
 // words per wave of the output layers' column partials (colo): 32 logits /
 // means and the value; the Gaussian head adds its 32 log_std (and a pad word)
 // the head of the three learner kernels and their helpers (a compile-time parameter)
-enum Head : int { kCat = 0, kGauss = 1, kMulti = 2 };
+enum Head : int { kCat = 0, kGauss = 1, kMulti = 2, kBern = 3 };
 template <Head HEAD>
 constexpr int kColo = HEAD == kGauss ? 66 : 33;
 
@@ -556,6 +564,120 @@ __device__ __forceinline__ void multi_loss_rows(const GArgs &g, float *base, con
     }
 }
 
+// ---- the Bernoulli head (include/agx_bernoulli.h) --------------------------
+// One row of the Bernoulli pass: the lane's two logits (masked: -1e8; past n:
+// off) and target bits -> the gradients of the lane's logits and of the value
+// and the row's loss / approx_kl terms (bern_head.h's and loss_sample's math, as
+// in agx_ppo_bern_loss_fwd_bwd).  Two row sums, whatever n is.
+struct BernRowOut {
+    float dl0, dl1, dvv, loss, kl;
+};
+__device__ __forceinline__ BernRowOut bern_row_loss(const GArgs &g, const LossCoef &k, bool on0, bool on1, float lg0,
+                                                    float lg1, bool t0, bool t1, float olp, float Ad, float Rt,
+                                                    float ov, float v, float inv_b, float entp) {
+    const BernBit b0 = bern_bit(lg0), b1 = bern_bit(lg1);
+    const float lp = row_sum((on0 ? (t0 ? b0.lp : b0.lq) : 0.f) + (on1 ? (t1 ? b1.lp : b1.lq) : 0.f));
+    const float H = -row_sum((on0 ? bern_neg_entropy(b0) : 0.f) + (on1 ? bern_neg_entropy(b1) : 0.f));
+    float gl, gv;
+    Acc one;
+    loss_sample(lp, olp, Ad, Rt, ov, v, H, k, gl, gv, one);
+    BernRowOut o;
+    o.dl0 = gl * bern_dlogp(b0, t0) + k.g_h * bern_dH(b0);
+    o.dl1 = gl * bern_dlogp(b1, t1) + k.g_h * bern_dH(b1);
+    o.dvv = gv;
+    o.loss = (one.pg + g.vf * 0.5f * one.vl - entp * H) * inv_b;
+    o.kl = one.kl * inv_b;  // approx_kl (ppo.py:899-902)
+    return o;
+}
+
+// The Bernoulli head's loss row pass over `bsz` rows of the general form: the
+// categorical pass's geometry in minibatch_grads (16 lanes per row, bits sub
+// and sub + 16 per lane, four rows per lane group in flight) and its outputs
+// (d(logits) in both layouts, d(value), the output-layer bias column partials
+// in colo, [kGW][33]).  tgt_e: the rows' target words (bit j = a_j != 0).
+__device__ __forceinline__ void bern_loss_rows(const GArgs &g, float *base, const unsigned *tgt_e,
+                                               const unsigned *gmask_e, const float *grow_e, long long s0, int bsz,
+                                               float inv_b, float entp, float *colo, float &lsum, float &klsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, rq = lane >> 4;
+    const int bp = g.bp, A = g.A;
+    const long long S = g.S;
+    const GLay &La = g.L[g.aout];
+    const GLay &Lc = g.L[g.cout];
+    const float *lgp = base + La.yr;
+    const float *vp = base + Lc.yr;
+    float *dla = base + La.dy;
+    float *dlac = base + La.dyc;
+    float *dlv = base + Lc.dy;
+    const int a0 = sub, a1 = sub + 16;
+    const bool on0 = a0 < A, on1 = a1 < A;
+    const LossCoef k = loss_coef(g, inv_b, entp);
+    float cb0 = 0.f, cb1 = 0.f, cbv = 0.f;  // output-layer bias gradients (column partials)
+    constexpr int R = 4;
+    for (int rb = 0; rb < bsz; rb += R * 4 * kGW) {
+        unsigned pbits[R], ptgt[R];
+        float plg0[R], plg1[R], polp[R], pad[R], pret[R], pov[R], pv[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row0 = rb + 4 * wave + rq + 4 * kGW * u;
+            const int row = row0 < bsz ? row0 : 0;
+            pbits[u] = gmask_e ? gmask_e[s0 + row] : 0xffffffffu;
+            plg0[u] = lgp[(size_t)row * A + (on0 ? a0 : 0)];
+            plg1[u] = lgp[(size_t)row * A + (on1 ? a1 : 0)];
+            ptgt[u] = tgt_e[s0 + row];
+            polp[u] = grow_e[s0 + row];
+            pad[u] = grow_e[S + s0 + row];
+            pret[u] = grow_e[2 * S + s0 + row];
+            pov[u] = grow_e[3 * S + s0 + row];
+            pv[u] = vp[row];
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row0 = rb + 4 * wave + rq + 4 * kGW * u;
+            const bool live = row0 < bsz;
+            const int row = live ? row0 : 0;
+            const bool ok0 = (pbits[u] >> a0) & 1u, ok1 = (pbits[u] >> a1) & 1u;
+            const float lg0 = on0 ? (ok0 ? plg0[u] : -1.0e8f) : 0.f;
+            const float lg1 = on1 ? (ok1 ? plg1[u] : -1.0e8f) : 0.f;
+            const bool t0 = (ptgt[u] >> a0) & 1u, t1 = (ptgt[u] >> a1) & 1u;
+            const BernRowOut o =
+                bern_row_loss(g, k, on0, on1, lg0, lg1, t0, t1, polp[u], pad[u], pret[u], pov[u], pv[u], inv_b, entp);
+            if (live) {
+                const float d0 = ok0 ? o.dl0 : 0.f, d1 = ok1 ? o.dl1 : 0.f;
+                if (on0) {
+                    dla[(size_t)row * A + a0] = d0;
+                    dlac[(size_t)a0 * bp + row] = d0;
+                    cb0 += d0;
+                }
+                if (on1) {
+                    dla[(size_t)row * A + a1] = d1;
+                    dlac[(size_t)a1 * bp + row] = d1;
+                    cb1 += d1;
+                }
+                if (sub == 0) {
+                    dlv[row] = o.dvv;
+                    cbv += o.dvv;
+                    lsum += o.loss;
+                    klsum += o.kl;
+                }
+            }
+        }
+    }
+    // bias gradients of the output layers: the wave's four row groups, then
+    // per wave into LDS (the caller sums the waves in order)
+    cb0 += __shfl_xor(cb0, 16, 64);
+    cb0 += __shfl_xor(cb0, 32, 64);
+    cb1 += __shfl_xor(cb1, 16, 64);
+    cb1 += __shfl_xor(cb1, 32, 64);
+    cbv += __shfl_xor(cbv, 16, 64);
+    cbv += __shfl_xor(cbv, 32, 64);
+    if (rq == 0) {
+        colo[wave * 33 + a0] = cb0;
+        colo[wave * 33 + a1] = cb1;
+        if (sub == 0) colo[wave * 33 + 32] = cbv;
+    }
+}
+
 // One minibatch's forward, PPO loss and backward over `bsz` rows (rows
 // s0 .. s0 + bsz - 1 of the epoch's minibatch-ordered rollout, observations at
 // xobs), accumulating the gradient row G (every entry written: dW by GEMM
@@ -565,7 +687,8 @@ __device__ __forceinline__ void multi_loss_rows(const GArgs &g, float *base, con
 // weights live (wb + L.wt).  Shared by the one-workgroup-per-agent learner and
 // the partnered one (each partner over its slice of the rows).
 // kGauss: gact_e holds the rows' float actions [A]; kMulti: the rows' target words
-// (multi_loss_rows); colo has kColo<HEAD> words per wave.
+// (multi_loss_rows); kBern: the rows' target words (bern_loss_rows); colo has
+// kColo<HEAD> words per wave.
 template <Head HEAD>
 __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, const float *wb, const float *pr, float *G,
                                                 const float *xobs, const int *gact_e, const unsigned *gmask_e,
@@ -596,6 +719,10 @@ __device__ __forceinline__ void minibatch_grads(const GArgs &g, float *base, con
         if (!(g.dbg & 8))
             multi_loss_rows(g, base, reinterpret_cast<const unsigned *>(gact_e), gmask_e, grow_e, s0, bsz, inv_b, entp,
                             colo, lsum, klsum);
+    } else if constexpr (HEAD == kBern) {
+        if (!(g.dbg & 8))
+            bern_loss_rows(g, base, reinterpret_cast<const unsigned *>(gact_e), gmask_e, grow_e, s0, bsz, inv_b, entp,
+                           colo, lsum, klsum);
     } else if (!(g.dbg & 8)) {
         const GLay &La = g.L[g.aout];
         const GLay &Lc = g.L[g.cout];
@@ -1238,12 +1365,57 @@ __device__ __forceinline__ void few_multi_loss_rows(const GArgs &g, float *S, co
     }
 }
 
+// The Bernoulli head's loss row pass of the few-row form: the lane group's row
+// (4 wave + rq) of the partner's rk <= 16 rows, bern_loss_rows' math per
+// element, the categorical few-row pass's outputs (d(logits) / d(value) to the
+// output layers' dY tiles, zero past the slice).
+__device__ __forceinline__ void few_bern_loss_rows(const GArgs &g, float *S, const unsigned *tgt_e,
+                                                   const unsigned *gmask_e, const float *grow_e, long long s0, int rk,
+                                                   float inv_b, float entp, float &lsum, float &klsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, rq = lane >> 4;
+    const int row = 4 * wave + rq;
+    const int A = g.A;
+    const long long S_ = g.S;
+    const GLay &La = g.L[g.aout];
+    const GLay &Lc = g.L[g.cout];
+    const float *lgp = S + La.yr + row * La.ld;
+    float *dla = S + La.dy + row * La.ld;
+    const bool live = row < rk;
+    const int rr = live ? row : 0;
+    const int a0 = sub, a1 = sub + 16;
+    const bool on0 = a0 < A, on1 = a1 < A;
+    const unsigned bits = gmask_e ? gmask_e[s0 + rr] : 0xffffffffu;
+    const float plg0 = lgp[on0 ? a0 : 0], plg1 = lgp[on1 ? a1 : 0];
+    const unsigned tgt = tgt_e[s0 + rr];
+    const float olp = grow_e[s0 + rr], Ad = grow_e[S_ + s0 + rr];
+    const float Rt = grow_e[2 * S_ + s0 + rr], ov = grow_e[3 * S_ + s0 + rr];
+    const float v = S[Lc.yr + row * Lc.ld];
+    const bool ok0 = (bits >> a0) & 1u, ok1 = (bits >> a1) & 1u;
+    const float lg0 = on0 ? (ok0 ? plg0 : -1.0e8f) : 0.f;
+    const float lg1 = on1 ? (ok1 ? plg1 : -1.0e8f) : 0.f;
+    const bool t0 = (tgt >> a0) & 1u, t1 = (tgt >> a1) & 1u;
+    const BernRowOut o =
+        bern_row_loss(g, loss_coef(g, inv_b, entp), on0, on1, lg0, lg1, t0, t1, olp, Ad, Rt, ov, v, inv_b, entp);
+    // rows past the slice: a zero gradient (their tiles hold the last minibatch's rows)
+    if (on0) dla[a0] = (live && ok0) ? o.dl0 : 0.f;
+    if (on1) dla[a1] = (live && ok1) ? o.dl1 : 0.f;
+    if (sub == 0) {
+        S[Lc.dy + row * Lc.ld] = live ? o.dvv : 0.f;
+        if (live) {
+            lsum += o.loss;
+            klsum += o.kl;
+        }
+    }
+}
+
 // One update's gradient of a partner's rows (rk <= 16 of them, observations
 // at xobs, rollout rows s0 ..) into the gradient row G, plus the loss /
 // approx_kl partial sums: the few-row counterpart of minibatch_grads, same
 // float operations per element.  S: the LDS tiles (plan_few).
 // kGauss: gact_e holds the rows' float actions [A] (few_gauss_loss_rows); kMulti:
-// the rows' target words (few_multi_loss_rows).
+// the rows' target words (few_multi_loss_rows); kBern: the rows' target words
+// (few_bern_loss_rows).
 template <Head HEAD>
 __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float *pr, const float *wb, float *G,
                                           const float *xobs, const int *gact_e, const unsigned *gmask_e,
@@ -1279,6 +1451,9 @@ __device__ __forceinline__ void few_grads(const GArgs &g, float *S, const float 
     } else if constexpr (HEAD == kMulti) {
         few_multi_loss_rows(g, S, reinterpret_cast<const unsigned *>(gact_e), gmask_e, grow_e, s0, rk, inv_b, entp,
                             lsum, klsum);
+    } else if constexpr (HEAD == kBern) {
+        few_bern_loss_rows(g, S, reinterpret_cast<const unsigned *>(gact_e), gmask_e, grow_e, s0, rk, inv_b, entp,
+                           lsum, klsum);
     } else {
         const GLay &La = g.L[g.aout];
         const GLay &Lc = g.L[g.cout];
@@ -2004,6 +2179,50 @@ __global__ void ppo_multi_gather_kernel(const float *__restrict__ obs, const lon
     gr[3 * S + j] = old_v[sp];
 }
 
+// ppo_multi_gather_kernel for a Bernoulli head: the rollout's int64 actions
+// [P][S][n] packed into one target word per row (bit j = a_j != 0) and the
+// flat masks [P][S][n] into the categorical gather's word; the rest as there.
+__global__ void ppo_bern_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
+                                       const float *__restrict__ old_logp, const float *__restrict__ adv,
+                                       const float *__restrict__ ret, const float *__restrict__ old_v,
+                                       const double *__restrict__ adv_stats, const long long *__restrict__ perms,
+                                       const unsigned char *__restrict__ masks, int n, long long S, int D, int P,
+                                       float *__restrict__ gobs, unsigned *__restrict__ gtgt,
+                                       unsigned *__restrict__ gmask, float *__restrict__ grow,
+                                       unsigned *__restrict__ counters, int ncounters,
+                                       const int *__restrict__ epochs_p, unsigned *__restrict__ err) {
+    const int ep = blockIdx.y;  // e * P + p
+    const int p = ep % P;
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.y == 0)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncounters; i += gridDim.x * blockDim.x)
+            counters[i] = 0u;
+    if (j >= S) return;
+    if (epochs_p && ep / P >= epochs_p[p]) return;
+    long long src = perms[(size_t)ep * S + j];
+    if (src < 0 || src >= S) {
+        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        src = 0;
+    }
+    const size_t sp = (size_t)p * S + src, dst = (size_t)ep * S + j;
+    for (int d = 0; d < D; ++d) gobs[dst * D + d] = obs[sp * D + d];
+    unsigned tgt = 0;
+    for (int a = 0; a < n; ++a) tgt |= (act[sp * n + a] != 0 ? 1u : 0u) << a;
+    gtgt[dst] = tgt;
+    if (masks) {  // [P][S][n] u8 -> one bit per logit
+        unsigned bits = 0;
+        for (int a = 0; a < n; ++a) bits |= (masks[sp * n + a] != 0 ? 1u : 0u) << a;
+        gmask[dst] = bits;
+    }
+    float *gr = grow + (size_t)ep * 4 * S;
+    double a = adv[sp];
+    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
+    gr[j] = old_logp[sp];
+    gr[S + j] = (float)a;
+    gr[2 * S + j] = ret[sp];
+    gr[3 * S + j] = old_v[sp];
+}
+
 // A head the multi-categorical learner takes: a layer list agx_ppo_graph_check
 // admits, K >= 1 components of n_k >= 1 choices, sum n_k == net->n_actions.
 // -> the head with the components past K zeroed (the kernels never read them)
@@ -2099,7 +2318,8 @@ long long *&g_graph_stamps() {
 
 // agx_ppo_learn_graph (kGauss: agx_ppo_learn_gauss_graph, log_std at lso;
 // kMulti: agx_ppo_learn_multi_graph, the components of `head`; both validated
-// by the caller); `what` names the entry point in errors
+// by the caller; kBern: agx_ppo_learn_bern_graph); `what` names the entry point
+// in errors
 template <Head HEAD>
 int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const agx_ppo_learn_args *x,
                 void *workspace, void *stream, const agx_multi_head *head = nullptr) {
@@ -2157,6 +2377,13 @@ int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const
                                                       *head, a.A, S, a.D, (int)P, gobs,
                                                       reinterpret_cast<unsigned *>(gact), gmask, grow, counters,
                                                       ncounters, x->epochs_per_agent, x->error_word);
+    else if constexpr (HEAD == kBern)
+        ppo_bern_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
+                                                     x->adv, x->ret, x->old_value, x->adv_stats,
+                                                     reinterpret_cast<const long long *>(x->perms), x->action_masks,
+                                                     a.A, S, a.D, (int)P, gobs, reinterpret_cast<unsigned *>(gact),
+                                                     gmask, grow, counters, ncounters, x->epochs_per_agent,
+                                                     x->error_word);
     else
         ppo_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
                                                 x->adv, x->ret, x->old_value, x->adv_stats,
@@ -2286,4 +2513,24 @@ extern "C" int agx_ppo_learn_multi_graph(const agx_ppo_graph *net, agx_multi_hea
     const int rc = multi_check("agx_ppo_learn_multi_graph", net, head, &hd);
     if (rc != AGX_OK) return rc;
     return learn_graph<kMulti>("agx_ppo_learn_multi_graph", net, -1, x, workspace, stream, &hd);
+}
+
+extern "C" int agx_ppo_bern_graph_check(const agx_ppo_graph *net) {
+    GArgs a{};
+    AGX_REQUIRE(net, "agx_ppo_bern_graph_check: null graph");
+    return plan_graph(net, 1, a);
+}
+
+extern "C" size_t agx_ppo_learn_bern_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S,
+                                                           int64_t epochs, int64_t batch) {
+    if (agx_ppo_bern_graph_check(net) != AGX_OK) return 0;
+    return learn_graph_workspace_bytes<kBern>(net, P, S, epochs, batch);
+}
+
+extern "C" int agx_ppo_learn_bern_graph(const agx_ppo_graph *net, const agx_ppo_learn_args *x, void *workspace,
+                                        void *stream) {
+    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_bern_graph: null net / args / workspace");
+    const int rc = agx_ppo_bern_graph_check(net);
+    if (rc != AGX_OK) return rc;
+    return learn_graph<kBern>("agx_ppo_learn_bern_graph", net, -1, x, workspace, stream);
 }

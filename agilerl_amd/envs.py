@@ -50,6 +50,18 @@ class MultiDiscrete:
         return (np.random.random_sample(self.nvec.shape) * self.nvec).astype(self.dtype)
 
 
+class MultiBinary:
+    """``n`` independent 0 / 1 switches (gymnasium's ``spaces.MultiBinary``, 1-D)."""
+
+    def __init__(self, n: int):
+        self.n = int(n)
+        self.shape = (self.n,)
+        self.dtype = np.int8
+
+    def sample(self):
+        return np.random.randint(0, 2, self.shape).astype(self.dtype)
+
+
 class Dict:
     """Mapping of named spaces; a plain dict is key-sorted like gymnasium's
     ``spaces.Dict``."""
@@ -86,19 +98,26 @@ class SyntheticVecEnv:
     ``action_dim`` (None: the Discrete env) makes it a continuous-control
     stand-in: actions are ``Box(action_low, action_high, (action_dim,))``.
     ``nvec`` (None: today's env) makes it a factored-control stand-in: actions
-    are ``MultiDiscrete(nvec)``, one row [K] per env."""
+    are ``MultiDiscrete(nvec)``, one row [K] per env.  ``n_binary`` (None: today's
+    env) makes it a binary-switch stand-in: actions are ``MultiBinary(n_binary)``,
+    one row [n] of 0 / 1 per env.  The observation, reward and termination
+    streams of a seed are the same whatever the action space."""
 
     #: the step never touches the GPU (PopulationRunner may pace a persistent rollout)
     agx_device_free = True
 
     def __init__(self, num_envs: int, obs_dim: int = 8, n_actions: int = 4, p_done: float = 1 / 200,
                  seed: int = 0, ring: int = 97, max_episode_steps: int | None = None, action_dim: int | None = None,
-                 action_low: float = -1.0, action_high: float = 1.0, nvec=None):
+                 action_low: float = -1.0, action_high: float = 1.0, nvec=None,
+                 n_binary: int | None = None):
         self.num_envs = int(num_envs)
         self.single_observation_space = Box(-np.inf, np.inf, (obs_dim,))
         if nvec is not None and action_dim is not None:
             raise ValueError("SyntheticVecEnv: nvec (MultiDiscrete) or action_dim (Box), not both")
-        self.single_action_space = MultiDiscrete(nvec) if nvec is not None else \
+        if n_binary is not None and (nvec is not None or action_dim is not None):
+            raise ValueError("SyntheticVecEnv: n_binary (MultiBinary) excludes nvec and action_dim")
+        self.single_action_space = MultiBinary(n_binary) if n_binary is not None else \
+            MultiDiscrete(nvec) if nvec is not None else \
             Discrete(n_actions) if action_dim is None else Box(action_low, action_high, (int(action_dim),))
         self.observation_space = self.single_observation_space
         self.action_space = self.single_action_space

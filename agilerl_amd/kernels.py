@@ -263,6 +263,70 @@ def ppo_multi_loss_fwd_bwd(logits, value, nvec, actions, old_logp, adv, ret, old
     return out[0], out[1], stats
 
 
+def ppo_act_bern_graph(desc, P, N, params, obs, obs_agent_stride, workspace, *, sample, seed, counter, mask=None,
+                       mask_agent_stride=0, actions=None, log_probs=None, values=None, entropy=None,
+                       out_agent_stride=0, actions_flat=None, agent_env_base=None) -> None:
+    """agx_ppo_act_bern_graph: the Bernoulli policy step of P agents x N envs
+    over the layer list ``desc`` (an agx_ppo_graph whose n_actions is the
+    MultiBinary space's n) in one launch.  actions int64 [P, .., n] holding
+    0 / 1 (row r of agent p at (p out_agent_stride + r) n), log_probs / values /
+    entropy with agent stride out_agent_stride, actions_flat int64 [P N n];
+    each may be None.  mask: uint8 [P, .., n] with agent stride
+    mask_agent_stride."""
+    _lib.call("agx_ppo_act_bern_graph", ctypes.byref(desc), int(P), int(N), params.data_ptr(), obs.data_ptr(),
+              int(obs_agent_stride), _lib.ptr(mask), int(mask_agent_stride), 1 if sample else 0, int(seed),
+              int(counter), _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy),
+              int(out_agent_stride), _lib.ptr(actions_flat), _lib.ptr(agent_env_base), workspace.data_ptr(),
+              _lib.stream())
+
+
+def ppo_bern_loss_fwd_bwd(logits, value, actions, old_logp, adv, ret, old_value, batch, clip_coef=0.2, vf_coef=0.5,
+                          ent_coef=0.01, index=None, mask=None, out=None, stats=None, n=None):
+    """The Bernoulli twin of ppo_loss_fwd_bwd (agx_ppo_bern_loss_fwd_bwd):
+    logits [nmb * batch, n] (raw), value [nmb * batch]; actions int64
+    [rows, n] (anything but 0 counts as 1), mask uint8 [rows, n] (1 = legal) or
+    None, and old_logp / adv / ret / old_value [rows] are the rollout, gathered
+    through ``index`` when given.  ``n``: the bit count handed to the kernel
+    (default: the logits' width; the kernel rejects anything outside 1..32).
+    Returns (g_logits, g_value, stats[nmb, 8])."""
+    _need(logits, "logits", _f32)
+    if logits.dim() != 2:
+        raise ValueError("logits: expected [samples, n]")
+    n = logits.shape[1] if n is None else int(n)
+    S = logits.shape[0]
+    if S % batch:
+        raise ValueError(f"samples ({S}) must be a multiple of batch ({batch}); call per minibatch")
+    nmb = S // batch
+    _need(value, "value", _f32)
+    if value.numel() != S:
+        raise ValueError(f"value: expected {S} elements")
+    _need(actions, "actions", _i64)
+    if actions.dim() != 2 or actions.shape[1] != logits.shape[1]:
+        raise ValueError(f"actions: expected [rows, {logits.shape[1]}]")
+    src = actions.shape[0]
+    for t, name in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
+        _need(t, name, _f32)
+        if t.numel() != src:
+            raise ValueError(f"{name}: expected {src} elements")
+    if mask is not None:
+        _need(mask, "mask", torch.uint8, (src, logits.shape[1]))
+    if index is not None:
+        _need(index, "index", _i64)
+        if index.numel() != S:
+            raise ValueError("index: one entry per sample")
+    elif src != S:
+        raise ValueError("without an index the rollout arrays must match logits")
+    if out is None:
+        out = (torch.empty_like(logits), torch.empty_like(value))
+    if stats is None:
+        stats = torch.empty(nmb, 8, dtype=_f32, device=logits.device)
+    _lib.call("agx_ppo_bern_loss_fwd_bwd", logits.data_ptr(), value.data_ptr(), n, actions.data_ptr(),
+              _lib.ptr(mask), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(), old_value.data_ptr(),
+              _lib.ptr(index), int(batch), int(nmb), float(clip_coef), float(vf_coef), float(ent_coef),
+              out[0].data_ptr(), out[1].data_ptr(), stats.data_ptr(), _lib.stream())
+    return out[0], out[1], stats
+
+
 # --------------------------------------------------------------------------- #
 # PER                                                                         #
 # --------------------------------------------------------------------------- #

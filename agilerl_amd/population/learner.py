@@ -285,11 +285,34 @@ class MultiGraphLearner(GraphLearner):
         self.name = "agx_ppo_learn_multi_graph"
 
 
+class BernGraphLearner(GraphLearner):
+    """agx_ppo_learn_bern_graph: GraphLearner for a MultiBinary population (the
+    actor output is the n Bernoulli logits; int64 actions [.., n] holding
+    0 / 1, flat masks [.., n])."""
+
+    def __init__(self, pop):
+        self.desc = pop.bern_learn_descriptor()
+        if self.desc is None:
+            raise _lib.AgxError("network outside the Bernoulli graph learner's coverage")
+        lib = _lib.load()
+        self.batch_ws = pop.split_batch
+        nbytes = lib.agx_ppo_learn_bern_graph_workspace_bytes(ctypes.byref(self.desc), pop.P, pop.S,
+                                                              pop.update_epochs, self.batch_ws)
+        if nbytes == 0:
+            raise _lib.AgxError(f"agx_ppo_learn_bern_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=pop.device)
+        self._outputs(pop)
+        self.fn = lib.agx_ppo_learn_bern_graph
+        self.name = "agx_ppo_learn_bern_graph"
+
+
 def make_learner(pop) -> FusedLearner:
     if pop.gaussian:
         return GaussGraphLearner(pop)
     if pop.multidiscrete:
         return MultiGraphLearner(pop)
+    if pop.multibinary:
+        return BernGraphLearner(pop)
     return FusedLearner(pop) if pop.fused_descriptor() is not None else GraphLearner(pop)
 
 
@@ -401,3 +424,49 @@ def policy_step_multi(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_strid
                         mask_agent_stride=mask_agent_stride, actions=actions, log_probs=log_probs, values=values,
                         entropy=entropy, out_agent_stride=out_agent_stride, actions_flat=actions_flat,
                         agent_env_base=pop.env_base_d)
+
+
+def bern_act_workspace(pop, desc: AgxPPOGraph):
+    """(desc, scratch) of agx_ppo_act_bern_graph for this population, as
+    graph_act_workspace."""
+    ws = getattr(pop, "_act_ws", None)
+    if ws is None or ws[0] is not desc:
+        lib = _lib.load()
+        nbytes = lib.agx_ppo_act_bern_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
+        if nbytes == 0:
+            raise _lib.AgxError(f"agx_ppo_act_bern_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+        ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
+    return ws
+
+
+def policy_step_bern(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
+                     counter: int, actions=None, log_probs=None, values=None, entropy=None,
+                     out_agent_stride: int = 0, actions_flat=None, action_mask=None,
+                     mask_agent_stride: int = 0) -> None:
+    """agx_ppo_act_bern_graph over all P agents x N envs: the policy step of a
+    MultiBinary population (one launch), the agents' own Philox streams;
+    int64 actions [.., n] holding 0 / 1, a flat mask [.., n]."""
+    from ..kernels import ppo_act_bern_graph
+
+    ws = bern_act_workspace(pop, desc)
+    ppo_act_bern_graph(desc, pop.P, pop.N, pop.params.data, obs, obs_agent_stride, ws[1], sample=sample,
+                       seed=pop.act_seed, counter=counter, mask=action_mask, mask_agent_stride=mask_agent_stride,
+                       actions=actions, log_probs=log_probs, values=values, entropy=entropy,
+                       out_agent_stride=out_agent_stride, actions_flat=actions_flat, agent_env_base=pop.env_base_d)
+
+
+def policy_step_vector(pop, obs: torch.Tensor, obs_agent_stride: int, **kw) -> None:
+    """The one-launch policy step of a population whose actions are int64
+    vectors: policy_step_multi (MultiDiscrete) or policy_step_bern
+    (MultiBinary) over the population's own descriptor."""
+    if pop.multibinary:
+        policy_step_bern(pop, pop.bern_descriptor(), obs, obs_agent_stride, **kw)
+    else:
+        policy_step_multi(pop, pop.multi_descriptor(), obs, obs_agent_stride, **kw)
+
+
+def vector_act_workspace(pop):
+    """The policy-step scratch of such a population, allocated now."""
+    if pop.multibinary:
+        return bern_act_workspace(pop, pop.bern_descriptor())
+    return multi_act_workspace(pop, pop.multi_descriptor())

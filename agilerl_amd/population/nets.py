@@ -357,6 +357,81 @@ class MultiDiscreteActorCriticSpec(ActorCriticSpec):
         return d
 
 
+@dataclass
+class MultiBinaryActorCriticSpec(ActorCriticSpec):
+    """The actor-critic of a MultiBinary action space (networks/actors.py:268
+    with networks/distributions.py:201-207): one independent Bernoulli per
+    logit of the actor's n outputs.  ``n_actions`` is n, so the layer list, the
+    parameter order and the initial draws are those of the categorical spec
+    with n actions; there are no extra parameters.  The categorical kernels
+    never see this spec: the policy step is agx_ppo_act_bern_graph over
+    ``bern_descriptor()`` and the fused learner agx_ppo_learn_bern_graph over
+    ``bern_learn_descriptor()``.  ``action_dtype``: the space's numpy dtype
+    name, what the env is handed its 0 / 1 actions in."""
+
+    action_dtype: str = "int8"
+
+    head = "multibinary"
+
+    def __post_init__(self) -> None:
+        if not 1 <= int(self.n_actions) <= 32:
+            raise ValueError(f"a MultiBinary head takes 1..32 bits (got {self.n_actions})")
+        super().__post_init__()
+
+    @property
+    def n_components(self) -> int:
+        return self.n_actions
+
+    def shape_key(self) -> tuple:
+        return super().shape_key() + (self.head, self.action_dtype)
+
+    def bern_descriptor(self):
+        """agx_ppo_graph of the networks for agx_ppo_act_bern_graph, or None
+        when the layer list is outside what the kernel takes."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+
+        d = layer_list(self)
+        lib = _lib.load(require_gpu=False)  # pure host-side validation
+        if d is None or lib.agx_ppo_act_bern_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
+            return None
+        return d
+
+    def bern_learn_descriptor(self):
+        """agx_ppo_graph of the networks for agx_ppo_learn_bern_graph, or None
+        when the fused Bernoulli learner does not take the layer list: then
+        the autograd learner runs."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+
+        d = layer_list(self)
+        lib = _lib.load(require_gpu=False)  # pure host-side validation
+        if d is None or lib.agx_ppo_bern_graph_check(ctypes.byref(d)) != 0:
+            return None
+        return d
+
+
+def bernoulli_head(logits: torch.Tensor, action: torch.Tensor, mask: torch.Tensor | None = None):
+    """log-prob of ``action`` [..., n] (anything but 0 counts as 1) and entropy
+    of n independent Bernoullis over ``logits`` [..., n] as
+    ``agilerl/utils/torch_utils.py:348-376`` (illegal logits -> -1e8 first,
+    distributions.py:16-28), in the form of include/agx_bernoulli.h: finite
+    for |logit| up to 1e8.  -> (logp [...], entropy [...])."""
+    if mask is not None:
+        logits = torch.where(mask.bool(), logits, torch.full_like(logits, -1e8))
+    s = torch.log1p(torch.exp(-logits.abs()))
+    log_p = torch.clamp(logits, max=0.0) - s
+    log_q = torch.clamp(-logits, max=0.0) - s
+    logp = torch.where(action != 0, log_p, log_q).sum(-1)
+    p, q = torch.sigmoid(logits), torch.sigmoid(-logits)
+    ent = -(p * torch.log(p + 1e-8) + q * torch.log(q + 1e-8)).sum(-1)
+    return logp, ent
+
+
 def multi_categorical(logits: torch.Tensor, nvec, action: torch.Tensor, mask: torch.Tensor | None = None):
     """log-prob of ``action`` [..., K] and entropy of the K categoricals over
     slices of ``logits`` [..., L] as ``agilerl/utils/torch_utils.py:284-333``

@@ -48,6 +48,15 @@ through agx_ppo_learn_multi_graph (the runtime-shape learner with a
 multi-categorical head) instead; ``fused=False`` or a layer list that learner
 does not take keeps the autograd path whatever the switch says.  The switch is
 opt-in for now: the default build of such a population behaves as before.
+
+A MultiBinary spec (nets.MultiBinaryActorCriticSpec) reuses that storage with
+one column per bit: int64 actions (P, T, N, n) holding 0 / 1 and flat masks
+(P, T, N, n).  It acts through agx_ppo_act_bern_graph and learns through
+agx_ppo_learn_bern_graph (the runtime-shape learner with a Bernoulli head);
+with ``fused=False``, AGX_BERN_FUSED=0 or a layer list that learner does not
+take, on the autograd path with the fused Bernoulli loss kernel
+(agx_ppo_bern_loss_fwd_bwd).  ``vector_int`` is true of both kinds of
+population, ``act_width`` their action columns (K or n).
 """
 
 from __future__ import annotations
@@ -132,7 +141,52 @@ class _PPOMultiLossFn(torch.autograd.Function):
         return (g1.view(sl) * gl, g2.view(sv) * gl) + (None,) * 12
 
 
+class _PPOBernLossFn(torch.autograd.Function):
+    """_PPOLossFn for a Bernoulli head (agx_ppo_bern_loss_fwd_bwd): the masked
+    logits, the log-prob of the stored bits [rows, n], the entropy and the loss
+    in one launch; ``logits`` are the raw network output, and a masked logit
+    gets gradient 0."""
+
+    @staticmethod
+    def forward(ctx, logits, value, actions, masks, old_logp, adv, ret, old_v, gidx, b, clip, vf, ent):
+        n = logits.shape[-1]
+        g1, g2, stats = K.ppo_bern_loss_fwd_bwd(
+            logits.contiguous().view(-1, n), value.contiguous().view(-1), actions, old_logp, adv, ret, old_v,
+            b, clip, vf, ent, index=gidx, mask=masks)
+        ctx.save_for_backward(g1, g2)
+        ctx.shapes = (logits.shape, value.shape)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum(), stats
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        g1, g2 = ctx.saved_tensors
+        sl, sv = ctx.shapes
+        return (g1.view(sl) * gl, g2.view(sv) * gl) + (None,) * 11
+
+
 class PPOPopulation:
+    # a MultiBinary population's descriptors, made on first use (bern_descriptor, bern_learn_descriptor)
+    _bern = None
+    _blearn = None
+
+    @property
+    def multibinary(self) -> bool:
+        """A MultiBinary action space: the MultiDiscrete storage with one column
+        per bit (0 / 1), the Bernoulli policy step, loss and learner
+        (agx_bernoulli.h)."""
+        return getattr(self.spec, "head", "categorical") == "multibinary"
+
+    @property
+    def vector_int(self) -> bool:
+        """int64 action vectors [.., act_width]: MultiDiscrete or MultiBinary."""
+        return self.multidiscrete or self.multibinary
+
+    @property
+    def act_width(self) -> int:
+        """Stored action columns per row: K components, n bits, else 1."""
+        return (len(self.spec.nvec) if self.multidiscrete else self.spec.n_actions if self.multibinary else 1)
+
     def __init__(self, spec: ActorCriticSpec, pop_size: int, num_envs: int, *, learn_step=2048,
                  batch_size=128, lr=1e-3, gamma=0.99, gae_lambda=0.95, clip_coef=0.2, ent_coef=0.01,
                  vf_coef=0.5, max_grad_norm=0.5, update_epochs=4, target_kl=None, seeds=None,
@@ -238,8 +292,8 @@ class PPOPopulation:
         # image specs keep uint8 frames (normalised inside the first conv's load)
         self.obs = torch.zeros(P, T, N, D, dtype=getattr(self.spec, "obs_dtype", torch.float32), device=dev)
         self.actions = (torch.zeros(P, T, N, self.spec.n_actions, dtype=torch.float32, device=dev) if self.gaussian
-                        else torch.zeros(P, T, N, len(self.spec.nvec), dtype=torch.int64, device=dev)
-                        if self.multidiscrete else torch.zeros(P, T, N, dtype=torch.int64, device=dev))
+                        else torch.zeros(P, T, N, self.act_width, dtype=torch.int64, device=dev)
+                        if self.vector_int else torch.zeros(P, T, N, dtype=torch.int64, device=dev))
         self.rewards = torch.zeros(P, T, N, **f32)
         self.dones = torch.zeros(P, T, N, dtype=torch.uint8, device=dev)
         self.values = torch.zeros(P, T, N, **f32)
@@ -275,7 +329,7 @@ class PPOPopulation:
                               counter=int(counter), actions=action, log_probs=logp, values=value, entropy=ent,
                               out_agent_stride=N)
             return action, logp, ent, value
-        if self.multidiscrete:  # one agx_ppo_act_multi_graph launch, int64 actions [P, N, K]
+        if self.vector_int:  # one agx_ppo_act_multi_graph / _bern_graph launch, int64 actions [P, N, K]
             if counter is None:
                 self.act_counter += 1
                 counter = self.act_counter
@@ -298,7 +352,7 @@ class PPOPopulation:
     def fused_descriptor(self):
         """agx_ppo_net for this architecture, or None when the fused kernels do
         not cover it (then the plain-PyTorch forward / learner run)."""
-        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian or self.multidiscrete:
+        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian or self.vector_int:
             return None  # the fused kernels take the categorical MLP actor-critic shapes only
         if self._desc is None:
             from .learner import net_descriptor
@@ -312,7 +366,7 @@ class PPOPopulation:
         an architecture mutation produces); None: the plain-PyTorch learner."""
         desc = self.fused_descriptor()
         if (desc is not None or not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian
-                or self.multidiscrete):
+                or self.vector_int):
             return desc
         if self._gdesc is None:
             from .learner import graph_descriptor
@@ -325,7 +379,7 @@ class PPOPopulation:
         actor-critic, the compiled shapes included, so that a population's
         agents are evaluated together in one launch whatever kernels they train
         on (agx_ppo_eval_multi_persistent).  None: the PyTorch policy step."""
-        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian or self.multidiscrete:
+        if not self.fused or not isinstance(self.spec, ActorCriticSpec) or self.gaussian or self.vector_int:
             return None
         if self.fused_descriptor() is None:
             return self.learn_descriptor()  # already the runtime layer list
@@ -361,6 +415,19 @@ class PPOPopulation:
                                     _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
         return self._multi
 
+    def bern_descriptor(self):
+        """agx_ppo_graph of a MultiBinary population's networks for
+        agx_ppo_act_bern_graph.  There is no other policy step for such a
+        population: a layer list the kernel does not take is an error."""
+        if not self.multibinary:
+            return None
+        if self._bern is None:
+            self._bern = self.spec.bern_descriptor()
+            if self._bern is None:
+                raise _lib.AgxError("agx_ppo_act_bern_graph does not take this network: " +
+                                    _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
+        return self._bern
+
     def multi_head(self):
         """agx_multi_head of the spec's nvec (made once)."""
         if self._mhead is None:
@@ -370,15 +437,16 @@ class PPOPopulation:
     @torch.no_grad()
     def _multi_step(self, obs: torch.Tensor, *, sample: bool, counter: int, action_mask=None):
         """obs [P, N, D] -> (actions int64 [P, N, K], log_prob, entropy, value
-        [P, N]) of a MultiDiscrete population; action_mask uint8 [P, N, L]."""
-        from .learner import policy_step_multi
+        [P, N]) of a MultiDiscrete population; action_mask uint8 [P, N, L].  A
+        MultiBinary population: 0 / 1 actions [P, N, n], action_mask [P, N, n]."""
+        from .learner import policy_step_vector
 
         P, N, L = self.P, self.N, self.spec.n_actions
-        action = torch.empty(P, N, len(self.spec.nvec), dtype=torch.int64, device=self.device)
+        action = torch.empty(P, N, self.act_width, dtype=torch.int64, device=self.device)
         logp, ent, value = (torch.empty(P, N, dtype=torch.float32, device=self.device) for _ in range(3))
-        policy_step_multi(self, self.multi_descriptor(), obs.contiguous(), N * self.spec.obs_dim, sample=sample,
-                          counter=counter, actions=action, log_probs=logp, values=value, entropy=ent,
-                          out_agent_stride=N, action_mask=action_mask, mask_agent_stride=N * L)
+        policy_step_vector(self, obs.contiguous(), N * self.spec.obs_dim, sample=sample,
+                           counter=counter, actions=action, log_probs=logp, values=value, entropy=ent,
+                           out_agent_stride=N, action_mask=action_mask, mask_agent_stride=N * L)
         return action, logp, ent, value
 
     def gauss_learn_descriptor(self):
@@ -405,10 +473,21 @@ class PPOPopulation:
             self._mlearn = self.spec.multi_learn_descriptor() or False
         return self._mlearn or None
 
+    def bern_learn_descriptor(self):
+        """agx_ppo_graph of a MultiBinary population's networks for the fused
+        learner (agx_ppo_learn_bern_graph); None: not a MultiBinary
+        population, ``fused`` off, AGX_BERN_FUSED=0, or a layer list
+        agx_ppo_bern_graph_check rejects — then the autograd learner runs."""
+        if not self.multibinary or not self.fused or os.environ.get("AGX_BERN_FUSED", "1") == "0":
+            return None
+        if self._blearn is None:
+            self._blearn = self.spec.bern_learn_descriptor() or False
+        return self._blearn or None
+
     def _fused_learner(self) -> bool:
         """True when learn() runs a fused HIP learner (any head)."""
         return (self.learn_descriptor() is not None or self.gauss_learn_descriptor() is not None
-                or self.multi_learn_descriptor() is not None)
+                or self.multi_learn_descriptor() is not None or self.bern_learn_descriptor() is not None)
 
     @torch.no_grad()
     def act_into(self, t: int, actions_flat: torch.Tensor | None = None) -> None:
@@ -424,17 +503,17 @@ class PPOPopulation:
                               counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
                               values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat)
             return
-        if self.multidiscrete:  # int64 [P*N*K] staging; slot t's stored masks, when the population keeps them
-            from .learner import policy_step_multi
+        if self.vector_int:  # int64 [P*N*K] staging; slot t's stored masks, when the population keeps them
+            from .learner import policy_step_vector
 
             self.act_counter += 1
             TN = self.T * self.N
             masks = self.action_masks
-            policy_step_multi(self, self.multi_descriptor(), self.obs[:, t], TN * self.spec.obs_dim, sample=True,
-                              counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
-                              values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat,
-                              action_mask=None if masks is None else masks[:, t],
-                              mask_agent_stride=TN * self.spec.n_actions)
+            policy_step_vector(self, self.obs[:, t], TN * self.spec.obs_dim, sample=True,
+                               counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
+                               values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat,
+                               action_mask=None if masks is None else masks[:, t],
+                               mask_agent_stride=TN * self.spec.n_actions)
             return
         desc = self.fused_descriptor()
         if desc is None and self.learn_descriptor() is not None:  # a mutated shape: the runtime-shape kernel
@@ -477,7 +556,7 @@ class PPOPopulation:
         """Bootstrap value + GAE (+ per-agent advantage statistics).  The fused
         runner computes last_value in its final rollout-step launch."""
         self.rollout_id += 1
-        if last_value is None and (self.gaussian or self.multidiscrete):
+        if last_value is None and (self.gaussian or self.vector_int):
             last_value = self.values_of(last_obs)
         elif last_value is None:
             with torch.no_grad():
@@ -510,13 +589,13 @@ class PPOPopulation:
     @torch.no_grad()
     def values_of(self, obs: torch.Tensor) -> torch.Tensor:
         """The critic's values [P, N] of obs [P, N, D] from a Gaussian
-        (or MultiDiscrete) population's policy-step kernel (sample = 0, values only)."""
-        from .learner import policy_step_gauss, policy_step_multi
+        (or MultiDiscrete / MultiBinary) population's policy-step kernel (sample = 0, values only)."""
+        from .learner import policy_step_gauss, policy_step_vector
 
         value = torch.empty(self.P, self.N, dtype=torch.float32, device=self.device)
-        if self.multidiscrete:
-            policy_step_multi(self, self.multi_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim,
-                              sample=False, counter=0, values=value, out_agent_stride=self.N)
+        if self.vector_int:
+            policy_step_vector(self, obs.contiguous(), self.N * self.spec.obs_dim,
+                               sample=False, counter=0, values=value, out_agent_stride=self.N)
             return value
         policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim, sample=False,
                           counter=0, values=value, out_agent_stride=self.N)
@@ -530,7 +609,7 @@ class PPOPopulation:
         prefetches after pacing the rollout instead)."""
         self.learn_steps += 1
         # the categorical kernels, else the Gaussian graph learner, else (when switched on)
-        # the multi-categorical graph learner
+        # the multi-categorical graph learner, else the Bernoulli graph learner
         if self._fused_learner():
             from .learner import fused_learn
 
@@ -691,7 +770,7 @@ class PPOPopulation:
         host pacing it, the device is waiting for this thread, so nothing
         there may wait for the device — and a hipMalloc / hipHostMalloc, or an
         event sync, can.  Any fused learner: the categorical kernels, the
-        Gaussian and the multi-categorical graph learner."""
+        Gaussian, the multi-categorical and the Bernoulli graph learner."""
         if self._fused_learner():
             from .learner import learner_stale, make_learner
 
@@ -756,7 +835,7 @@ class PPOPopulation:
         P, S, D = self.P, self.S, self.spec.obs_dim
         image = not isinstance(self.spec, ActorCriticSpec)
         obs = self.obs.view(P, S, D)
-        act = (self.actions.view(P * S, -1) if self.gaussian or self.multidiscrete else self.actions.view(P, S))
+        act = (self.actions.view(P * S, -1) if self.gaussian or self.vector_int else self.actions.view(P, S))
         masks = None if self.action_masks is None else self.action_masks.view(P, S, -1)
         flat_masks = None if masks is None else masks.view(P * S, -1)  # the multi-categorical loss gathers them
         old_logp = self.log_probs.view(-1)
@@ -790,6 +869,10 @@ class PPOPopulation:
                     loss, stats = _PPOMultiLossFn.apply(logits, value, self.multi_head(), act, flat_masks, old_logp,
                                                         adv, ret, old_v, gidx, s1 - s0, self.clip_coef,
                                                         self.vf_coef, ent_coef)
+                elif self.multibinary:  # the loss kernel gathers the int64 bits [.., n] and the masks
+                    logits, value = self.spec.forward(self.params, ob)
+                    loss, stats = _PPOBernLossFn.apply(logits, value, act, flat_masks, old_logp, adv, ret, old_v,
+                                                       gidx, s1 - s0, self.clip_coef, self.vf_coef, ent_coef)
                 else:
                     loss, stats = self._categorical_loss(ob, torch.gather(act, 1, idx), masks, idx, rows, image,
                                                          (old_logp, adv, ret, old_v), gidx, s1 - s0, ent_coef)
@@ -825,7 +908,7 @@ class PPOPopulation:
             policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim,
                               sample=False, counter=0, actions=action, out_agent_stride=self.N)
             return action
-        if self.multidiscrete:  # the first arg-max of every component, [P, N, K]
+        if self.vector_int:  # the first arg-max of every component, [P, N, K]; the mode of every bit, [P, N, n]
             return self._multi_step(obs, sample=False, counter=0)[0]
         logits, _ = self.spec.forward(self.params.data, obs)
         return torch.argmax(logits, dim=-1)

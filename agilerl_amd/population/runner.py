@@ -224,8 +224,8 @@ class PopulationRunner:
         pop = self.pop
         if pop.gaussian:
             return torch.zeros(pop.P * pop.N * pop.spec.n_actions, dtype=torch.float32, **kw)
-        if pop.multidiscrete:
-            return torch.zeros(pop.P * pop.N * len(pop.spec.nvec), dtype=torch.int64, **kw)
+        if pop.vector_int:  # a MultiBinary population: one column per bit
+            return torch.zeros(pop.P * pop.N * pop.act_width, dtype=torch.int64, **kw)
         return torch.zeros(pop.P * pop.N, dtype=torch.int64, **kw)
 
     def _ctl_bytes(self) -> int:
@@ -287,11 +287,15 @@ class PopulationRunner:
         # numpy views of the staging made once (Tensor.numpy() costs ~1-3 us a call)
         if self._np is None:
             act = self.act_h.numpy()
-            if self.pop.gaussian or self.pop.multidiscrete:  # the env takes [P*N, A] floats / [P*N, K] choices
+            if self.pop.gaussian or self.pop.vector_int:  # the env takes [P*N, A] floats / [P*N, K] choices
                 act = act.reshape(self.pop.P * self.pop.N, -1)
+            # a MultiBinary population: the env takes its 0 / 1 bits in the space's dtype
+            self._act_cast = self.pop.spec.action_dtype if self.pop.multibinary else None
             self._np = (act, self.obs_h.numpy(), self.rew_h.numpy(), self.done_h.numpy(),
                         self.term_h.numpy())
         act, obs, rew, done, term_np = self._np
+        if self._act_cast is not None:
+            act = act.astype(self._act_cast)
         _, _, term, trunc, _ = self.env.step(act, out_obs=obs, out_rew=rew, out_done=done)
         if trunc is not None and np.count_nonzero(trunc):  # done = term | trunc (on_policy.py:121-126)
             done |= trunc
@@ -443,11 +447,11 @@ class PopulationRunner:
             policy_step_gauss(pop, pop.gauss_descriptor(), self.last_obs, N * pop.spec.obs_dim, sample=False,
                               counter=0, values=self.last_value, out_agent_stride=N)
             self.last_value_valid = True
-        elif pop.multidiscrete:  # ... or from the multi-categorical one
-            from .learner import policy_step_multi
+        elif pop.vector_int:  # ... or from the multi-categorical / Bernoulli one
+            from .learner import policy_step_vector
 
-            policy_step_multi(pop, pop.multi_descriptor(), self.last_obs, N * pop.spec.obs_dim, sample=False,
-                              counter=0, values=self.last_value, out_agent_stride=N)
+            policy_step_vector(pop, self.last_obs, N * pop.spec.obs_dim, sample=False,
+                               counter=0, values=self.last_value, out_agent_stride=N)
             self.last_value_valid = True
         elif gdesc is not None:  # a mutated shape: the bootstrap value from the runtime-shape kernel too
             from .learner import policy_step_graph
@@ -760,10 +764,10 @@ class _EvalDriver:
             from .learner import gauss_act_workspace
 
             gauss_act_workspace(pop, pop.gauss_descriptor())
-        elif pop.multidiscrete:
-            from .learner import multi_act_workspace
+        elif pop.vector_int:
+            from .learner import vector_act_workspace
 
-            multi_act_workspace(pop, pop.multi_descriptor())
+            vector_act_workspace(pop)
         self.obs = None
         self.stream = None  # a dedicated non-blocking stream, assigned by run_lockstep
         self._pipelined = False
@@ -843,11 +847,11 @@ class _EvalDriver:
 
             policy_step_gauss(pop, pop.gauss_descriptor(), self.obs_d, N * D, sample=True, counter=counter,
                               out_agent_stride=N, actions_flat=self.act_d, clip=pop.action_clip())
-        elif pop.multidiscrete:  # a MultiDiscrete population: int64 [P*N*K] staging
-            from .learner import policy_step_multi
+        elif pop.vector_int:  # a MultiDiscrete / MultiBinary population: int64 [P*N*K] staging
+            from .learner import policy_step_vector
 
-            policy_step_multi(pop, pop.multi_descriptor(), self.obs_d, N * D, sample=True, counter=counter,
-                              out_agent_stride=N, actions_flat=self.act_d)
+            policy_step_vector(pop, self.obs_d, N * D, sample=True, counter=counter,
+                               out_agent_stride=N, actions_flat=self.act_d)
         elif self.edescs is not None:  # the evaluation layer list (as the multi launch samples)
             from .learner import policy_step_graph
 
@@ -898,7 +902,9 @@ class _EvalDriver:
             reward = rew_n
         else:
             act = self.act_h.numpy().copy()
-            vec = self.pop.gaussian or self.pop.multidiscrete  # [P*N, A] floats / [P*N, K] choices
+            vec = self.pop.gaussian or self.pop.vector_int  # [P*N, A] floats / [P*N, K] choices
+            if self.pop.multibinary:  # 0 / 1 bits in the space's dtype
+                act = act.astype(self.pop.spec.action_dtype)
             self.obs, reward, term, trunc, _ = self.env.step(act.reshape(self.P * self.N, -1) if vec else act)
         self.step += 1
         self.scores += np.asarray(reward).reshape(-1)
