@@ -66,6 +66,11 @@ SIGNATURES = {
     "agx_ppo_act_gauss_graph_workspace_bytes": (_SZ, [_P, _I, _I]),
     "agx_ppo_act_gauss_graph": (_INT, [_P, _I, _I, _I, _P, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
                                        _P, _I, _P, _P, _P, _P, _P, _P]),
+    "agx_ppo_rollout_gauss_graph_max_workgroups": (_I, []),
+    "agx_ppo_rollout_gauss_graph_persistent": (_INT, [_P, _I, _I, _I, _P, _P, _I, ctypes.c_uint32, ctypes.c_uint64,
+                                                      ctypes.c_uint64, _P, _P, _P, _P, _D, _P, _P]),
+    "agx_ppo_eval_gauss_graph_persistent": (_INT, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, ctypes.c_uint32,
+                                                   ctypes.c_uint64, ctypes.c_uint64, _P, _P, _D, _P, _P]),
     "agx_ppo_gauss_loss_fwd_bwd": (_INT, [_P] * 9 + [_I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "agx_ppo_gauss_graph_check": (_INT, [_P, _I]),
     "agx_ppo_learn_gauss_graph_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I, _I]),
@@ -74,6 +79,11 @@ SIGNATURES = {
     "agx_ppo_act_multi_graph_workspace_bytes": (_SZ, [_P, _I, _I]),
     "agx_ppo_act_multi_graph": (_INT, [_P, AgxMultiHead, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64,
                                        ctypes.c_uint64, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "agx_ppo_rollout_multi_graph_max_workgroups": (_I, []),
+    "agx_ppo_rollout_multi_graph_persistent": (_INT, [_P, AgxMultiHead, _I, _I, _P, _P, _I, ctypes.c_uint32,
+                                                      ctypes.c_uint64, ctypes.c_uint64, _P, _P, _D, _P, _P]),
+    "agx_ppo_eval_multi_graph_persistent": (_INT, [_P, AgxMultiHead, _I, _I, _P, _P, _P, _P, _I, ctypes.c_uint32,
+                                                   ctypes.c_uint64, ctypes.c_uint64, _P, _P, _D, _P, _P]),
     "agx_ppo_multi_loss_fwd_bwd": (_INT, [_P, _P, AgxMultiHead] + [_P] * 7 + [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
     "agx_ppo_multi_graph_check": (_INT, [_P, AgxMultiHead]),
     "agx_ppo_learn_multi_graph_workspace_bytes": (_SZ, [_P, AgxMultiHead, _I, _I, _I, _I]),
@@ -82,6 +92,11 @@ SIGNATURES = {
     "agx_ppo_act_bern_graph_workspace_bytes": (_SZ, [_P, _I, _I]),
     "agx_ppo_act_bern_graph": (_INT, [_P, _I, _I, _P, _P, _I, _P, _I, _INT, ctypes.c_uint64, ctypes.c_uint64, _P, _P,
                                       _P, _P, _I, _P, _P, _P, _P]),
+    "agx_ppo_rollout_bern_graph_max_workgroups": (_I, []),
+    "agx_ppo_rollout_bern_graph_persistent": (_INT, [_P, _I, _I, _P, _P, _I, ctypes.c_uint32, ctypes.c_uint64,
+                                                     ctypes.c_uint64, _P, _P, _D, _P, _P]),
+    "agx_ppo_eval_bern_graph_persistent": (_INT, [_P, _I, _I, _P, _P, _P, _P, _I, ctypes.c_uint32, ctypes.c_uint64,
+                                                  ctypes.c_uint64, _P, _P, _D, _P, _P]),
     "agx_ppo_bern_loss_fwd_bwd": (_INT, [_P, _P, ctypes.c_int32] + [_P] * 7 + [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
     "agx_ppo_bern_graph_check": (_INT, [_P]),
     "agx_ppo_learn_bern_graph_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),

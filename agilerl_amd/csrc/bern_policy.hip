@@ -12,6 +12,7 @@
 #include "../../include/agx_bernoulli.h"
 #include "bern_head.h"
 #include "graph_net.h"
+#include "head_rollout.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -113,6 +114,16 @@ __global__ __launch_bounds__(kGT) void ppo_act_bern_graph_kernel(const GActArgs 
     }
 }
 
+// bern_step as the step of head_rollout.h's persistent loop: the step's action
+// slot / host staging are int64 [.., n]
+struct BernRolloutHead {
+    __device__ __forceinline__ void step(const ActArgs &g, int n, int lda, int ldv, const float *lgp, const float *vp,
+                                         const float *, int p, int n0, int nrow) const {
+        const BernOut h{g.act_out, g.act_flat};
+        bern_step(g, h, n, lda, ldv, lgp, vp, p, n0, nrow);
+    }
+};
+
 // ---------------------------------------------------------------------------
 // loss
 // ---------------------------------------------------------------------------
@@ -207,6 +218,51 @@ extern "C" int agx_ppo_act_bern_graph(const agx_ppo_graph *net, int64_t P, int64
     else
         ppo_act_bern_graph_kernel<false><<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
     return check_launch("agx_ppo_act_bern_graph");
+}
+
+// ---------------------------------------------------------------------------
+// persistent rollout / evaluation
+// ---------------------------------------------------------------------------
+extern "C" int64_t agx_ppo_rollout_bern_graph_max_workgroups(void) {
+    return head_rollout_max_workgroups<BernRolloutHead>();
+}
+
+extern "C" int agx_ppo_rollout_bern_graph_persistent(const agx_ppo_graph *net, int64_t P, int64_t N,
+                                                     const float *params, const agx_rollout_io *ios, int64_t nsteps,
+                                                     uint32_t base, uint64_t seed, uint64_t counter0, void *args_host,
+                                                     agx_rollout_ctl *ctl, double timeout_s, void *workspace,
+                                                     void *stream) {
+    const char *who = "agx_ppo_rollout_bern_graph_persistent";
+    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
+                                  who))
+        return rc;
+    GArgs full{};
+    if (int rc = plan_graph(net, 1, full)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
+    if (int rc = fill_head_rollout_steps(steps, net->obs_dim, net->n_actions, P, N, params, ios, nsteps, seed,
+                                         counter0, who))
+        return rc;
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream,
+                                  BernRolloutHead{}, who);
+}
+
+extern "C" int agx_ppo_eval_bern_graph_persistent(const agx_ppo_graph *net, int64_t P, int64_t N, const float *params,
+                                                  const float *stage_obs, int64_t *actions_flat,
+                                                  const int64_t *agent_env_base, int64_t nsteps, uint32_t base,
+                                                  uint64_t seed, uint64_t counter0, void *args_host,
+                                                  agx_rollout_ctl *ctl, double timeout_s, void *workspace,
+                                                  void *stream) {
+    const char *who = "agx_ppo_eval_bern_graph_persistent";
+    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
+                                  nsteps, base, timeout_s, who))
+        return rc;
+    GArgs full{};
+    if (int rc = plan_graph(net, 1, full)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
+    fill_head_eval_steps(steps, net->obs_dim, net->n_actions, P, N, params, stage_obs, actions_flat, agent_env_base,
+                         nsteps, seed, counter0);
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream,
+                                  BernRolloutHead{}, who);
 }
 
 extern "C" int agx_ppo_bern_loss_fwd_bwd(const float *logits, const float *value, int32_t n, const int64_t *actions,

@@ -7,6 +7,7 @@
 #include "../../include/agx_gauss.h"
 #include "gauss_head.h"
 #include "graph_net.h"
+#include "head_rollout.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -116,6 +117,19 @@ __global__ __launch_bounds__(kGT) void ppo_act_gauss_graph_kernel(const GActArgs
     }
 }
 
+// gauss_step as the step of head_rollout.h's persistent loop: the step's action
+// slot / host staging are floats [.., A], the staging copy clipped to lo / hi
+struct GaussRolloutHead {
+    long long log_std_off;
+    const float *lo, *hi;  // [A] device, or null
+    __device__ __forceinline__ void step(const ActArgs &g, int A, int lda, int ldv, const float *mup, const float *vp,
+                                         const float *pr, int p, int n0, int nrow) const {
+        const GaussHead h{log_std_off, reinterpret_cast<float *>(g.act_out), reinterpret_cast<float *>(g.act_flat),
+                          lo, hi};
+        gauss_step(g, h, A, lda, ldv, mup, vp, pr + log_std_off, p, n0, nrow);
+    }
+};
+
 // ---------------------------------------------------------------------------
 // loss
 // ---------------------------------------------------------------------------
@@ -221,6 +235,66 @@ extern "C" int agx_ppo_act_gauss_graph(const agx_ppo_graph *net, int64_t log_std
     else
         ppo_act_gauss_graph_kernel<false><<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
     return check_launch("agx_ppo_act_gauss_graph");
+}
+
+// ---------------------------------------------------------------------------
+// persistent rollout / evaluation
+// ---------------------------------------------------------------------------
+extern "C" int64_t agx_ppo_rollout_gauss_graph_max_workgroups(void) {
+    return head_rollout_max_workgroups<GaussRolloutHead>();
+}
+
+namespace {
+// agx_ppo_act_gauss_graph's rules for the net and the head -> the plan
+int gauss_persistent_plan(const agx_ppo_graph *net, int64_t log_std_off, const float *clip_low,
+                          const float *clip_high, GArgs &full, const char *who) {
+    AGX_REQUIRE(!clip_low == !clip_high, "%s: clip_low and clip_high come together", who);
+    const int rc = plan_graph(net, 1, full, net->n_actions);
+    if (rc != AGX_OK) return rc;
+    AGX_REQUIRE(log_std_off >= 0 && log_std_off + net->n_actions <= net->n_params,
+                "%s: log_std outside the parameter row", who);
+    return AGX_OK;
+}
+}  // namespace
+
+extern "C" int agx_ppo_rollout_gauss_graph_persistent(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
+                                                      int64_t N, const float *params, const agx_rollout_io *ios,
+                                                      int64_t nsteps, uint32_t base, uint64_t seed,
+                                                      uint64_t counter0, const float *clip_low,
+                                                      const float *clip_high, void *args_host, agx_rollout_ctl *ctl,
+                                                      double timeout_s, void *workspace, void *stream) {
+    const char *who = "agx_ppo_rollout_gauss_graph_persistent";
+    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
+                                  who))
+        return rc;
+    GArgs full{};
+    if (int rc = gauss_persistent_plan(net, log_std_off, clip_low, clip_high, full, who)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
+    if (int rc = fill_head_rollout_steps(steps, net->obs_dim, net->n_actions, P, N, params, ios, nsteps, seed,
+                                         counter0, who))
+        return rc;
+    const GaussRolloutHead h{(long long)log_std_off, clip_low, clip_high};
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
+}
+
+extern "C" int agx_ppo_eval_gauss_graph_persistent(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
+                                                   int64_t N, const float *params, const float *stage_obs,
+                                                   float *actions_flat, const float *clip_low,
+                                                   const float *clip_high, const int64_t *agent_env_base,
+                                                   int64_t nsteps, uint32_t base, uint64_t seed, uint64_t counter0,
+                                                   void *args_host, agx_rollout_ctl *ctl, double timeout_s,
+                                                   void *workspace, void *stream) {
+    const char *who = "agx_ppo_eval_gauss_graph_persistent";
+    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
+                                  nsteps, base, timeout_s, who))
+        return rc;
+    GArgs full{};
+    if (int rc = gauss_persistent_plan(net, log_std_off, clip_low, clip_high, full, who)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
+    fill_head_eval_steps(steps, net->obs_dim, net->n_actions, P, N, params, stage_obs, actions_flat, agent_env_base,
+                         nsteps, seed, counter0);
+    const GaussRolloutHead h{(long long)log_std_off, clip_low, clip_high};
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
 }
 
 extern "C" int agx_ppo_gauss_loss_fwd_bwd(const float *mean, const float *value, const float *log_std,

@@ -23,6 +23,7 @@
 // loads stay outside the loop, once per lane.
 #include "../../include/agx_multi.h"
 #include "graph_net.h"
+#include "head_rollout.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -46,12 +47,15 @@ struct MultiHead {
 
 // The multi-categorical step of rows [0, nrow) of agent p's row block n0
 // (logits at lgp [nrow][L] with row stride lda, values at vp with stride ldv).
-__device__ __forceinline__ void multi_step(const ActArgs &g, const MultiHead &h, int L, int lda, int ldv,
-                                           const float *lgp, const float *vp, int p, int n0, int nrow) {
+// head: the kernel's own argument (its nvec[k] reads stay scalar loads of the
+// argument block; a copy would be indexed in scratch)
+__device__ __forceinline__ void multi_step(const ActArgs &g, const agx_multi_head &head, long long *act_out,
+                                           long long *act_flat, int L, int lda, int ldv, const float *lgp,
+                                           const float *vp, int p, int n0, int nrow) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane & 15, rq = lane >> 4;
     const int j0 = sub, j1 = sub + 16;
-    const int K = h.head.K;
+    const int K = head.K;
     for (int r0 = 0; r0 < nrow; r0 += 4 * kGW) {
         const int r = r0 + 4 * wave + rq;
         const bool live = r < nrow;
@@ -73,7 +77,7 @@ __device__ __forceinline__ void multi_step(const ActArgs &g, const MultiHead &h,
         float lp = 0.f, H = 0.f;
         int ch0 = 0, ch1 = 0, off = 0;
         for (int k = 0; k < K; ++k) {  // wave-uniform: K and nvec are kernel arguments
-            const int n = h.head.nvec[k];
+            const int n = head.nvec[k];
             const bool in0 = j0 >= off && j0 < off + n, in1 = j1 >= off && j1 < off + n;
             const float lse = seg_lse(in0, in1, lg0, lg1);
             const float p0 = in0 ? expf(lg0 - lse) : 0.f, p1 = in1 ? expf(lg1 - lse) : 0.f;
@@ -100,12 +104,12 @@ __device__ __forceinline__ void multi_step(const ActArgs &g, const MultiHead &h,
         }
         if (!live) continue;
         const size_t row = (size_t)p * g.out_pstride + n0 + r;
-        if (h.act_out) {
-            if (j0 < K) h.act_out[row * K + j0] = ch0;
-            if (j1 < K) h.act_out[row * K + j1] = ch1;
+        if (act_out) {
+            if (j0 < K) act_out[row * K + j0] = ch0;
+            if (j1 < K) act_out[row * K + j1] = ch1;
         }
-        if (h.act_flat) {  // host staging: system-scope (write-through) stores
-            long long *f = h.act_flat + ((size_t)p * g.N + n0 + r) * K;
+        if (act_flat) {  // host staging: system-scope (write-through) stores
+            long long *f = act_flat + ((size_t)p * g.N + n0 + r) * K;
             if (j0 < K) __hip_atomic_store(f + j0, (long long)ch0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (j1 < K) __hip_atomic_store(f + j1, (long long)ch1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
@@ -141,13 +145,23 @@ __global__ __launch_bounds__(kGT) void ppo_act_multi_graph_kernel(const GActArgs
         const auto prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pr), 0,
                                                            __builtin_amdgcn_readfirstlane(ga.n * 4), 0x00020000);
         few_forward(ga.L, ga.nl, gdyn, pr, prs, ga.oc, ga.ld0, nullptr);
-        multi_step(g, h, ga.A, La.ld, Lc.ld, gdyn + La.yr, gdyn + Lc.yr, p, n0, nrow);
+        multi_step(g, h.head, h.act_out, h.act_flat, ga.A, La.ld, Lc.ld, gdyn + La.yr, gdyn + Lc.yr, p, n0, nrow);
     } else {
         float *base = ga.ws + ((size_t)p * gridDim.x + blockIdx.x) * ga.ws_block;
         forward_layers(ga.L, ga.nl, obs, nrow, base, pr, ga.rows, lds);
-        multi_step(g, h, ga.A, ga.A, 1, base + La.yr, base + Lc.yr, p, n0, nrow);
+        multi_step(g, h.head, h.act_out, h.act_flat, ga.A, ga.A, 1, base + La.yr, base + Lc.yr, p, n0, nrow);
     }
 }
+
+// multi_step as the step of head_rollout.h's persistent loop: the step's
+// action slot / host staging are int64 [.., K]
+struct MultiRolloutHead {
+    agx_multi_head head;
+    __device__ __forceinline__ void step(const ActArgs &g, int L, int lda, int ldv, const float *lgp, const float *vp,
+                                         const float *, int p, int n0, int nrow) const {
+        multi_step(g, head, g.act_out, g.act_flat, L, lda, ldv, lgp, vp, p, n0, nrow);
+    }
+};
 
 // ---------------------------------------------------------------------------
 // loss
@@ -302,6 +316,67 @@ extern "C" int agx_ppo_act_multi_graph(const agx_ppo_graph *net, agx_multi_head 
     else
         ppo_act_multi_graph_kernel<false><<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
     return check_launch("agx_ppo_act_multi_graph");
+}
+
+// ---------------------------------------------------------------------------
+// persistent rollout / evaluation
+// ---------------------------------------------------------------------------
+extern "C" int64_t agx_ppo_rollout_multi_graph_max_workgroups(void) {
+    return head_rollout_max_workgroups<MultiRolloutHead>();
+}
+
+namespace {
+// agx_ppo_act_multi_graph's rules for the net and the head -> the plan and the kernel's head
+int multi_persistent_plan(const agx_ppo_graph *net, const agx_multi_head &head, GArgs &full, MultiRolloutHead &h,
+                          const char *who) {
+    const int L = head_width(head, who);
+    if (L < 0) return AGX_EINVAL;
+    const int rc = plan_graph(net, 1, full);
+    if (rc != AGX_OK) return rc;
+    AGX_REQUIRE(L == net->n_actions, "%s: nvec sums to %d, the actor's output has %d logits", who, L, net->n_actions);
+    h = MultiRolloutHead{};
+    h.head.K = head.K;  // the components past K are never read: pass them as zeros
+    for (int k = 0; k < head.K; ++k) h.head.nvec[k] = head.nvec[k];
+    return AGX_OK;
+}
+}  // namespace
+
+extern "C" int agx_ppo_rollout_multi_graph_persistent(const agx_ppo_graph *net, agx_multi_head head, int64_t P,
+                                                      int64_t N, const float *params, const agx_rollout_io *ios,
+                                                      int64_t nsteps, uint32_t base, uint64_t seed,
+                                                      uint64_t counter0, void *args_host, agx_rollout_ctl *ctl,
+                                                      double timeout_s, void *workspace, void *stream) {
+    const char *who = "agx_ppo_rollout_multi_graph_persistent";
+    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
+                                  who))
+        return rc;
+    GArgs full{};
+    MultiRolloutHead h;
+    if (int rc = multi_persistent_plan(net, head, full, h, who)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
+    if (int rc = fill_head_rollout_steps(steps, net->obs_dim, net->n_actions, P, N, params, ios, nsteps, seed,
+                                         counter0, who))
+        return rc;
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
+}
+
+extern "C" int agx_ppo_eval_multi_graph_persistent(const agx_ppo_graph *net, agx_multi_head head, int64_t P,
+                                                   int64_t N, const float *params, const float *stage_obs,
+                                                   int64_t *actions_flat, const int64_t *agent_env_base,
+                                                   int64_t nsteps, uint32_t base, uint64_t seed, uint64_t counter0,
+                                                   void *args_host, agx_rollout_ctl *ctl, double timeout_s,
+                                                   void *workspace, void *stream) {
+    const char *who = "agx_ppo_eval_multi_graph_persistent";
+    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
+                                  nsteps, base, timeout_s, who))
+        return rc;
+    GArgs full{};
+    MultiRolloutHead h;
+    if (int rc = multi_persistent_plan(net, head, full, h, who)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
+    fill_head_eval_steps(steps, net->obs_dim, net->n_actions, P, N, params, stage_obs, actions_flat, agent_env_base,
+                         nsteps, seed, counter0);
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
 }
 
 extern "C" int agx_ppo_multi_loss_fwd_bwd(const float *logits, const float *value, agx_multi_head head,

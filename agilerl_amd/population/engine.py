@@ -463,7 +463,8 @@ class PopulationEngine:
         # queue, the later one waiting behind a launch that waits for the host.
         # The remaining groups (the PyTorch policy step) step together in lock
         # step with per-step launches, after the persistent passes.
-        paced = [g for g in self.groups if g.runner.persistent or g.runner.graph_persistent]
+        paced = [g for g in self.groups
+                 if g.runner.persistent or g.runner.graph_persistent or g.runner.head_persistent]
         stepped = [g for g in self.groups if g not in paced]
         for k in range(loop):
             batches = [[g] for g in paced] + ([stepped] if stepped else [])

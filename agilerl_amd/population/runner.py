@@ -37,12 +37,29 @@ where its step may use the device freely.  A gymnasium env that does not touch
 the GPU can opt in by setting the attribute.
 
 Architectures outside the fused kernels use the plain-PyTorch policy step
-with per-field copies (``_collect_torch``).  A Gaussian (Box-action)
-population takes the same per-step path with its own HIP policy step
-(agx_ppo_act_gauss_graph, one launch per vector step): float32 action staging
-of P*N*A, the env is handed [P*N, A].  A MultiDiscrete population does the
-same through agx_ppo_act_multi_graph: int64 staging of P*N*K, the env is
-handed [P*N, K].
+with per-field copies (``_collect_torch``).
+
+A Gaussian (Box-action), MultiDiscrete or MultiBinary population on a paced
+env collects its rollout in one persistent launch too (``head_persistent``:
+agx_ppo_rollout_gauss_graph_persistent / _multi_ / _bern_, the host-paced
+loop above around the head's own policy step) and evaluates in one resident
+launch per chunk (agx_ppo_eval_*_graph_persistent).  The action staging is
+sized by the head: float32 P*N*A (the env is handed [P*N, A], clipped to the
+Box bounds as on_policy.py:104-119 does; the rollout slot keeps the unclipped
+sample), or int64 P*N*K / P*N*n (the env is handed [P*N, K]).  With action
+masks, an env that is not paced, non-float32 observations or a grid beyond
+the head kernel's co-residency limit, such a population takes the per-step
+path of ``_collect_torch`` with its HIP policy step (agx_ppo_act_gauss_graph /
+_multi_graph / _bern_graph, one launch per vector step); both paths run the
+same device functions on the same counters, so the rollout buffers hold the
+same bits wherever the env's transitions do not depend on which copy of the
+action it was handed.  For MultiDiscrete / MultiBinary the env's copy is the
+same on both paths.  For a Box population it is NOT: the persistent path
+hands the env the action clipped to the bounds, ``_collect_torch`` still
+hands it the unclipped sample, so on an env that reacts to out-of-bounds
+actions the trajectory depends on the path the runner selects (grid size,
+``agx_device_free``, AGX_PERSISTENT_ROLLOUT, AGX_ZERO_COPY); the synthetic
+envs ignore their actions.  Aligning the per-step path is open.
 """
 
 from __future__ import annotations
@@ -165,6 +182,17 @@ def _packed(P: int, N: int, D: int, owner=None, obs_dtype=torch.float32, **kw):
     return buf, obs, rew, done
 
 
+def head_max_workgroups(pop) -> int:
+    """Co-resident workgroups of the persistent rollout kernel of ``pop``'s
+    head (each head's kernel has its own occupancy)."""
+    lib = _lib.load()
+    if pop.gaussian:
+        return int(lib.agx_ppo_rollout_gauss_graph_max_workgroups())
+    if pop.multibinary:
+        return int(lib.agx_ppo_rollout_bern_graph_max_workgroups())
+    return int(lib.agx_ppo_rollout_multi_graph_max_workgroups())
+
+
 class PopulationRunner:
     def __init__(self, pop: PPOPopulation, env):
         if env.num_envs != pop.P * pop.N:
@@ -185,11 +213,16 @@ class PopulationRunner:
         self.graph_persistent = bool(paced and gdesc is not None and pop.obs.dtype == torch.float32 and
                                      lib.agx_ppo_rollout_graph_workgroups(P, N) <=
                                      lib.agx_ppo_rollout_graph_max_workgroups())
-        if self.persistent or self.graph_persistent:
+        # a Gaussian / MultiDiscrete / MultiBinary population: the head's own persistent
+        # launch (no legal-action masks: the runner stages none)
+        self.head_persistent = bool(paced and (pop.gaussian or pop.vector_int) and pop.action_masks is None and
+                                    pop.obs.dtype == torch.float32 and
+                                    lib.agx_ppo_rollout_graph_workgroups(P, N) <= head_max_workgroups(pop))
+        if self.persistent or self.graph_persistent or self.head_persistent:
             self.stage_h, self.obs_h, self.rew_h, self.done_h = _packed(P, N, D, owner=self)
-            self.act_h = _coherent(self, P * N * 8).view(torch.int64)
-            self.n_wg = int(lib.agx_ppo_rollout_graph_workgroups(P, N) if self.graph_persistent
-                            else lib.agx_rollout_workgroups(P, N))
+            self.act_h = self._coherent_actions()
+            self.n_wg = int(lib.agx_rollout_workgroups(P, N) if self.persistent
+                            else lib.agx_ppo_rollout_graph_workgroups(P, N))
             self.ctl_h = _coherent(self, self._ctl_bytes())
             self.args_h = _coherent(self, int(lib.agx_rollout_args_bytes(pop.T + 1)))
             self.seq_base = 0
@@ -228,9 +261,16 @@ class PopulationRunner:
             return torch.zeros(pop.P * pop.N * pop.act_width, dtype=torch.int64, **kw)
         return torch.zeros(pop.P * pop.N, dtype=torch.int64, **kw)
 
+    def _coherent_actions(self) -> torch.Tensor:
+        """_action_staging in coherent host memory (a persistent launch's)."""
+        pop = self.pop
+        if pop.gaussian:
+            return _coherent(self, pop.P * pop.N * pop.spec.n_actions * 4).view(torch.float32)
+        return _coherent(self, pop.P * pop.N * pop.act_width * 8).view(torch.int64)
+
     def _ctl_bytes(self) -> int:
         lib, P, N = _lib.load(), self.pop.P, self.pop.N
-        return int(lib.agx_ppo_rollout_graph_ctl_bytes(P, N) if self.graph_persistent
+        return int(lib.agx_ppo_rollout_graph_ctl_bytes(P, N) if self.graph_persistent or self.head_persistent
                    else lib.agx_rollout_ctl_bytes(P, N))
 
     # ------------------------------------------------------------------ #
@@ -305,7 +345,7 @@ class PopulationRunner:
     def collect(self) -> None:
         pop, env = self.pop, self.env
         desc = pop.fused_descriptor()
-        if desc is None and not self.graph_persistent:
+        if desc is None and not self.graph_persistent and not self.head_persistent:
             return self._collect_torch()
         P, N, T = pop.P, pop.N, pop.T
         if self._ios is None:
@@ -315,7 +355,7 @@ class PopulationRunner:
             if not self.zero_copy:
                 self.stage_d.copy_(self.stage_h, non_blocking=True)
             self.started = True
-        if self.persistent or self.graph_persistent:
+        if self.persistent or self.graph_persistent or self.head_persistent:
             return self._collect_persistent(desc)
         lib = _lib.load()
         fn = lib.agx_ppo_rollout_step
@@ -342,7 +382,12 @@ class PopulationRunner:
         self.env_steps += P * N * T
 
     def _collect_persistent(self, desc) -> None:
-        """One launch for the whole rollout; the host paces it step by step."""
+        """One launch for the whole rollout; the host paces it step by step.
+        Between the launch and the host's final release nothing here may wait
+        for the device (no allocation, synchronize, .item() or hipHostFree: the
+        pacing stays inside _pacing_begin / _pacing_end), and every exception
+        path releases the workgroups with the abort word before it drains
+        (_pace_persistent)."""
         _pacing_begin()
         try:
             lib, ctl, base = self._launch_persistent(desc)
@@ -361,7 +406,9 @@ class PopulationRunner:
             torch.cuda.current_stream().synchronize()
             self.ctl_h.zero_()
             base = 0
-        if self.graph_persistent:  # a mutated shape: the runtime-shape policy step in the same loop
+        if self.head_persistent:
+            self._launch_head(lib, base, ctl)
+        elif self.graph_persistent:  # a mutated shape: the runtime-shape policy step in the same loop
             from .learner import graph_act_workspace
 
             gdesc = pop.learn_descriptor()
@@ -379,6 +426,39 @@ class PopulationRunner:
         self.seq_base = base + T + 1
         self._mark_stats()
         return lib, ctl, base
+
+    def _launch_head(self, lib, base: int, ctl: int) -> None:
+        """The head's persistent rollout launch.  Its policy-step scratch and
+        (Gaussian) the clip bounds are taken BEFORE the launch: an allocation
+        can wait for the device, which from the launch on waits for this
+        thread."""
+        pop = self.pop
+        P, N, T = pop.P, pop.N, pop.T
+        tail = (self.args_h.data_ptr(), ctl, self.timeout_s)
+        if pop.gaussian:
+            from .learner import gauss_act_workspace
+
+            gdesc = pop.gauss_descriptor()
+            ws = gauss_act_workspace(pop, gdesc)[1]
+            lo, hi = pop.action_clip() or (None, None)
+            _lib.check(lib.agx_ppo_rollout_gauss_graph_persistent(
+                ctypes.byref(gdesc), pop.spec.log_std, P, N, pop.params.data.data_ptr(), self._ios, T + 1, base,
+                pop.act_seed, pop.act_counter, _lib.ptr(lo), _lib.ptr(hi), *tail, ws.data_ptr(), _lib.stream()),
+                "agx_ppo_rollout_gauss_graph_persistent")
+            return
+        from .learner import vector_act_workspace
+
+        ws = vector_act_workspace(pop)[1]
+        if pop.multibinary:
+            _lib.check(lib.agx_ppo_rollout_bern_graph_persistent(
+                ctypes.byref(pop.bern_descriptor()), P, N, pop.params.data.data_ptr(), self._ios, T + 1, base,
+                pop.act_seed, pop.act_counter, *tail, ws.data_ptr(), _lib.stream()),
+                "agx_ppo_rollout_bern_graph_persistent")
+        else:
+            _lib.check(lib.agx_ppo_rollout_multi_graph_persistent(
+                ctypes.byref(pop.multi_descriptor()), pop.multi_head(), P, N, pop.params.data.data_ptr(), self._ios,
+                T + 1, base, pop.act_seed, pop.act_counter, *tail, ws.data_ptr(), _lib.stream()),
+                "agx_ppo_rollout_multi_graph_persistent")
 
     def _mark_stats(self) -> None:
         """Event after the rollout's last episode-accounting write: the
@@ -473,9 +553,14 @@ class PopulationRunner:
         the next rollout starts from a fresh reset like the reference's next
         collect_rollouts (on_policy.py:50-56).  -> float64 [P].
 
-        Compiled shapes on a device-free env run the pass as ONE persistent
-        launch (agx_ppo_eval_persistent, paced like the rollout); other
-        shapes launch the policy step per vector step (_EvalDriver)."""
+        A runner that paces persistent launches (a device-free env) runs
+        the pass as resident launches paced like the rollout: categorical
+        populations in agx_ppo_eval_multi_persistent where
+        population_eval_ok holds, else agx_ppo_eval_persistent (compiled
+        shapes) / agx_ppo_eval_graph_persistent (runtime shapes); Gaussian,
+        MultiDiscrete and MultiBinary populations (``head_persistent``) in
+        agx_ppo_eval_gauss_graph_persistent / _multi_ / _bern_.  Any other
+        runner launches the policy step per vector step (_EvalDriver)."""
         pop = self.pop
         pop.eval_rounds = getattr(pop, "eval_rounds", 0) + 1
         out = np.zeros((loop, pop.P))
@@ -499,7 +584,7 @@ class PopulationRunner:
             P, N, D = pop.P, pop.N, pop.spec.obs_dim
             lib = _lib.load()
             _, obs, rew, done = _packed(P, N, D, owner=self)
-            act = _coherent(self, P * N * 8).view(torch.int64)
+            act = self._coherent_actions()  # sized by the head
             # room for the group's own evaluation launch and the population-wide one
             ctl = _coherent(self, max(self._ctl_bytes(), int(lib.agx_ppo_rollout_graph_ctl_bytes(P, N))))
             args = _coherent(self, int(lib.agx_rollout_args_bytes(_EVAL_CHUNK)))
@@ -648,6 +733,7 @@ def population_eval_ok(runners: list, paced: bool = True) -> bool:
     launches (a device-free env; not asked with paced=False), every network
     has an evaluation layer list, one env width, and the kernel takes the
     whole grid."""
+    # categorical only: a head_persistent runner (Gaussian / MultiDiscrete / MultiBinary) never joins
     if not runners or (paced and not all(r.persistent or r.graph_persistent for r in runners)):
         return False
     pops = [r.pop for r in runners]
@@ -672,7 +758,9 @@ class _EvalDriver:
     mode keeps ONE launch resident for the pass and paces it through its own
     control block: agx_ppo_eval_multi_persistent (every agent on its own
     network, all groups at once) where population_eval_ok holds, else the
-    group's agx_ppo_eval_persistent / agx_ppo_eval_graph_persistent;
+    group's agx_ppo_eval_persistent / agx_ppo_eval_graph_persistent, or for
+    a head_persistent runner (Gaussian / MultiDiscrete / MultiBinary) the
+    head's agx_ppo_eval_gauss_graph_persistent / _multi_ / _bern_ (``head``);
     otherwise one policy-step launch + event wait per step (the evaluation
     layer list when the multi form is available, so both give the same
     samples)."""
@@ -699,7 +787,8 @@ class _EvalDriver:
         # the evaluation layer list wherever the multi form can run, per-step
         # launches included: persistent and per-step passes then sample alike
         self.edescs = _eval_nets(self.runners)[1] if capable else None
-        self.persistent = bool(self.multi or (allow_persistent and (
+        self.head = bool(allow_persistent and not self.multi and runner.head_persistent)
+        self.persistent = bool(self.multi or self.head or (allow_persistent and (
             (runner.persistent and self.desc is not None) or (runner.graph_persistent and self.gdesc is not None))))
         self.step = 0
         self.scores = np.zeros(P * N)
@@ -713,7 +802,10 @@ class _EvalDriver:
             self.launched_to = 0  # steps covered by launches so far (0: no launch resident)
             # per-step host work kept to the env step: numpy views of the staging
             # and the control-block entry points, taken once
-            self._views = (self.obs_h.numpy(), self.rew_h.numpy(), self.done_h.numpy(), self.act_h.numpy())
+            act_n = self.act_h.numpy()
+            if self.head:  # the env takes [P*N, A] floats / [P*N, K] choices
+                act_n = act_n.reshape(P * N, -1)
+            self._views = (self.obs_h.numpy(), self.rew_h.numpy(), self.done_h.numpy(), act_n)
             self._signal, self._wait_fn, self._ctl = lib.agx_host_signal, lib.agx_host_wait, self.ctl_h.data_ptr()
             if self.multi:
                 self.n_wg = int(lib.agx_ppo_rollout_graph_workgroups(P, N))
@@ -768,6 +860,7 @@ class _EvalDriver:
             from .learner import vector_act_workspace
 
             vector_act_workspace(pop)
+        self._clip = pop.action_clip() if pop.gaussian else None  # made now: nothing may allocate while a launch waits
         self.obs = None
         self.stream = None  # a dedicated non-blocking stream, assigned by run_lockstep
         self._pipelined = False
@@ -804,6 +897,8 @@ class _EvalDriver:
                                                          self.ctl_h.data_ptr(), self.runner.timeout_s, tally,
                                                          self.stream.cuda_stream),
                        "agx_ppo_eval_multi_persistent")
+        elif self.head:  # the head's own launch (its act workspace and clip bounds were taken at construction)
+            self._launch_head(lib, n)
         elif self.desc is not None:
             _lib.check(lib.agx_ppo_eval_persistent(ctypes.byref(self.desc), self.P, self.N,
                                                    pop.params.data.data_ptr(), self.obs_h.data_ptr(), None,
@@ -824,6 +919,24 @@ class _EvalDriver:
         _pacing_begin()
         self.launch_step0 = self.step
         self.launched_to = self.step + n
+
+    def _launch_head(self, lib, n: int) -> None:
+        pop = self.pop
+        head = (self.P, self.N, pop.params.data.data_ptr(), self.obs_h.data_ptr(), self.act_h.data_ptr())
+        tail = (pop.env_base_d.data_ptr(), n, 0, pop.act_seed, self.counter0 + self.step, self.args_h.data_ptr(),
+                self.ctl_h.data_ptr(), self.runner.timeout_s, pop._act_ws[1].data_ptr(), self.stream.cuda_stream)
+        if pop.gaussian:
+            lo, hi = self._clip or (None, None)
+            _lib.check(lib.agx_ppo_eval_gauss_graph_persistent(ctypes.byref(pop.gauss_descriptor()), pop.spec.log_std,
+                                                               *head, _lib.ptr(lo), _lib.ptr(hi), *tail),
+                       "agx_ppo_eval_gauss_graph_persistent")
+        elif pop.multibinary:
+            _lib.check(lib.agx_ppo_eval_bern_graph_persistent(ctypes.byref(pop.bern_descriptor()), *head, *tail),
+                       "agx_ppo_eval_bern_graph_persistent")
+        else:
+            _lib.check(lib.agx_ppo_eval_multi_graph_persistent(ctypes.byref(pop.multi_descriptor()), pop.multi_head(),
+                                                               *head, *tail),
+                       "agx_ppo_eval_multi_graph_persistent")
 
     def request(self) -> None:
         """Start the policy step of vector step self.step."""
@@ -895,6 +1008,8 @@ class _EvalDriver:
         if self.persistent:
             obs_n, rew_n, done_n, act_n = self._views
             try:
+                if self.head and self.pop.multibinary:  # 0 / 1 bits in the space's dtype
+                    act_n = act_n.astype(self.pop.spec.action_dtype)
                 _, _, term, trunc, _ = self.env.step(act_n, out_obs=obs_n, out_rew=rew_n, out_done=done_n)
             except BaseException:
                 self.abort()

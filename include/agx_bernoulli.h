@@ -55,6 +55,30 @@ int agx_ppo_act_bern_graph(const agx_ppo_graph *net, int64_t P, int64_t N, const
                            float *entropy, int64_t out_agent_stride, int64_t *actions_flat,
                            const int64_t *agent_env_base, void *workspace, void *stream);
 
+/* Persistent rollout / evaluation of a MultiBinary population: the host-paced
+ * loops of agx_ppo_rollout_graph_persistent / agx_ppo_eval_graph_persistent
+ * (agx_graph.h: same agx_rollout_io steps, control block protocol and bytes,
+ * args bytes, workgroup count agx_ppo_rollout_graph_workgroups(P, N), Philox
+ * counters, AGX_ROLLOUT_ABORT / AGX_ROLLOUT_STOP) around
+ * agx_ppo_act_bern_graph's step, one launch per rollout.  A step's
+ * agx_rollout_io.actions is the int64 slot [..][n] (row r of agent p at
+ * (p slot_agent_stride + r) n) and actions_flat the int64 staging [P N n],
+ * both 0 / 1.  No step may stage a legal-action mask (AGX_EINVAL).  Every
+ * workgroup must be co-resident: AGX_EUNSUPPORTED beyond
+ * agx_ppo_rollout_bern_graph_max_workgroups() (this kernel's own occupancy).
+ * The net is checked as agx_ppo_act_bern_graph checks it; `workspace` as
+ * there. */
+int64_t agx_ppo_rollout_bern_graph_max_workgroups(void);
+int agx_ppo_rollout_bern_graph_persistent(const agx_ppo_graph *net, int64_t P, int64_t N, const float *params,
+                                          const agx_rollout_io *ios, int64_t nsteps, uint32_t base, uint64_t seed,
+                                          uint64_t counter0, void *args_host, agx_rollout_ctl *ctl, double timeout_s,
+                                          void *workspace, void *stream);
+int agx_ppo_eval_bern_graph_persistent(const agx_ppo_graph *net, int64_t P, int64_t N, const float *params,
+                                       const float *stage_obs, int64_t *actions_flat, const int64_t *agent_env_base,
+                                       int64_t nsteps, uint32_t base, uint64_t seed, uint64_t counter0,
+                                       void *args_host, agx_rollout_ctl *ctl, double timeout_s, void *workspace,
+                                       void *stream);
+
 /* The Bernoulli twin of agx_ppo_loss_fwd_bwd (agx.h; ppo.py:868-902):
  * num_minibatches minibatches of `batch` rows over n bits (1 <= n <=
  * AGX_PPO_GRAPH_MAX_ACTIONS, else AGX_EINVAL).

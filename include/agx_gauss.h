@@ -49,6 +49,37 @@ int agx_ppo_act_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, int64
                             float *actions_flat, const float *clip_low, const float *clip_high,
                             const int64_t *agent_env_base, void *workspace, void *stream);
 
+/* Persistent rollout / evaluation of a Box-action population: the host-paced
+ * loops of agx_ppo_rollout_graph_persistent / agx_ppo_eval_graph_persistent
+ * (agx_graph.h: same agx_rollout_io steps, control block protocol and bytes,
+ * args bytes, workgroup count agx_ppo_rollout_graph_workgroups(P, N), Philox
+ * counters counter0 + 1 + t / counter0 + t, AGX_ROLLOUT_ABORT / AGX_ROLLOUT_STOP)
+ * around agx_ppo_act_gauss_graph's step, one launch per rollout (replaces
+ * rollouts/on_policy.py:23-203's per-step forward).  A step's
+ * agx_rollout_io.actions is the float slot [..][A] (row n of agent p at
+ * (p slot_agent_stride + n) A) and actions_flat the float staging [P N A];
+ * the staging copy is clipped to clip_low / clip_high [A] (device, both or
+ * neither; on_policy.py:104-119 clips for the env), the slot holds the
+ * unclipped sample.  The step after the last runs unsampled at counter 0 and
+ * writes values only.  No step may stage a legal-action mask (AGX_EINVAL).
+ * Every workgroup must be co-resident: AGX_EUNSUPPORTED beyond
+ * agx_ppo_rollout_gauss_graph_max_workgroups() (this kernel's own occupancy).
+ * The net and log_std_off are checked as agx_ppo_act_gauss_graph checks them;
+ * `workspace` as there.  The evaluation writes the sampled, clipped actions
+ * to actions_flat only. */
+int64_t agx_ppo_rollout_gauss_graph_max_workgroups(void);
+int agx_ppo_rollout_gauss_graph_persistent(const agx_ppo_graph *net, int64_t log_std_off, int64_t P, int64_t N,
+                                           const float *params, const agx_rollout_io *ios, int64_t nsteps,
+                                           uint32_t base, uint64_t seed, uint64_t counter0, const float *clip_low,
+                                           const float *clip_high, void *args_host, agx_rollout_ctl *ctl,
+                                           double timeout_s, void *workspace, void *stream);
+int agx_ppo_eval_gauss_graph_persistent(const agx_ppo_graph *net, int64_t log_std_off, int64_t P, int64_t N,
+                                        const float *params, const float *stage_obs, float *actions_flat,
+                                        const float *clip_low, const float *clip_high, const int64_t *agent_env_base,
+                                        int64_t nsteps, uint32_t base, uint64_t seed, uint64_t counter0,
+                                        void *args_host, agx_rollout_ctl *ctl, double timeout_s, void *workspace,
+                                        void *stream);
+
 /* PPO.learn for a Gaussian head: agx_ppo_learn_graph (agx_graph.h) with the
  * actor output as the mean and the A log_std floats at log_std_off of every
  * agent's row.  log_std belongs to the actor clip group and to no layer: the

@@ -60,6 +60,31 @@ int agx_ppo_act_multi_graph(const agx_ppo_graph *net, agx_multi_head head, int64
                             float *log_probs, float *values, float *entropy, int64_t out_agent_stride,
                             int64_t *actions_flat, const int64_t *agent_env_base, void *workspace, void *stream);
 
+/* Persistent rollout / evaluation of a MultiDiscrete population: the
+ * host-paced loops of agx_ppo_rollout_graph_persistent /
+ * agx_ppo_eval_graph_persistent (agx_graph.h: same agx_rollout_io steps,
+ * control block protocol and bytes, args bytes, workgroup count
+ * agx_ppo_rollout_graph_workgroups(P, N), Philox counters, AGX_ROLLOUT_ABORT /
+ * AGX_ROLLOUT_STOP) around agx_ppo_act_multi_graph's step, one launch per
+ * rollout.  A step's agx_rollout_io.actions is the int64 slot [..][K] (row n
+ * of agent p at (p slot_agent_stride + n) K) and actions_flat the int64
+ * staging [P N K].  No step may stage a legal-action mask (AGX_EINVAL).
+ * Every workgroup must be co-resident: AGX_EUNSUPPORTED beyond
+ * agx_ppo_rollout_multi_graph_max_workgroups() (this kernel's own occupancy).
+ * The net and the head are checked as agx_ppo_act_multi_graph checks them;
+ * `workspace` as there.  With K = 1 the rollout equals
+ * agx_ppo_rollout_graph_persistent's at n_actions = n_0 bit for bit. */
+int64_t agx_ppo_rollout_multi_graph_max_workgroups(void);
+int agx_ppo_rollout_multi_graph_persistent(const agx_ppo_graph *net, agx_multi_head head, int64_t P, int64_t N,
+                                           const float *params, const agx_rollout_io *ios, int64_t nsteps,
+                                           uint32_t base, uint64_t seed, uint64_t counter0, void *args_host,
+                                           agx_rollout_ctl *ctl, double timeout_s, void *workspace, void *stream);
+int agx_ppo_eval_multi_graph_persistent(const agx_ppo_graph *net, agx_multi_head head, int64_t P, int64_t N,
+                                        const float *params, const float *stage_obs, int64_t *actions_flat,
+                                        const int64_t *agent_env_base, int64_t nsteps, uint32_t base, uint64_t seed,
+                                        uint64_t counter0, void *args_host, agx_rollout_ctl *ctl, double timeout_s,
+                                        void *workspace, void *stream);
+
 /* The multi-categorical twin of agx_ppo_loss_fwd_bwd (agx.h; ppo.py:868-902):
  * num_minibatches minibatches of `batch` rows.
  *   logits [nmb batch][L], value [nmb batch]                    (network outputs, raw)
