@@ -489,12 +489,8 @@ class PPO:
         if action_mask is not None:
             mask = torch.as_tensor(np.asarray(action_mask), device=self.device).reshape(n, pop.spec.n_actions)
             mask = (mask != 0).to(torch.uint8).contiguous()
-        if pop.gaussian:
-            return self._get_action_gauss(o, action_mask)
-        if pop.multidiscrete:
-            return self._get_action_multi(o, mask)
-        if pop.multibinary:
-            return self._get_action_bern(o, mask)
+        if pop.head is not None:
+            return self._get_action_head(o, mask)
         out = dict(actions=torch.empty(n, dtype=torch.int64, device=self.device),
                    log_probs=torch.empty(n, device=self.device), values=torch.empty(n, device=self.device),
                    entropy=torch.empty(n, device=self.device))
@@ -531,75 +527,35 @@ class PPO:
                       out["entropy"].data_ptr(), 0, None, None, _lib.stream())
         return tuple(out[k].cpu().numpy() for k in ("actions", "log_probs", "entropy", "values"))
 
-    def _get_action_gauss(self, o: torch.Tensor, action_mask):
-        """get_action of a Box policy: one agx_ppo_act_gauss_graph launch on
-        this agent's row -> float actions [n, A]; outside training the
-        returned actions are clipped to the bounds (ppo.py:604-614), the
-        log-prob stays the unclipped sample's."""
-        if action_mask is not None:
-            raise ValueError("action masks apply to Discrete action spaces")
+    def _get_action_head(self, o: torch.Tensor, mask):
+        """get_action of a Box / MultiDiscrete / MultiBinary policy: one
+        agx_ppo_act_<stem>_graph launch on this agent's row -> float actions
+        [n, A], int64 choices [n, K] or 0 / 1 bits [n, bits] in the space's
+        dtype; ``mask``: the flat uint8 mask [n, L] of an int head, or None.
+        Outside training a Box policy's returned actions are clipped to the
+        bounds (ppo.py:604-614), the log-prob stays the unclipped sample's."""
+        from ..population.learner import head_act
+
         pop = self.population
-        n, A = o.shape[0], pop.spec.n_actions
-        gdesc = pop.gauss_descriptor()
+        head, n = pop.head, o.shape[0]
+        gdesc = pop.head_descriptor()
         self._counter += 1
         ws = getattr(self, "_act_graph_ws", None)
         if ws is None or ws[0] is not gdesc or ws[1] < n:
-            nbytes = _lib.load().agx_ppo_act_gauss_graph_workspace_bytes(ctypes.byref(gdesc), 1, n)
+            size = getattr(_lib.load(), f"agx_ppo_act_{head.stem}_graph_workspace_bytes")
+            nbytes = size(ctypes.byref(gdesc), 1, n)
             ws = self._act_graph_ws = (gdesc, n, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
-        actions = torch.empty(n, A, device=self.device)
+        actions = torch.empty(n, pop.act_width, dtype=head.dtype, device=self.device)
         logp, value, ent = (torch.empty(n, device=self.device) for _ in range(3))
         clip = None if self.training else pop.action_clip()
-        env_copy = torch.empty(n, A, device=self.device) if clip is not None else None
-        _lib.call("agx_ppo_act_gauss_graph", ctypes.byref(gdesc), pop.spec.log_std, 1, n,
-                  pop.params.data[self.row].data_ptr(), o.data_ptr(), 0, 1,
-                  pop.act_seed + 7919 * pop.agent_ids[self.row], (1 << 40) + self._counter, actions.data_ptr(),
-                  logp.data_ptr(), value.data_ptr(), ent.data_ptr(), 0, _lib.ptr(env_copy),
-                  _lib.ptr(clip[0]) if clip else None, _lib.ptr(clip[1]) if clip else None, None, ws[2].data_ptr(),
-                  _lib.stream())
-        a = env_copy if env_copy is not None else actions
-        return tuple(t.cpu().numpy() for t in (a, logp, ent, value))
-
-    def _get_action_multi(self, o: torch.Tensor, mask):
-        """get_action of a MultiDiscrete policy: one agx_ppo_act_multi_graph
-        launch on this agent's row -> int64 actions [n, K]; ``mask``: the flat
-        uint8 mask [n, L] or None."""
-        from ..kernels import ppo_act_multi_graph
-
-        pop = self.population
-        n, K = o.shape[0], len(pop.spec.nvec)
-        gdesc = pop.multi_descriptor()
-        self._counter += 1
-        ws = getattr(self, "_act_graph_ws", None)
-        if ws is None or ws[0] is not gdesc or ws[1] < n:
-            nbytes = _lib.load().agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(gdesc), 1, n)
-            ws = self._act_graph_ws = (gdesc, n, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
-        actions = torch.empty(n, K, dtype=torch.int64, device=self.device)
-        logp, value, ent = (torch.empty(n, device=self.device) for _ in range(3))
-        ppo_act_multi_graph(gdesc, pop.multi_head(), 1, n, pop.params.data[self.row], o, 0, ws[2], sample=True,
-                            seed=pop.act_seed + 7919 * pop.agent_ids[self.row], counter=(1 << 40) + self._counter,
-                            mask=mask, actions=actions, log_probs=logp, values=value, entropy=ent)
-        return tuple(t.cpu().numpy() for t in (actions, logp, ent, value))
-
-    def _get_action_bern(self, o: torch.Tensor, mask):
-        """get_action of a MultiBinary policy: one agx_ppo_act_bern_graph
-        launch on this agent's row -> 0 / 1 actions [n, bits] in the space's
-        dtype; ``mask``: the flat uint8 mask [n, bits] or None."""
-        from ..kernels import ppo_act_bern_graph
-
-        pop = self.population
-        n, nb = o.shape[0], pop.spec.n_actions
-        gdesc = pop.bern_descriptor()
-        self._counter += 1
-        ws = getattr(self, "_act_graph_ws", None)
-        if ws is None or ws[0] is not gdesc or ws[1] < n:
-            nbytes = _lib.load().agx_ppo_act_bern_graph_workspace_bytes(ctypes.byref(gdesc), 1, n)
-            ws = self._act_graph_ws = (gdesc, n, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
-        actions = torch.empty(n, nb, dtype=torch.int64, device=self.device)
-        logp, value, ent = (torch.empty(n, device=self.device) for _ in range(3))
-        ppo_act_bern_graph(gdesc, 1, n, pop.params.data[self.row], o, 0, ws[2], sample=True,
-                           seed=pop.act_seed + 7919 * pop.agent_ids[self.row], counter=(1 << 40) + self._counter,
-                           mask=mask, actions=actions, log_probs=logp, values=value, entropy=ent)
-        a = actions.cpu().numpy().astype(pop.spec.action_dtype)
+        env_copy = torch.empty_like(actions) if clip is not None else None
+        head_act(head, gdesc, pop.head_args(), 1, n, pop.params.data[self.row], o, 0, ws[2], sample=True,
+                 seed=pop.act_seed + 7919 * pop.agent_ids[self.row], counter=(1 << 40) + self._counter,
+                 action_mask=mask, actions=actions, log_probs=logp, values=value, entropy=ent,
+                 actions_flat=env_copy, clip=clip)
+        a = (env_copy if env_copy is not None else actions).cpu().numpy()
+        if pop.multibinary:
+            a = a.astype(pop.spec.action_dtype)
         return (a,) + tuple(t.cpu().numpy() for t in (logp, ent, value))
 
     @property

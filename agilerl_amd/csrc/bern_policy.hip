@@ -12,7 +12,7 @@
 #include "../../include/agx_bernoulli.h"
 #include "bern_head.h"
 #include "graph_net.h"
-#include "head_rollout.h"
+#include "head_policy.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kGT) void ppo_act_bern_graph_kernel(const GActArgs 
     }
 }
 
-// bern_step as the step of head_rollout.h's persistent loop: the step's action
+// bern_step as the step of head_policy.h's persistent loop: the step's action
 // slot / host staging are int64 [.., n]
 struct BernRolloutHead {
     __device__ __forceinline__ void step(const ActArgs &g, int n, int lda, int ldv, const float *lgp, const float *vp,
@@ -166,11 +166,7 @@ __global__ __launch_bounds__(256) void ppo_bern_loss_kernel(
         Acc one;
         loss_sample(lp, old_logp[src], adv[src], ret[src], old_v[src], value[o], H, k, gl, gv, one);
         if (sub == 0) {
-            acc.pg += one.pg;
-            acc.vl += one.vl;
-            acc.h += one.h;
-            acc.kl += one.kl;
-            acc.cf += one.cf;
+            acc.add(one);
             g_value[o] = gv;
         }
         // a masked logit passes nothing back (the reference's torch.where)
@@ -185,11 +181,17 @@ __global__ __launch_bounds__(256) void ppo_bern_loss_kernel(
 
 using namespace agx;
 
+namespace {
+// the rules of every Bernoulli entry point for the net (the head has no parameters) -> the plan
+int bern_plan(const agx_ppo_graph *net, GArgs &full, BernRolloutHead &, const char *) {
+    return plan_graph(net, 1, full);
+}
+}  // namespace
+
 extern "C" size_t agx_ppo_act_bern_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t N) {
     GArgs full{};
-    GActArgs a{};
     if (!net || P <= 0 || N <= 0 || plan_graph(net, 1, full) != AGX_OK) return 0;
-    return (size_t)P * ceil_div(N, kActRows) * act_plan(full, a) * sizeof(float);
+    return head_act_workspace_bytes(full, P, N);
 }
 
 extern "C" int agx_ppo_act_bern_graph(const agx_ppo_graph *net, int64_t P, int64_t N, const float *params,
@@ -198,26 +200,17 @@ extern "C" int agx_ppo_act_bern_graph(const agx_ppo_graph *net, int64_t P, int64
                                       int64_t *actions, float *log_probs, float *values, float *entropy,
                                       int64_t out_agent_stride, int64_t *actions_flat, const int64_t *agent_env_base,
                                       void *workspace, void *stream) {
-    AGX_REQUIRE(net && params && obs && workspace && P > 0 && N > 0 && P <= 65535,
-                "agx_ppo_act_bern_graph: bad arguments");
+    const char *who = "agx_ppo_act_bern_graph";
+    AGX_REQUIRE(net && params && obs && workspace && P > 0 && N > 0 && P <= 65535, "%s: bad arguments", who);
     GArgs full{};
-    const int rc = plan_graph(net, 1, full);
-    if (rc != AGX_OK) return rc;
-    GActArgs a{};
-    act_plan(full, a);
-    a.ws = static_cast<float *>(workspace);
+    BernRolloutHead r{};
+    if (int rc = bern_plan(net, full, r, who)) return rc;
     const ActArgs g = act_step_args(P, N, params, obs, obs_agent_stride, action_mask, mask_agent_stride, sample, seed,
                                     counter, nullptr, log_probs, values, entropy, out_agent_stride, nullptr,
                                     agent_env_base);
-    BernOut h{};
-    h.act_out = reinterpret_cast<long long *>(actions);
-    h.act_flat = reinterpret_cast<long long *>(actions_flat);
-    dim3 grid((unsigned)ceil_div(N, kActRows), (unsigned)P);
-    if (const size_t dyn = act_plan_few(ppo_act_bern_graph_kernel<true>, a))
-        ppo_act_bern_graph_kernel<true><<<grid, kGT, dyn, as_stream(stream)>>>(a, g, h);
-    else
-        ppo_act_bern_graph_kernel<false><<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
-    return check_launch("agx_ppo_act_bern_graph");
+    const BernOut h{reinterpret_cast<long long *>(actions), reinterpret_cast<long long *>(actions_flat)};
+    return launch_head_act(ppo_act_bern_graph_kernel<true>, ppo_act_bern_graph_kernel<false>, full, g, P, N, workspace,
+                           stream, h, who);
 }
 
 // ---------------------------------------------------------------------------
@@ -232,18 +225,10 @@ extern "C" int agx_ppo_rollout_bern_graph_persistent(const agx_ppo_graph *net, i
                                                      uint32_t base, uint64_t seed, uint64_t counter0, void *args_host,
                                                      agx_rollout_ctl *ctl, double timeout_s, void *workspace,
                                                      void *stream) {
-    const char *who = "agx_ppo_rollout_bern_graph_persistent";
-    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
-                                  who))
-        return rc;
-    GArgs full{};
-    if (int rc = plan_graph(net, 1, full)) return rc;
-    ActArgs *steps = static_cast<ActArgs *>(args_host);
-    if (int rc = fill_head_rollout_steps(steps, net->obs_dim, net->n_actions, P, N, params, ios, nsteps, seed,
-                                         counter0, who))
-        return rc;
-    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream,
-                                  BernRolloutHead{}, who);
+    auto plan = [&](GArgs &full, BernRolloutHead &h, const char *who) { return bern_plan(net, full, h, who); };
+    return head_rollout_persistent<BernRolloutHead>(net, plan, P, N, params, ios, nsteps, base, seed, counter0,
+                                                    args_host, ctl, timeout_s, workspace, stream,
+                                                    "agx_ppo_rollout_bern_graph_persistent");
 }
 
 extern "C" int agx_ppo_eval_bern_graph_persistent(const agx_ppo_graph *net, int64_t P, int64_t N, const float *params,
@@ -252,17 +237,11 @@ extern "C" int agx_ppo_eval_bern_graph_persistent(const agx_ppo_graph *net, int6
                                                   uint64_t seed, uint64_t counter0, void *args_host,
                                                   agx_rollout_ctl *ctl, double timeout_s, void *workspace,
                                                   void *stream) {
-    const char *who = "agx_ppo_eval_bern_graph_persistent";
-    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
-                                  nsteps, base, timeout_s, who))
-        return rc;
-    GArgs full{};
-    if (int rc = plan_graph(net, 1, full)) return rc;
-    ActArgs *steps = static_cast<ActArgs *>(args_host);
-    fill_head_eval_steps(steps, net->obs_dim, net->n_actions, P, N, params, stage_obs, actions_flat, agent_env_base,
-                         nsteps, seed, counter0);
-    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream,
-                                  BernRolloutHead{}, who);
+    auto plan = [&](GArgs &full, BernRolloutHead &h, const char *who) { return bern_plan(net, full, h, who); };
+    return head_eval_persistent<BernRolloutHead>(net, plan, P, N, params, stage_obs, actions_flat, agent_env_base,
+                                                 nsteps, base, seed, counter0, args_host, ctl, timeout_s, workspace,
+                                                 stream,
+                                                 "agx_ppo_eval_bern_graph_persistent");
 }
 
 extern "C" int agx_ppo_bern_loss_fwd_bwd(const float *logits, const float *value, int32_t n, const int64_t *actions,
@@ -278,15 +257,7 @@ extern "C" int agx_ppo_bern_loss_fwd_bwd(const float *logits, const float *value
     AGX_REQUIRE(logits && value && actions && old_logp && adv && ret && old_value && g_logits && g_value,
                 "agx_ppo_bern_loss_fwd_bwd: null pointer");
     if (num_minibatches == 0) return AGX_OK;
-    LossCoef k;
-    k.clip = clip_coef;
-    k.lo = 1.f - clip_coef;
-    k.hi = 1.f + clip_coef;
-    k.inv_b = 1.f / (float)batch;
-    k.vf = vf_coef;
-    k.ent = ent_coef;
-    k.vf_half_inv_b = vf_coef * 0.5f * k.inv_b;
-    k.g_h = -ent_coef * k.inv_b;
+    const LossCoef k = loss_coef(batch, clip_coef, vf_coef, ent_coef);
     const int64_t blocks = ceil_div(num_minibatches, 4);
     AGX_REQUIRE(blocks < ((int64_t)1 << 31), "agx_ppo_bern_loss_fwd_bwd: too many minibatches");
     ppo_bern_loss_kernel<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(

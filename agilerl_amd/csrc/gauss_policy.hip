@@ -7,7 +7,7 @@
 #include "../../include/agx_gauss.h"
 #include "gauss_head.h"
 #include "graph_net.h"
-#include "head_rollout.h"
+#include "head_policy.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kGT) void ppo_act_gauss_graph_kernel(const GActArgs
     }
 }
 
-// gauss_step as the step of head_rollout.h's persistent loop: the step's action
+// gauss_step as the step of head_policy.h's persistent loop: the step's action
 // slot / host staging are floats [.., A], the staging copy clipped to lo / hi
 struct GaussRolloutHead {
     long long log_std_off;
@@ -169,11 +169,7 @@ __global__ __launch_bounds__(256) void ppo_gauss_loss_kernel(
         Acc one;
         loss_sample(lp, old_logp[src], adv[src], ret[src], old_v[src], value[o], H, k, gl, gv, one);
         if (sub == 0) {
-            acc.pg += one.pg;
-            acc.vl += one.vl;
-            acc.h += one.h;
-            acc.kl += one.kl;
-            acc.cf += one.cf;
+            acc.add(one);
             g_value[o] = gv;
         }
         const float z0 = a0 - mu0, z1 = a1 - mu1;
@@ -202,11 +198,27 @@ __global__ __launch_bounds__(256) void ppo_gauss_loss_kernel(
 
 using namespace agx;
 
+namespace {
+// the layer list of a Gaussian actor-critic: its log_std floats are the part
+// of the parameter row that no layer owns
+int gauss_graph(const agx_ppo_graph *net, GArgs &full) { return plan_graph(net, 1, full, net->n_actions); }
+
+// the rules of every Gaussian entry point for the net and the head -> the plan and the persistent kernel's head
+int gauss_plan(const agx_ppo_graph *net, int64_t log_std_off, const float *clip_low, const float *clip_high,
+               GArgs &full, GaussRolloutHead &h, const char *who) {
+    AGX_REQUIRE(!clip_low == !clip_high, "%s: clip_low and clip_high come together", who);
+    if (int rc = gauss_graph(net, full)) return rc;
+    AGX_REQUIRE(log_std_off >= 0 && log_std_off + net->n_actions <= net->n_params,
+                "%s: log_std outside the parameter row", who);
+    h = GaussRolloutHead{(long long)log_std_off, clip_low, clip_high};
+    return AGX_OK;
+}
+}  // namespace
+
 extern "C" size_t agx_ppo_act_gauss_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t N) {
     GArgs full{};
-    GActArgs a{};
-    if (!net || P <= 0 || N <= 0 || plan_graph(net, 1, full, net->n_actions) != AGX_OK) return 0;
-    return (size_t)P * ceil_div(N, kActRows) * act_plan(full, a) * sizeof(float);
+    if (!net || P <= 0 || N <= 0 || gauss_graph(net, full) != AGX_OK) return 0;
+    return head_act_workspace_bytes(full, P, N);
 }
 
 extern "C" int agx_ppo_act_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, int64_t P, int64_t N,
@@ -215,26 +227,16 @@ extern "C" int agx_ppo_act_gauss_graph(const agx_ppo_graph *net, int64_t log_std
                                        float *values, float *entropy, int64_t out_agent_stride, float *actions_flat,
                                        const float *clip_low, const float *clip_high, const int64_t *agent_env_base,
                                        void *workspace, void *stream) {
-    AGX_REQUIRE(net && params && obs && workspace && P > 0 && N > 0 && P <= 65535,
-                "agx_ppo_act_gauss_graph: bad arguments");
-    AGX_REQUIRE(!clip_low == !clip_high, "agx_ppo_act_gauss_graph: clip_low and clip_high come together");
+    const char *who = "agx_ppo_act_gauss_graph";
+    AGX_REQUIRE(net && params && obs && workspace && P > 0 && N > 0 && P <= 65535, "%s: bad arguments", who);
     GArgs full{};
-    const int rc = plan_graph(net, 1, full, net->n_actions);
-    if (rc != AGX_OK) return rc;
-    AGX_REQUIRE(log_std_off >= 0 && log_std_off + net->n_actions <= net->n_params,
-                "agx_ppo_act_gauss_graph: log_std outside the parameter row");
-    GActArgs a{};
-    act_plan(full, a);
-    a.ws = static_cast<float *>(workspace);
+    GaussRolloutHead r{};
+    if (int rc = gauss_plan(net, log_std_off, clip_low, clip_high, full, r, who)) return rc;
     const ActArgs g = act_step_args(P, N, params, obs, obs_agent_stride, nullptr, 0, sample, seed, counter, nullptr,
                                     log_probs, values, entropy, out_agent_stride, nullptr, agent_env_base);
-    const GaussHead h{(long long)log_std_off, actions, actions_flat, clip_low, clip_high};
-    dim3 grid((unsigned)ceil_div(N, kActRows), (unsigned)P);
-    if (const size_t dyn = act_plan_few(ppo_act_gauss_graph_kernel<true>, a))
-        ppo_act_gauss_graph_kernel<true><<<grid, kGT, dyn, as_stream(stream)>>>(a, g, h);
-    else
-        ppo_act_gauss_graph_kernel<false><<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
-    return check_launch("agx_ppo_act_gauss_graph");
+    const GaussHead h{r.log_std_off, actions, actions_flat, clip_low, clip_high};
+    return launch_head_act(ppo_act_gauss_graph_kernel<true>, ppo_act_gauss_graph_kernel<false>, full, g, P, N,
+                           workspace, stream, h, who);
 }
 
 // ---------------------------------------------------------------------------
@@ -244,37 +246,18 @@ extern "C" int64_t agx_ppo_rollout_gauss_graph_max_workgroups(void) {
     return head_rollout_max_workgroups<GaussRolloutHead>();
 }
 
-namespace {
-// agx_ppo_act_gauss_graph's rules for the net and the head -> the plan
-int gauss_persistent_plan(const agx_ppo_graph *net, int64_t log_std_off, const float *clip_low,
-                          const float *clip_high, GArgs &full, const char *who) {
-    AGX_REQUIRE(!clip_low == !clip_high, "%s: clip_low and clip_high come together", who);
-    const int rc = plan_graph(net, 1, full, net->n_actions);
-    if (rc != AGX_OK) return rc;
-    AGX_REQUIRE(log_std_off >= 0 && log_std_off + net->n_actions <= net->n_params,
-                "%s: log_std outside the parameter row", who);
-    return AGX_OK;
-}
-}  // namespace
-
 extern "C" int agx_ppo_rollout_gauss_graph_persistent(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
                                                       int64_t N, const float *params, const agx_rollout_io *ios,
                                                       int64_t nsteps, uint32_t base, uint64_t seed,
                                                       uint64_t counter0, const float *clip_low,
                                                       const float *clip_high, void *args_host, agx_rollout_ctl *ctl,
                                                       double timeout_s, void *workspace, void *stream) {
-    const char *who = "agx_ppo_rollout_gauss_graph_persistent";
-    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
-                                  who))
-        return rc;
-    GArgs full{};
-    if (int rc = gauss_persistent_plan(net, log_std_off, clip_low, clip_high, full, who)) return rc;
-    ActArgs *steps = static_cast<ActArgs *>(args_host);
-    if (int rc = fill_head_rollout_steps(steps, net->obs_dim, net->n_actions, P, N, params, ios, nsteps, seed,
-                                         counter0, who))
-        return rc;
-    const GaussRolloutHead h{(long long)log_std_off, clip_low, clip_high};
-    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
+    auto plan = [&](GArgs &full, GaussRolloutHead &h, const char *who) {
+        return gauss_plan(net, log_std_off, clip_low, clip_high, full, h, who);
+    };
+    return head_rollout_persistent<GaussRolloutHead>(net, plan, P, N, params, ios, nsteps, base, seed, counter0,
+                                                     args_host, ctl, timeout_s, workspace, stream,
+                                                     "agx_ppo_rollout_gauss_graph_persistent");
 }
 
 extern "C" int agx_ppo_eval_gauss_graph_persistent(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
@@ -284,17 +267,13 @@ extern "C" int agx_ppo_eval_gauss_graph_persistent(const agx_ppo_graph *net, int
                                                    int64_t nsteps, uint32_t base, uint64_t seed, uint64_t counter0,
                                                    void *args_host, agx_rollout_ctl *ctl, double timeout_s,
                                                    void *workspace, void *stream) {
-    const char *who = "agx_ppo_eval_gauss_graph_persistent";
-    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
-                                  nsteps, base, timeout_s, who))
-        return rc;
-    GArgs full{};
-    if (int rc = gauss_persistent_plan(net, log_std_off, clip_low, clip_high, full, who)) return rc;
-    ActArgs *steps = static_cast<ActArgs *>(args_host);
-    fill_head_eval_steps(steps, net->obs_dim, net->n_actions, P, N, params, stage_obs, actions_flat, agent_env_base,
-                         nsteps, seed, counter0);
-    const GaussRolloutHead h{(long long)log_std_off, clip_low, clip_high};
-    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
+    auto plan = [&](GArgs &full, GaussRolloutHead &h, const char *who) {
+        return gauss_plan(net, log_std_off, clip_low, clip_high, full, h, who);
+    };
+    return head_eval_persistent<GaussRolloutHead>(net, plan, P, N, params, stage_obs, actions_flat, agent_env_base,
+                                                  nsteps, base, seed, counter0, args_host, ctl, timeout_s, workspace,
+                                                  stream,
+                                                  "agx_ppo_eval_gauss_graph_persistent");
 }
 
 extern "C" int agx_ppo_gauss_loss_fwd_bwd(const float *mean, const float *value, const float *log_std,
@@ -311,15 +290,7 @@ extern "C" int agx_ppo_gauss_loss_fwd_bwd(const float *mean, const float *value,
                     g_log_std,
                 "agx_ppo_gauss_loss_fwd_bwd: null pointer");
     if (num_minibatches == 0) return AGX_OK;
-    LossCoef k;
-    k.clip = clip_coef;
-    k.lo = 1.f - clip_coef;
-    k.hi = 1.f + clip_coef;
-    k.inv_b = 1.f / (float)batch;
-    k.vf = vf_coef;
-    k.ent = ent_coef;
-    k.vf_half_inv_b = vf_coef * 0.5f * k.inv_b;
-    k.g_h = -ent_coef * k.inv_b;
+    const LossCoef k = loss_coef(batch, clip_coef, vf_coef, ent_coef);
     const int64_t blocks = ceil_div(num_minibatches, 4);
     AGX_REQUIRE(blocks < ((int64_t)1 << 31), "agx_ppo_gauss_loss_fwd_bwd: too many minibatches");
     ppo_gauss_loss_kernel<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(

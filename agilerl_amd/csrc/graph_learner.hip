@@ -47,7 +47,7 @@
 // one target word (bit off_k + a_k per component, gact as the categorical
 // index: 4 bytes per row) and the loss row pass walks the K components
 // (GArgs::mk / mn, by value in the kernel arguments) with the lanes outside the
-// component neutral in row_max / row_sum, as multi_policy.hip's multi_step.
+// component neutral in row_max / row_sum, as multi_policy.hip's MultiHead::step.
 // For K = 1 the pass runs the categorical pass's float operations in its order.
 //
 // kBern: the Bernoulli head of a MultiBinary action space

@@ -1,8 +1,9 @@
-// Persistent rollout / evaluation of the non-categorical PPO heads (Gaussian,
-// multi-categorical, Bernoulli): ppo_rollout_graph_persistent_kernel's
-// host-paced loop (graph_rollout.hip) written once over the head's step, and
-// the host side that plans and launches it.  Each head's .hip includes this
-// header and instantiates the kernel with its own Head:
+// What the Gaussian, multi-categorical and Bernoulli PPO heads share over a
+// runtime layer list: the persistent rollout / evaluation launch (rollout.h's
+// host-paced loop, ppo_rollout_graph_persistent_kernel's of graph_rollout.hip,
+// written once over the head's step) and the host side that plans and launches
+// it and the heads' per-step kernels.  Each head's .hip includes this header
+// and instantiates the persistent kernel with its own Head:
 //
 //   struct Head {  // passed by value to the kernel
 //       // the head's step of rows [0, nrow) of agent p's row block n0 over the
@@ -13,9 +14,15 @@
 //                            const float *pr, int p, int n0, int nrow) const;
 //   };
 //
-// The steps carry no legal-action mask (ActArgs.mask is null): the head steps
-// read a mask with plain loads, which a host staging rewritten inside one
-// launch does not allow.
+// The per-step kernels (ppo_act_{gauss,multi,bern}_graph_kernel) stay in the
+// heads' files, each with its own argument struct: written as one template over
+// this Head, with the actions routed through ActArgs, the Gaussian and the
+// Bernoulli launch measured 1.6 % and 0.5 % slower (profiles/head_policy_ab.md).
+// Only their host launcher is shared (launch_head_act).
+//
+// The persistent steps carry no legal-action mask (ActArgs.mask is null): the
+// head steps read a mask with plain loads, which a host staging rewritten
+// inside one launch does not allow.
 #pragma once
 
 #include "graph_net.h"
@@ -24,13 +31,15 @@
 namespace agx {
 namespace {
 
-// Step t: wait for the host's release, then the step's ActArgs (host memory):
-// the observation rows from the host staging (system-scope loads) into this
-// block's scratch / LDS tile and the rollout slot, the previous step's reward /
-// done into slot t-1 with the episode accounting, and (act) the forward + the
-// head's step, whose actions go to the host staging with system-scope stores;
-// then this block's done word.  FEW: the block's 16 rows through few_forward's
-// LDS tiles (act_plan_few).
+// Persistent rollout / evaluation (agx_ppo_rollout_*_graph_persistent,
+// agx_ppo_eval_*_graph_persistent): agx_ppo_rollout_persistent's host-paced loop
+// (learner.hip) around the head's step.  Step t: wait for the
+// host's release, then the step's ActArgs (host memory): the observation rows
+// from the host staging (system-scope loads) into this block's scratch / LDS
+// tile and the rollout slot, the previous step's reward / done into slot t-1
+// with the episode accounting, and (act) the forward + the head's step, whose
+// actions go to the host staging with system-scope stores; then this block's
+// done word.
 template <bool FEW, class Head>
 __global__ __launch_bounds__(kGT) void ppo_rollout_head_persistent_kernel(const GActArgs ga, const ActArgs *steps,
                                                                           int nsteps, agx_rollout_ctl *ctl,
@@ -62,6 +71,8 @@ __global__ __launch_bounds__(kGT) void ppo_rollout_head_persistent_kernel(const 
         if (!s_go) return;
         const ActArgs g = s_args;
         const int nrow = g.N - n0 < ga.rows ? g.N - n0 : ga.rows;
+        // the host staging of this block's rows (one round trip), then the
+        // previous step's reward / done and the episode accounting
         const float *ob = g.obs + (size_t)p * g.obs_pstride + (size_t)n0 * D;
         for (int i = tid; i < nrow * D; i += kGT) {
             const float x = ld_sys(ob + i);
@@ -82,8 +93,8 @@ __global__ __launch_bounds__(kGT) void ppo_rollout_head_persistent_kernel(const 
             const float *pr = g.params + (size_t)p * ga.n;
             const GLay &La = ga.L[ga.aout], &Lc = ga.L[ga.cout];
             if constexpr (FEW) {
-                const auto prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pr), 0,
-                                                                   __builtin_amdgcn_readfirstlane(ga.n * 4), 0x00020000);
+                const auto prs = __builtin_amdgcn_make_buffer_rsrc(
+                    const_cast<float *>(pr), 0, __builtin_amdgcn_readfirstlane(ga.n * 4), 0x00020000);
                 few_forward(ga.L, ga.nl, gdyn, pr, prs, ga.oc, ga.ld0, nullptr);
                 h.step(g, ga.A, La.ld, Lc.ld, gdyn + La.yr, gdyn + Lc.yr, pr, p, n0, nrow);
             } else {
@@ -96,7 +107,32 @@ __global__ __launch_bounds__(kGT) void ppo_rollout_head_persistent_kernel(const 
     }
 }
 
-// co-resident workgroups of Head's kernel (its general form, no dynamic LDS)
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+// scratch of a per-step or persistent launch over the planned layer list `full`
+inline size_t head_act_workspace_bytes(const GArgs &full, int64_t P, int64_t N) {
+    GActArgs a{};
+    return (size_t)P * ceil_div(N, kActRows) * act_plan(full, a) * sizeof(float);
+}
+
+// one per-step launch over `full` of a head's kernel pair (few: its few-row form, taken when its tiles
+// fit) with the head's argument struct h
+template <class Kernel, class Args>
+int launch_head_act(Kernel few, Kernel general, const GArgs &full, const ActArgs &g, int64_t P, int64_t N,
+                    void *workspace, void *stream, const Args &h, const char *who) {
+    GActArgs a{};
+    act_plan(full, a);
+    a.ws = static_cast<float *>(workspace);
+    dim3 grid((unsigned)ceil_div(N, kActRows), (unsigned)P);
+    if (const size_t dyn = act_plan_few(few, a))
+        few<<<grid, kGT, dyn, as_stream(stream)>>>(a, g, h);
+    else
+        general<<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
+    return check_launch(who);
+}
+
+// co-resident workgroups of Head's persistent kernel (its general form, no dynamic LDS)
 template <class Head>
 int64_t head_rollout_max_workgroups() {
     static int occ = -1;
@@ -110,8 +146,7 @@ int64_t head_rollout_max_workgroups() {
     return (int64_t)occ * cu_count();
 }
 
-// launch_graph_persistent (graph_rollout.hip) for Head's kernel over the
-// planned layer list `full`: the same grid, control block and choice of form
+// one persistent launch of Head's kernel over `full`, every workgroup resident
 template <class Head>
 int launch_head_persistent(const GArgs &full, int64_t P, int64_t N, const ActArgs *steps, int64_t nsteps,
                            uint32_t base, agx_rollout_ctl *ctl, double timeout_s, void *workspace, void *stream,
@@ -147,30 +182,51 @@ int launch_head_persistent(const GArgs &full, int64_t P, int64_t N, const ActArg
     return check_launch(who);
 }
 
-// the steps of a rollout launch (agx_ppo_rollout_graph_persistent's): step t
-// samples with counter0 + 1 + t, the step after the last runs unsampled at
-// counter 0 and writes values only; no mask
-inline int fill_head_rollout_steps(ActArgs *steps, int D, int A, int64_t P, int64_t N, const float *params,
-                                   const agx_rollout_io *ios, int64_t nsteps, uint64_t seed, uint64_t counter0,
-                                   const char *who) {
+// The rollout entry of a head (agx_ppo_rollout_{gauss,multi,bern}_graph_persistent).
+// plan(full, h, who): the head's checks of the net
+// and the head -> the planned layer list and the kernel's Head.  Step t samples
+// with counter0 + 1 + t, the step after the last runs unsampled at counter 0
+// and writes values only.
+template <class Head, class Plan>
+int head_rollout_persistent(const agx_ppo_graph *net, Plan plan, int64_t P, int64_t N, const float *params,
+                            const agx_rollout_io *ios, int64_t nsteps, uint32_t base, uint64_t seed,
+                            uint64_t counter0, void *args_host, agx_rollout_ctl *ctl, double timeout_s,
+                            void *workspace, void *stream, const char *who) {
+    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
+                                  who))
+        return rc;
+    GArgs full{};
+    Head h{};
+    if (int rc = plan(full, h, who)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
     for (int64_t t = 0; t < nsteps; ++t) {
         const bool last = t + 1 == nsteps;
         if (int rc = check_rollout_io(ios + t, 1, params, who)) return rc;
         AGX_REQUIRE(!ios[t].stage_mask && !ios[t].mask_slot, "%s: step %lld stages a legal-action mask", who,
                     (long long)t);
-        fill_rollout_args(steps[t], D, A, P, N, params, ios + t, 1, last ? 0 : 1, seed,
+        fill_rollout_args(steps[t], net->obs_dim, net->n_actions, P, N, params, ios + t, 1, last ? 0 : 1, seed,
                           last ? 0 : counter0 + 1 + (uint64_t)t);
     }
-    return AGX_OK;
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
 }
 
-// the steps of an evaluation launch: sampled actions to the staging only, counters counter0 + t
-inline void fill_head_eval_steps(ActArgs *steps, int D, int A, int64_t P, int64_t N, const float *params,
-                                 const float *stage_obs, void *actions_flat, const int64_t *agent_env_base,
-                                 int64_t nsteps, uint64_t seed, uint64_t counter0) {
+// The evaluation entry of a head: sampled actions to the staging only, counters counter0 + t
+template <class Head, class Plan>
+int head_eval_persistent(const agx_ppo_graph *net, Plan plan, int64_t P, int64_t N, const float *params,
+                         const float *stage_obs, void *actions_flat, const int64_t *agent_env_base, int64_t nsteps,
+                         uint32_t base, uint64_t seed, uint64_t counter0, void *args_host, agx_rollout_ctl *ctl,
+                         double timeout_s, void *workspace, void *stream, const char *who) {
+    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
+                                  nsteps, base, timeout_s, who))
+        return rc;
+    GArgs full{};
+    Head h{};
+    if (int rc = plan(full, h, who)) return rc;
+    ActArgs *steps = static_cast<ActArgs *>(args_host);
     for (int64_t t = 0; t < nsteps; ++t)
-        steps[t] = eval_step_args(D, A, P, N, params, stage_obs, nullptr, static_cast<int64_t *>(actions_flat),
-                                  agent_env_base, seed, counter0 + (uint64_t)t);
+        steps[t] = eval_step_args(net->obs_dim, net->n_actions, P, N, params, stage_obs, nullptr,
+                                  static_cast<int64_t *>(actions_flat), agent_env_base, seed, counter0 + (uint64_t)t);
+    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
 }
 
 }  // namespace

@@ -23,7 +23,7 @@
 // loads stay outside the loop, once per lane.
 #include "../../include/agx_multi.h"
 #include "graph_net.h"
-#include "head_rollout.h"
+#include "head_policy.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kGT) void ppo_act_multi_graph_kernel(const GActArgs
     }
 }
 
-// multi_step as the step of head_rollout.h's persistent loop: the step's
+// multi_step as the step of head_policy.h's persistent loop: the step's
 // action slot / host staging are int64 [.., K]
 struct MultiRolloutHead {
     agx_multi_head head;
@@ -236,11 +236,7 @@ __global__ __launch_bounds__(256) void ppo_multi_loss_kernel(
         Acc one;
         loss_sample(lp, old_logp[src], adv[src], ret[src], old_v[src], value[o], H, k, gl, gv, one);
         if (sub == 0) {
-            acc.pg += one.pg;
-            acc.vl += one.vl;
-            acc.h += one.h;
-            acc.kl += one.kl;
-            acc.cf += one.cf;
+            acc.add(one);
             g_value[o] = gv;
         }
         // a masked logit passes nothing back (the reference's torch.where)
@@ -276,11 +272,32 @@ int head_width(const agx_multi_head &h, const char *who) {
 
 using namespace agx;
 
+namespace {
+// head with the components past K zeroed (they are never read): what the kernels take by value
+agx_multi_head head_arg(const agx_multi_head &head) {
+    agx_multi_head h{};
+    h.K = head.K;
+    for (int k = 0; k < head.K; ++k) h.nvec[k] = head.nvec[k];
+    return h;
+}
+
+// the rules of every multi-categorical entry point for the net and the head -> the plan and the
+// persistent kernel's head
+int multi_plan(const agx_ppo_graph *net, const agx_multi_head &head, GArgs &full, MultiRolloutHead &h,
+               const char *who) {
+    const int L = head_width(head, who);
+    if (L < 0) return AGX_EINVAL;
+    if (int rc = plan_graph(net, 1, full)) return rc;
+    AGX_REQUIRE(L == net->n_actions, "%s: nvec sums to %d, the actor's output has %d logits", who, L, net->n_actions);
+    h.head = head_arg(head);
+    return AGX_OK;
+}
+}  // namespace
+
 extern "C" size_t agx_ppo_act_multi_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t N) {
     GArgs full{};
-    GActArgs a{};
     if (!net || P <= 0 || N <= 0 || plan_graph(net, 1, full) != AGX_OK) return 0;
-    return (size_t)P * ceil_div(N, kActRows) * act_plan(full, a) * sizeof(float);
+    return head_act_workspace_bytes(full, P, N);
 }
 
 extern "C" int agx_ppo_act_multi_graph(const agx_ppo_graph *net, agx_multi_head head, int64_t P, int64_t N,
@@ -290,32 +307,17 @@ extern "C" int agx_ppo_act_multi_graph(const agx_ppo_graph *net, agx_multi_head 
                                        float *values, float *entropy, int64_t out_agent_stride,
                                        int64_t *actions_flat, const int64_t *agent_env_base, void *workspace,
                                        void *stream) {
-    AGX_REQUIRE(net && params && obs && workspace && P > 0 && N > 0 && P <= 65535,
-                "agx_ppo_act_multi_graph: bad arguments");
-    const int L = head_width(head, "agx_ppo_act_multi_graph");
-    if (L < 0) return AGX_EINVAL;
+    const char *who = "agx_ppo_act_multi_graph";
+    AGX_REQUIRE(net && params && obs && workspace && P > 0 && N > 0 && P <= 65535, "%s: bad arguments", who);
     GArgs full{};
-    const int rc = plan_graph(net, 1, full);
-    if (rc != AGX_OK) return rc;
-    AGX_REQUIRE(L == net->n_actions, "agx_ppo_act_multi_graph: nvec sums to %d, the actor's output has %d logits", L,
-                net->n_actions);
-    GActArgs a{};
-    act_plan(full, a);
-    a.ws = static_cast<float *>(workspace);
+    MultiRolloutHead r{};
+    if (int rc = multi_plan(net, head, full, r, who)) return rc;
     const ActArgs g = act_step_args(P, N, params, obs, obs_agent_stride, action_mask, mask_agent_stride, sample, seed,
                                     counter, nullptr, log_probs, values, entropy, out_agent_stride, nullptr,
                                     agent_env_base);
-    MultiHead h{};
-    h.head.K = head.K;  // the components past K are never read: pass them as zeros
-    for (int k = 0; k < head.K; ++k) h.head.nvec[k] = head.nvec[k];
-    h.act_out = reinterpret_cast<long long *>(actions);
-    h.act_flat = reinterpret_cast<long long *>(actions_flat);
-    dim3 grid((unsigned)ceil_div(N, kActRows), (unsigned)P);
-    if (const size_t dyn = act_plan_few(ppo_act_multi_graph_kernel<true>, a))
-        ppo_act_multi_graph_kernel<true><<<grid, kGT, dyn, as_stream(stream)>>>(a, g, h);
-    else
-        ppo_act_multi_graph_kernel<false><<<grid, kGT, 0, as_stream(stream)>>>(a, g, h);
-    return check_launch("agx_ppo_act_multi_graph");
+    const MultiHead h{r.head, reinterpret_cast<long long *>(actions), reinterpret_cast<long long *>(actions_flat)};
+    return launch_head_act(ppo_act_multi_graph_kernel<true>, ppo_act_multi_graph_kernel<false>, full, g, P, N,
+                           workspace, stream, h, who);
 }
 
 // ---------------------------------------------------------------------------
@@ -325,39 +327,15 @@ extern "C" int64_t agx_ppo_rollout_multi_graph_max_workgroups(void) {
     return head_rollout_max_workgroups<MultiRolloutHead>();
 }
 
-namespace {
-// agx_ppo_act_multi_graph's rules for the net and the head -> the plan and the kernel's head
-int multi_persistent_plan(const agx_ppo_graph *net, const agx_multi_head &head, GArgs &full, MultiRolloutHead &h,
-                          const char *who) {
-    const int L = head_width(head, who);
-    if (L < 0) return AGX_EINVAL;
-    const int rc = plan_graph(net, 1, full);
-    if (rc != AGX_OK) return rc;
-    AGX_REQUIRE(L == net->n_actions, "%s: nvec sums to %d, the actor's output has %d logits", who, L, net->n_actions);
-    h = MultiRolloutHead{};
-    h.head.K = head.K;  // the components past K are never read: pass them as zeros
-    for (int k = 0; k < head.K; ++k) h.head.nvec[k] = head.nvec[k];
-    return AGX_OK;
-}
-}  // namespace
-
 extern "C" int agx_ppo_rollout_multi_graph_persistent(const agx_ppo_graph *net, agx_multi_head head, int64_t P,
                                                       int64_t N, const float *params, const agx_rollout_io *ios,
                                                       int64_t nsteps, uint32_t base, uint64_t seed,
                                                       uint64_t counter0, void *args_host, agx_rollout_ctl *ctl,
                                                       double timeout_s, void *workspace, void *stream) {
-    const char *who = "agx_ppo_rollout_multi_graph_persistent";
-    if (int rc = check_persistent(net && ios && params && args_host && ctl && workspace, P, N, nsteps, base, timeout_s,
-                                  who))
-        return rc;
-    GArgs full{};
-    MultiRolloutHead h;
-    if (int rc = multi_persistent_plan(net, head, full, h, who)) return rc;
-    ActArgs *steps = static_cast<ActArgs *>(args_host);
-    if (int rc = fill_head_rollout_steps(steps, net->obs_dim, net->n_actions, P, N, params, ios, nsteps, seed,
-                                         counter0, who))
-        return rc;
-    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
+    auto plan = [&](GArgs &full, MultiRolloutHead &h, const char *who) { return multi_plan(net, head, full, h, who); };
+    return head_rollout_persistent<MultiRolloutHead>(net, plan, P, N, params, ios, nsteps, base, seed, counter0,
+                                                     args_host, ctl, timeout_s, workspace, stream,
+                                                     "agx_ppo_rollout_multi_graph_persistent");
 }
 
 extern "C" int agx_ppo_eval_multi_graph_persistent(const agx_ppo_graph *net, agx_multi_head head, int64_t P,
@@ -366,17 +344,11 @@ extern "C" int agx_ppo_eval_multi_graph_persistent(const agx_ppo_graph *net, agx
                                                    int64_t nsteps, uint32_t base, uint64_t seed, uint64_t counter0,
                                                    void *args_host, agx_rollout_ctl *ctl, double timeout_s,
                                                    void *workspace, void *stream) {
-    const char *who = "agx_ppo_eval_multi_graph_persistent";
-    if (int rc = check_persistent(net && params && stage_obs && actions_flat && args_host && ctl && workspace, P, N,
-                                  nsteps, base, timeout_s, who))
-        return rc;
-    GArgs full{};
-    MultiRolloutHead h;
-    if (int rc = multi_persistent_plan(net, head, full, h, who)) return rc;
-    ActArgs *steps = static_cast<ActArgs *>(args_host);
-    fill_head_eval_steps(steps, net->obs_dim, net->n_actions, P, N, params, stage_obs, actions_flat, agent_env_base,
-                         nsteps, seed, counter0);
-    return launch_head_persistent(full, P, N, steps, nsteps, base, ctl, timeout_s, workspace, stream, h, who);
+    auto plan = [&](GArgs &full, MultiRolloutHead &h, const char *who) { return multi_plan(net, head, full, h, who); };
+    return head_eval_persistent<MultiRolloutHead>(net, plan, P, N, params, stage_obs, actions_flat, agent_env_base,
+                                                  nsteps, base, seed, counter0, args_host, ctl, timeout_s, workspace,
+                                                  stream,
+                                                  "agx_ppo_eval_multi_graph_persistent");
 }
 
 extern "C" int agx_ppo_multi_loss_fwd_bwd(const float *logits, const float *value, agx_multi_head head,
@@ -392,22 +364,11 @@ extern "C" int agx_ppo_multi_loss_fwd_bwd(const float *logits, const float *valu
     AGX_REQUIRE(logits && value && actions && old_logp && adv && ret && old_value && g_logits && g_value,
                 "agx_ppo_multi_loss_fwd_bwd: null pointer");
     if (num_minibatches == 0) return AGX_OK;
-    LossCoef k;
-    k.clip = clip_coef;
-    k.lo = 1.f - clip_coef;
-    k.hi = 1.f + clip_coef;
-    k.inv_b = 1.f / (float)batch;
-    k.vf = vf_coef;
-    k.ent = ent_coef;
-    k.vf_half_inv_b = vf_coef * 0.5f * k.inv_b;
-    k.g_h = -ent_coef * k.inv_b;
-    agx_multi_head hd{};
-    hd.K = head.K;
-    for (int c = 0; c < head.K; ++c) hd.nvec[c] = head.nvec[c];
+    const LossCoef k = loss_coef(batch, clip_coef, vf_coef, ent_coef);
     const int64_t blocks = ceil_div(num_minibatches, 4);
     AGX_REQUIRE(blocks < ((int64_t)1 << 31), "agx_ppo_multi_loss_fwd_bwd: too many minibatches");
     ppo_multi_loss_kernel<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(
-        logits, value, hd, L, reinterpret_cast<const long long *>(actions), mask, old_logp, adv, ret, old_value, index,
-        batch, num_minibatches, k, g_logits, g_value, stats);
+        logits, value, head_arg(head), L, reinterpret_cast<const long long *>(actions), mask, old_logp, adv, ret,
+        old_value, index, batch, num_minibatches, k, g_logits, g_value, stats);
     return check_launch("agx_ppo_multi_loss_fwd_bwd");
 }

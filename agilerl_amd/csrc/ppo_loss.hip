@@ -100,15 +100,7 @@ extern "C" int agx_ppo_loss_fwd_bwd(const float *logp, const float *old_logp, co
                     g_value && g_entropy,
                 "agx_ppo_loss_fwd_bwd: null pointer");
     if (num_minibatches == 0) return AGX_OK;
-    LossCoef k;
-    k.clip = clip_coef;
-    k.lo = 1.f - clip_coef;
-    k.hi = 1.f + clip_coef;
-    k.inv_b = 1.f / (float)batch;
-    k.vf = vf_coef;
-    k.ent = ent_coef;
-    k.vf_half_inv_b = vf_coef * 0.5f * k.inv_b;
-    k.g_h = -ent_coef * k.inv_b;
+    const LossCoef k = loss_coef(batch, clip_coef, vf_coef, ent_coef);
     hipStream_t s = as_stream(stream);
     const bool vec = !index && batch % 4 == 0 && aligned16(logp) && aligned16(old_logp) &&
                      aligned16(adv) && aligned16(ret) && aligned16(old_value) &&

@@ -1,7 +1,7 @@
 // The per-sample PPO clipped-surrogate loss (ppo.py:868-902) and the
 // minibatch reduction shared by agx_ppo_loss_fwd_bwd (ppo_loss.hip: a
-// ready-made log-prob and entropy per row) and agx_ppo_gauss_loss_fwd_bwd
-// (gauss_policy.hip: the Gaussian head fused in).
+// ready-made log-prob and entropy per row) and the head losses with the
+// head fused in (gauss_policy.hip, multi_policy.hip, bern_policy.hip).
 #pragma once
 
 #include "agx_common.h"
@@ -12,8 +12,29 @@ struct LossCoef {
     float lo, hi, clip, vf_half_inv_b, inv_b, g_h, vf, ent;
 };
 
+// the coefficients of a minibatch of `batch` rows (the loss entry points' fill)
+inline LossCoef loss_coef(int64_t batch, float clip_coef, float vf_coef, float ent_coef) {
+    LossCoef k;
+    k.clip = clip_coef;
+    k.lo = 1.f - clip_coef;
+    k.hi = 1.f + clip_coef;
+    k.inv_b = 1.f / (float)batch;
+    k.vf = vf_coef;
+    k.ent = ent_coef;
+    k.vf_half_inv_b = vf_coef * 0.5f * k.inv_b;
+    k.g_h = -ent_coef * k.inv_b;
+    return k;
+}
+
 struct Acc {
     float pg = 0.f, vl = 0.f, h = 0.f, kl = 0.f, cf = 0.f;
+    __device__ __forceinline__ void add(const Acc &o) {
+        pg += o.pg;
+        vl += o.vl;
+        h += o.h;
+        kl += o.kl;
+        cf += o.cf;
+    }
 };
 
 __device__ __forceinline__ void loss_sample(float lp, float olp, float A, float R, float ov,

@@ -144,6 +144,37 @@ def ppo_loss_fwd_bwd(logp, old_logp, adv, ret, old_value, value, entropy, batch,
     return out[0], out[1], out[2], stats
 
 
+def _head_loss_rows(out, out_name, value, batch, actions, act_dtype, act_cols, old_logp, adv, ret, old_value, index,
+                    mask):
+    """The checks the head losses share: ``out`` (the actor output, f32
+    [nmb * batch, W]) against value, the rollout arrays (actions [rows, act_cols]
+    of act_dtype, old_logp / adv / ret / old_value [rows], mask uint8 [rows, W] or
+    None) and ``index``.  -> nmb."""
+    S, W = out.shape
+    if S % batch:
+        raise ValueError(f"samples ({S}) must be a multiple of batch ({batch}); call per minibatch")
+    _need(value, "value", _f32)
+    if value.numel() != S:
+        raise ValueError(f"value: expected {S} elements")
+    _need(actions, "actions", act_dtype)
+    if actions.dim() != 2 or actions.shape[1] != act_cols:
+        raise ValueError(f"actions: expected [rows, {act_cols}]")
+    src = actions.shape[0]
+    for t, name in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
+        _need(t, name, _f32)
+        if t.numel() != src:
+            raise ValueError(f"{name}: expected {src} elements")
+    if mask is not None:
+        _need(mask, "mask", torch.uint8, (src, W))
+    if index is not None:
+        _need(index, "index", _i64)
+        if index.numel() != S:
+            raise ValueError("index: one entry per sample")
+    elif src != S:
+        raise ValueError(f"without an index the rollout arrays must match {out_name}")
+    return S // batch
+
+
 def ppo_gauss_loss_fwd_bwd(mean, value, log_std, actions, old_logp, adv, ret, old_value, batch, clip_coef=0.2,
                            vf_coef=0.5, ent_coef=0.01, index=None, out=None, stats=None):
     """The Gaussian twin of ppo_loss_fwd_bwd (agx_ppo_gauss_loss_fwd_bwd): mean
@@ -154,28 +185,10 @@ def ppo_gauss_loss_fwd_bwd(mean, value, log_std, actions, old_logp, adv, ret, ol
     _need(mean, "mean", _f32)
     if mean.dim() != 2:
         raise ValueError("mean: expected [samples, A]")
-    S, A = mean.shape
-    if S % batch:
-        raise ValueError(f"samples ({S}) must be a multiple of batch ({batch}); call per minibatch")
-    nmb = S // batch
-    _need(value, "value", _f32)
-    if value.numel() != S:
-        raise ValueError(f"value: expected {S} elements")
+    A = mean.shape[1]
+    nmb = _head_loss_rows(mean, "mean", value, batch, actions, _f32, A, old_logp, adv, ret, old_value, index,
+                                 None)
     _need(log_std, "log_std", _f32, (nmb, A))
-    _need(actions, "actions", _f32)
-    if actions.dim() != 2 or actions.shape[1] != A:
-        raise ValueError(f"actions: expected [rows, {A}]")
-    src = actions.shape[0]
-    for t, n in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
-        _need(t, n, _f32)
-        if t.numel() != src:
-            raise ValueError(f"{n}: expected {src} elements")
-    if index is not None:
-        _need(index, "index", _i64)
-        if index.numel() != S:
-            raise ValueError("index: one entry per sample")
-    elif src != S:
-        raise ValueError("without an index the rollout arrays must match mean")
     if out is None:
         out = (torch.empty_like(mean), torch.empty_like(value), torch.empty_like(log_std))
     if stats is None:
@@ -200,22 +213,6 @@ def multi_head(nvec) -> _lib.AgxMultiHead:
     return h
 
 
-def ppo_act_multi_graph(desc, head, P, N, params, obs, obs_agent_stride, workspace, *, sample, seed, counter,
-                        mask=None, mask_agent_stride=0, actions=None, log_probs=None, values=None, entropy=None,
-                        out_agent_stride=0, actions_flat=None, agent_env_base=None) -> None:
-    """agx_ppo_act_multi_graph: the multi-categorical policy step of P agents x
-    N envs over the layer list ``desc`` (an agx_ppo_graph whose n_actions is
-    sum(nvec)) in one launch.  actions int64 [P, .., K] (row n of agent p at
-    (p out_agent_stride + n) K), log_probs / values / entropy with agent stride
-    out_agent_stride, actions_flat int64 [P N K]; each may be None.  mask:
-    uint8 [P, .., L] with agent stride mask_agent_stride."""
-    _lib.call("agx_ppo_act_multi_graph", ctypes.byref(desc), head, int(P), int(N), params.data_ptr(), obs.data_ptr(),
-              int(obs_agent_stride), _lib.ptr(mask), int(mask_agent_stride), 1 if sample else 0, int(seed),
-              int(counter), _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy),
-              int(out_agent_stride), _lib.ptr(actions_flat), _lib.ptr(agent_env_base), workspace.data_ptr(),
-              _lib.stream())
-
-
 def ppo_multi_loss_fwd_bwd(logits, value, nvec, actions, old_logp, adv, ret, old_value, batch, clip_coef=0.2,
                            vf_coef=0.5, ent_coef=0.01, index=None, mask=None, out=None, stats=None):
     """The multi-categorical twin of ppo_loss_fwd_bwd (agx_ppo_multi_loss_fwd_bwd):
@@ -229,29 +226,8 @@ def ppo_multi_loss_fwd_bwd(logits, value, nvec, actions, old_logp, adv, ret, old
     _need(logits, "logits", _f32)
     if logits.dim() != 2 or logits.shape[1] != L:
         raise ValueError(f"logits: expected [samples, {L}]")
-    S = logits.shape[0]
-    if S % batch:
-        raise ValueError(f"samples ({S}) must be a multiple of batch ({batch}); call per minibatch")
-    nmb = S // batch
-    _need(value, "value", _f32)
-    if value.numel() != S:
-        raise ValueError(f"value: expected {S} elements")
-    _need(actions, "actions", _i64)
-    if actions.dim() != 2 or actions.shape[1] != K:
-        raise ValueError(f"actions: expected [rows, {K}]")
-    src = actions.shape[0]
-    for t, n in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
-        _need(t, n, _f32)
-        if t.numel() != src:
-            raise ValueError(f"{n}: expected {src} elements")
-    if mask is not None:
-        _need(mask, "mask", torch.uint8, (src, L))
-    if index is not None:
-        _need(index, "index", _i64)
-        if index.numel() != S:
-            raise ValueError("index: one entry per sample")
-    elif src != S:
-        raise ValueError("without an index the rollout arrays must match logits")
+    nmb = _head_loss_rows(logits, "logits", value, batch, actions, _i64, K, old_logp, adv, ret, old_value,
+                                 index, mask)
     if out is None:
         out = (torch.empty_like(logits), torch.empty_like(value))
     if stats is None:
@@ -261,23 +237,6 @@ def ppo_multi_loss_fwd_bwd(logits, value, nvec, actions, old_logp, adv, ret, old
               _lib.ptr(index), int(batch), int(nmb), float(clip_coef), float(vf_coef), float(ent_coef),
               out[0].data_ptr(), out[1].data_ptr(), stats.data_ptr(), _lib.stream())
     return out[0], out[1], stats
-
-
-def ppo_act_bern_graph(desc, P, N, params, obs, obs_agent_stride, workspace, *, sample, seed, counter, mask=None,
-                       mask_agent_stride=0, actions=None, log_probs=None, values=None, entropy=None,
-                       out_agent_stride=0, actions_flat=None, agent_env_base=None) -> None:
-    """agx_ppo_act_bern_graph: the Bernoulli policy step of P agents x N envs
-    over the layer list ``desc`` (an agx_ppo_graph whose n_actions is the
-    MultiBinary space's n) in one launch.  actions int64 [P, .., n] holding
-    0 / 1 (row r of agent p at (p out_agent_stride + r) n), log_probs / values /
-    entropy with agent stride out_agent_stride, actions_flat int64 [P N n];
-    each may be None.  mask: uint8 [P, .., n] with agent stride
-    mask_agent_stride."""
-    _lib.call("agx_ppo_act_bern_graph", ctypes.byref(desc), int(P), int(N), params.data_ptr(), obs.data_ptr(),
-              int(obs_agent_stride), _lib.ptr(mask), int(mask_agent_stride), 1 if sample else 0, int(seed),
-              int(counter), _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy),
-              int(out_agent_stride), _lib.ptr(actions_flat), _lib.ptr(agent_env_base), workspace.data_ptr(),
-              _lib.stream())
 
 
 def ppo_bern_loss_fwd_bwd(logits, value, actions, old_logp, adv, ret, old_value, batch, clip_coef=0.2, vf_coef=0.5,
@@ -293,29 +252,8 @@ def ppo_bern_loss_fwd_bwd(logits, value, actions, old_logp, adv, ret, old_value,
     if logits.dim() != 2:
         raise ValueError("logits: expected [samples, n]")
     n = logits.shape[1] if n is None else int(n)
-    S = logits.shape[0]
-    if S % batch:
-        raise ValueError(f"samples ({S}) must be a multiple of batch ({batch}); call per minibatch")
-    nmb = S // batch
-    _need(value, "value", _f32)
-    if value.numel() != S:
-        raise ValueError(f"value: expected {S} elements")
-    _need(actions, "actions", _i64)
-    if actions.dim() != 2 or actions.shape[1] != logits.shape[1]:
-        raise ValueError(f"actions: expected [rows, {logits.shape[1]}]")
-    src = actions.shape[0]
-    for t, name in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
-        _need(t, name, _f32)
-        if t.numel() != src:
-            raise ValueError(f"{name}: expected {src} elements")
-    if mask is not None:
-        _need(mask, "mask", torch.uint8, (src, logits.shape[1]))
-    if index is not None:
-        _need(index, "index", _i64)
-        if index.numel() != S:
-            raise ValueError("index: one entry per sample")
-    elif src != S:
-        raise ValueError("without an index the rollout arrays must match logits")
+    nmb = _head_loss_rows(logits, "logits", value, batch, actions, _i64, logits.shape[1], old_logp, adv, ret,
+                                 old_value, index, mask)
     if out is None:
         out = (torch.empty_like(logits), torch.empty_like(value))
     if stats is None:

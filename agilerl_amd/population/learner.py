@@ -1,9 +1,9 @@
-"""Host side of the fused PPO learners: agx_ppo_learn (learner.hip, the
-compiled network shapes), agx_ppo_learn_graph (graph_learner.hip, any MLP
-actor-critic as a runtime layer list: the shapes architecture mutations
-produce), agx_ppo_learn_gauss_graph (the same with a Gaussian head: Box
-action spaces) and agx_ppo_learn_multi_graph (the same with a multi-categorical
-head: MultiDiscrete action spaces)."""
+"""Host side of the fused PPO learners and policy steps: agx_ppo_learn
+(learner.hip, the compiled network shapes), agx_ppo_learn_graph
+(graph_learner.hip, any MLP actor-critic as a runtime layer list: the shapes
+architecture mutations produce) and agx_ppo_learn_{gauss,multi,bern}_graph
+(the same with a Gaussian, multi-categorical or Bernoulli head: Box,
+MultiDiscrete and MultiBinary action spaces; ppo_pop.HEADS)."""
 
 from __future__ import annotations
 
@@ -240,79 +240,51 @@ class GraphLearner(FusedLearner):
         return False  # one workgroup per agent: no partner hand-off to time out
 
 
-class GaussGraphLearner(GraphLearner):
-    """agx_ppo_learn_gauss_graph: GraphLearner for a Box-action population (the
-    actor output is the Gaussian mean, log_std at ``pop.spec.log_std``)."""
+class HeadGraphLearner(GraphLearner):
+    """agx_ppo_learn_<stem>_graph: GraphLearner for a population with a
+    non-categorical head (ppo_pop.HEADS); ``pop.head_args()`` follows the
+    descriptor."""
 
     def __init__(self, pop):
-        self.desc = pop.gauss_learn_descriptor()
+        self.desc = pop.head_learn_descriptor()
+        self.name = f"agx_ppo_learn_{pop.head.stem}_graph"
         if self.desc is None:
-            raise _lib.AgxError("network outside the Gaussian graph learner's coverage")
+            raise _lib.AgxError(f"network outside the coverage of {self.name}")
         lib = _lib.load()
         self.batch_ws = pop.split_batch
-        self.log_std = int(pop.spec.log_std)
-        nbytes = lib.agx_ppo_learn_gauss_graph_workspace_bytes(ctypes.byref(self.desc), self.log_std, pop.P, pop.S,
-                                                               pop.update_epochs, self.batch_ws)
-        if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_learn_gauss_graph_workspace_bytes: {lib.agx_last_error().decode()}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=pop.device)
-        self._outputs(pop)
-        gauss = lib.agx_ppo_learn_gauss_graph
-        self.fn = lambda desc, args, ws, stream: gauss(desc, self.log_std, args, ws, stream)
-        self.name = "agx_ppo_learn_gauss_graph"
-
-
-class MultiGraphLearner(GraphLearner):
-    """agx_ppo_learn_multi_graph: GraphLearner for a MultiDiscrete population
-    (the actor output is the L = sum(nvec) logits, ``pop.multi_head()`` passed
-    by value; int64 actions [.., K], flat masks [.., L])."""
-
-    def __init__(self, pop):
-        self.desc = pop.multi_learn_descriptor()
-        if self.desc is None:
-            raise _lib.AgxError("network outside the multi-categorical graph learner's coverage")
-        lib = _lib.load()
-        self.batch_ws = pop.split_batch
-        self.head = pop.multi_head()
-        nbytes = lib.agx_ppo_learn_multi_graph_workspace_bytes(ctypes.byref(self.desc), self.head, pop.P, pop.S,
-                                                               pop.update_epochs, self.batch_ws)
-        if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_learn_multi_graph_workspace_bytes: {lib.agx_last_error().decode()}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=pop.device)
-        self._outputs(pop)
-        multi = lib.agx_ppo_learn_multi_graph
-        self.fn = lambda desc, args, ws, stream: multi(desc, self.head, args, ws, stream)
-        self.name = "agx_ppo_learn_multi_graph"
-
-
-class BernGraphLearner(GraphLearner):
-    """agx_ppo_learn_bern_graph: GraphLearner for a MultiBinary population (the
-    actor output is the n Bernoulli logits; int64 actions [.., n] holding
-    0 / 1, flat masks [.., n])."""
-
-    def __init__(self, pop):
-        self.desc = pop.bern_learn_descriptor()
-        if self.desc is None:
-            raise _lib.AgxError("network outside the Bernoulli graph learner's coverage")
-        lib = _lib.load()
-        self.batch_ws = pop.split_batch
-        nbytes = lib.agx_ppo_learn_bern_graph_workspace_bytes(ctypes.byref(self.desc), pop.P, pop.S,
+        lead = pop.head_args()
+        nbytes = getattr(lib, self.name + "_workspace_bytes")(ctypes.byref(self.desc), *lead, pop.P, pop.S,
                                                               pop.update_epochs, self.batch_ws)
         if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_learn_bern_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+            raise _lib.AgxError(f"{self.name}_workspace_bytes: {lib.agx_last_error().decode()}")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=pop.device)
         self._outputs(pop)
-        self.fn = lib.agx_ppo_learn_bern_graph
-        self.name = "agx_ppo_learn_bern_graph"
+        learn = getattr(lib, self.name)
+        self.fn = (lambda desc, args, ws, stream: learn(desc, *lead, args, ws, stream)) if lead else learn
+
+
+class GaussGraphLearner(HeadGraphLearner):
+    """A Box-action population (the actor output is the Gaussian mean, log_std
+    at ``pop.spec.log_std``)."""
+
+
+class MultiGraphLearner(HeadGraphLearner):
+    """A MultiDiscrete population (the actor output is the L = sum(nvec)
+    logits, ``pop.multi_head()`` passed by value; int64 actions [.., K], flat
+    masks [.., L])."""
+
+
+class BernGraphLearner(HeadGraphLearner):
+    """A MultiBinary population (the actor output is the n Bernoulli logits;
+    int64 actions [.., n] holding 0 / 1, flat masks [.., n])."""
+
+
+_HEAD_LEARNERS = {"gauss": GaussGraphLearner, "multi": MultiGraphLearner, "bern": BernGraphLearner}
 
 
 def make_learner(pop) -> FusedLearner:
-    if pop.gaussian:
-        return GaussGraphLearner(pop)
-    if pop.multidiscrete:
-        return MultiGraphLearner(pop)
-    if pop.multibinary:
-        return BernGraphLearner(pop)
+    if pop.head is not None:
+        return _HEAD_LEARNERS[pop.head.stem](pop)
     return FusedLearner(pop) if pop.fused_descriptor() is not None else GraphLearner(pop)
 
 
@@ -339,19 +311,25 @@ def policy_step(pop, desc: AgxPPONet, obs: torch.Tensor, obs_agent_stride: int, 
               _lib.ptr(actions_flat), pop.env_base_d.data_ptr(), _lib.stream())
 
 
-def graph_act_workspace(pop, desc: AgxPPOGraph):
-    """(desc, scratch) of agx_ppo_act_graph for this population, allocated on
-    first use.  Callers that keep a persistent launch resident (lock-stepped
-    evaluation) take it before launching: an allocation can wait for the
-    device."""
+def act_workspace(pop, desc: AgxPPOGraph, stem: str):
+    """(desc, scratch) of agx_ppo_act_<stem>_graph (agx_ppo_act_graph: stem
+    "") for this population, allocated on first use.  Callers that keep a
+    persistent launch resident (lock-stepped evaluation) take it before
+    launching: an allocation can wait for the device."""
     ws = getattr(pop, "_act_ws", None)
     if ws is None or ws[0] is not desc:
         lib = _lib.load()
-        nbytes = lib.agx_ppo_act_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
+        name = f"agx_ppo_act_{stem}_graph_workspace_bytes" if stem else "agx_ppo_act_graph_workspace_bytes"
+        nbytes = getattr(lib, name)(ctypes.byref(desc), pop.P, pop.N)
         if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_act_graph_workspace_bytes: {lib.agx_last_error().decode()}")
+            raise _lib.AgxError(f"{name}: {lib.agx_last_error().decode()}")
         ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
     return ws
+
+
+def graph_act_workspace(pop, desc: AgxPPOGraph):
+    """act_workspace of the categorical runtime-shape step."""
+    return act_workspace(pop, desc, "")
 
 
 def policy_step_graph(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
@@ -367,106 +345,44 @@ def policy_step_graph(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_strid
               _lib.ptr(actions_flat), pop.env_base_d.data_ptr(), ws[1].data_ptr(), _lib.stream())
 
 
-
-def gauss_act_workspace(pop, desc: AgxPPOGraph):
-    """(desc, scratch) of agx_ppo_act_gauss_graph for this population, as
-    graph_act_workspace."""
-    ws = getattr(pop, "_act_ws", None)
-    if ws is None or ws[0] is not desc:
-        lib = _lib.load()
-        nbytes = lib.agx_ppo_act_gauss_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
-        if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_act_gauss_graph_workspace_bytes: {lib.agx_last_error().decode()}")
-        ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
-    return ws
-
-
-def policy_step_gauss(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
-                      counter: int, actions=None, log_probs=None, values=None, entropy=None,
-                      out_agent_stride: int = 0, actions_flat=None, clip=None) -> None:
-    """agx_ppo_act_gauss_graph over all P agents x N envs: the policy step of a
-    Box-action population (one launch), the agents' own Philox streams;
-    ``clip``: (low, high) device tensors [A] for the actions_flat copy."""
-    ws = gauss_act_workspace(pop, desc)
-    lo, hi = clip if clip is not None else (None, None)
-    _lib.call("agx_ppo_act_gauss_graph", ctypes.byref(desc), pop.spec.log_std, pop.P, pop.N,
-              pop.params.data.data_ptr(), obs.data_ptr(), obs_agent_stride, 1 if sample else 0, pop.act_seed, counter,
-              _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values), _lib.ptr(entropy), out_agent_stride,
-              _lib.ptr(actions_flat), _lib.ptr(lo), _lib.ptr(hi), pop.env_base_d.data_ptr(), ws[1].data_ptr(),
-              _lib.stream())
+def head_act(head, desc: AgxPPOGraph, lead: tuple, P: int, N: int, params: torch.Tensor, obs: torch.Tensor,
+             obs_agent_stride: int, workspace: torch.Tensor, *, sample: bool, seed: int, counter: int, actions=None,
+             log_probs=None, values=None, entropy=None, out_agent_stride: int = 0, actions_flat=None,
+             action_mask=None, mask_agent_stride: int = 0, clip=None, agent_env_base=None) -> None:
+    """agx_ppo_act_<stem>_graph of ``head`` (ppo_pop.HEADS): the policy step of
+    P agents x N envs over the layer list ``desc`` in one launch, ``lead`` the
+    head's own arguments.  actions [P, .., W] in the head's dtype (row n of
+    agent p at (p out_agent_stride + n) W), log_probs / values / entropy with
+    agent stride out_agent_stride, actions_flat [P N W]; each may be None.
+    action_mask (the int heads): uint8 [P, .., L] with agent stride
+    mask_agent_stride; clip (the Gaussian head): (low, high) device tensors
+    [A] for the actions_flat copy."""
+    if action_mask is not None and not head.masks:
+        raise ValueError("action masks apply to Discrete action spaces, not to a Gaussian policy")
+    mask = (_lib.ptr(action_mask), mask_agent_stride) if head.masks else ()
+    lo, hi = clip or (None, None)
+    bounds = (_lib.ptr(lo), _lib.ptr(hi)) if head.clip else ()
+    _lib.call(head.act, ctypes.byref(desc), *lead, P, N, params.data_ptr(), obs.data_ptr(), obs_agent_stride, *mask,
+              1 if sample else 0, seed, counter, _lib.ptr(actions), _lib.ptr(log_probs), _lib.ptr(values),
+              _lib.ptr(entropy), out_agent_stride, _lib.ptr(actions_flat), *bounds, _lib.ptr(agent_env_base),
+              workspace.data_ptr(), _lib.stream())
 
 
-def multi_act_workspace(pop, desc: AgxPPOGraph):
-    """(desc, scratch) of agx_ppo_act_multi_graph for this population, as
-    graph_act_workspace."""
-    ws = getattr(pop, "_act_ws", None)
-    if ws is None or ws[0] is not desc:
-        lib = _lib.load()
-        nbytes = lib.agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
-        if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_act_multi_graph_workspace_bytes: {lib.agx_last_error().decode()}")
-        ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
-    return ws
+def policy_step_head(pop, obs: torch.Tensor, obs_agent_stride: int, **kw) -> None:
+    """head_act over all P agents x N envs of a Gaussian / MultiDiscrete /
+    MultiBinary population (one launch), the agents' own Philox streams."""
+    head = pop.head
+    desc, ws = act_workspace(pop, pop.head_descriptor(), head.stem)
+    head_act(head, desc, pop.head_args(), pop.P, pop.N, pop.params.data, obs, obs_agent_stride, ws,
+             seed=pop.act_seed, agent_env_base=pop.env_base_d, **kw)
 
 
-def policy_step_multi(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
-                      counter: int, actions=None, log_probs=None, values=None, entropy=None,
-                      out_agent_stride: int = 0, actions_flat=None, action_mask=None,
-                      mask_agent_stride: int = 0) -> None:
-    """agx_ppo_act_multi_graph over all P agents x N envs: the policy step of a
-    MultiDiscrete population (one launch), the agents' own Philox streams;
-    int64 actions [.., K], a flat mask [.., L]."""
-    from ..kernels import ppo_act_multi_graph
-
-    ws = multi_act_workspace(pop, desc)
-    ppo_act_multi_graph(desc, pop.multi_head(), pop.P, pop.N, pop.params.data, obs, obs_agent_stride, ws[1],
-                        sample=sample, seed=pop.act_seed, counter=counter, mask=action_mask,
-                        mask_agent_stride=mask_agent_stride, actions=actions, log_probs=log_probs, values=values,
-                        entropy=entropy, out_agent_stride=out_agent_stride, actions_flat=actions_flat,
-                        agent_env_base=pop.env_base_d)
+def policy_step_gauss(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, **kw) -> None:
+    """policy_step_head under the name (and with the descriptor argument) each
+    head came with; ``desc`` must be ``pop.head_descriptor()``, the one the step runs."""
+    if desc is not pop.head_descriptor():
+        raise ValueError("the policy step runs the population's own descriptor (pop.head_descriptor())")
+    policy_step_head(pop, obs, obs_agent_stride, **kw)
 
 
-def bern_act_workspace(pop, desc: AgxPPOGraph):
-    """(desc, scratch) of agx_ppo_act_bern_graph for this population, as
-    graph_act_workspace."""
-    ws = getattr(pop, "_act_ws", None)
-    if ws is None or ws[0] is not desc:
-        lib = _lib.load()
-        nbytes = lib.agx_ppo_act_bern_graph_workspace_bytes(ctypes.byref(desc), pop.P, pop.N)
-        if nbytes == 0:
-            raise _lib.AgxError(f"agx_ppo_act_bern_graph_workspace_bytes: {lib.agx_last_error().decode()}")
-        ws = pop._act_ws = (desc, torch.empty(nbytes, dtype=torch.uint8, device=pop.device))
-    return ws
-
-
-def policy_step_bern(pop, desc: AgxPPOGraph, obs: torch.Tensor, obs_agent_stride: int, *, sample: bool,
-                     counter: int, actions=None, log_probs=None, values=None, entropy=None,
-                     out_agent_stride: int = 0, actions_flat=None, action_mask=None,
-                     mask_agent_stride: int = 0) -> None:
-    """agx_ppo_act_bern_graph over all P agents x N envs: the policy step of a
-    MultiBinary population (one launch), the agents' own Philox streams;
-    int64 actions [.., n] holding 0 / 1, a flat mask [.., n]."""
-    from ..kernels import ppo_act_bern_graph
-
-    ws = bern_act_workspace(pop, desc)
-    ppo_act_bern_graph(desc, pop.P, pop.N, pop.params.data, obs, obs_agent_stride, ws[1], sample=sample,
-                       seed=pop.act_seed, counter=counter, mask=action_mask, mask_agent_stride=mask_agent_stride,
-                       actions=actions, log_probs=log_probs, values=values, entropy=entropy,
-                       out_agent_stride=out_agent_stride, actions_flat=actions_flat, agent_env_base=pop.env_base_d)
-
-
-def policy_step_vector(pop, obs: torch.Tensor, obs_agent_stride: int, **kw) -> None:
-    """The one-launch policy step of a population whose actions are int64
-    vectors: policy_step_multi (MultiDiscrete) or policy_step_bern
-    (MultiBinary) over the population's own descriptor."""
-    if pop.multibinary:
-        policy_step_bern(pop, pop.bern_descriptor(), obs, obs_agent_stride, **kw)
-    else:
-        policy_step_multi(pop, pop.multi_descriptor(), obs, obs_agent_stride, **kw)
-
-
-def vector_act_workspace(pop):
-    """The policy-step scratch of such a population, allocated now."""
-    if pop.multibinary:
-        return bern_act_workspace(pop, pop.bern_descriptor())
-    return multi_act_workspace(pop, pop.multi_descriptor())
+policy_step_multi = policy_step_bern = policy_step_gauss

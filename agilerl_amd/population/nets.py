@@ -205,6 +205,37 @@ class ActorCriticSpec:
                     out[f"{net}.{ln_name}.bias"] = (lay.beta, (lay.fout,))
         return out
 
+    def _head_descriptor(self, check):
+        """The layer list when ``check(lib, head, descriptor)`` (pure host-side
+        validation) admits it; None otherwise, or for the categorical head."""
+        import ctypes
+
+        from .. import _lib
+        from .learner import layer_list
+        from .ppo_pop import HEADS
+
+        head = HEADS.get(self.head)
+        d = layer_list(self) if head is not None else None
+        if d is None or not check(_lib.load(require_gpu=False), head, ctypes.byref(d)):
+            return None
+        return d
+
+    def act_descriptor(self):
+        """agx_ppo_graph of a non-categorical head's networks (ppo_pop.HEADS) for
+        agx_ppo_act_<stem>_graph (a Gaussian spec's n_params counts the log_std
+        floats, which no layer owns), or None when the layer list is outside
+        what the kernel takes."""
+        return self._head_descriptor(
+            lambda lib, h, d: getattr(lib, f"agx_ppo_act_{h.stem}_graph_workspace_bytes")(d, 1, 1) != 0)
+
+    def learn_descriptor_head(self):
+        """agx_ppo_graph of such networks for agx_ppo_learn_<stem>_graph (the
+        head's own arguments after it: ``log_std``, ``multi_head()``, nothing),
+        or None when that learner does not take the layer list: then the
+        autograd learner runs."""
+        return self._head_descriptor(
+            lambda lib, h, d: getattr(lib, f"agx_ppo_{h.stem}_graph_check")(d, *h.lead(self)) == 0)
+
 
 @dataclass
 class GaussianActorCriticSpec(ActorCriticSpec):
@@ -216,7 +247,7 @@ class GaussianActorCriticSpec(ActorCriticSpec):
     actor clip group [0, actor_end) (ppo.py:910-911).  ``n_actions`` is the
     action dimension A.  The categorical kernels (agx_ppo_learn, agx_ppo_act,
     the persistent rollout and evaluation) never see this spec: the Gaussian
-    policy step is agx_ppo_act_gauss_graph over ``gauss_descriptor()``."""
+    policy step is agx_ppo_act_gauss_graph over ``act_descriptor()``."""
 
     action_std_init: float = 0.0
     log_std: int = -1  # offset of the A log_std floats in the row (set by __post_init__)
@@ -248,6 +279,9 @@ class GaussianActorCriticSpec(ActorCriticSpec):
         """[P, A] view of the agents' log_std."""
         return flat[:, self.log_std: self.log_std + self.n_actions]
 
+    gauss_descriptor = ActorCriticSpec.act_descriptor  # the names the head came with
+    gauss_learn_descriptor = ActorCriticSpec.learn_descriptor_head
+
     def state_dict_keys(self) -> dict[str, tuple[int, tuple[int, ...]]]:
         # log_std is the distribution wrapper's own parameter, so it precedes
         # head_net._wrapped.* in the reference's actor.parameters() / state dict
@@ -259,36 +293,6 @@ class GaussianActorCriticSpec(ActorCriticSpec):
             out[k] = v
         return out
 
-    def gauss_descriptor(self):
-        """agx_ppo_graph of the networks for agx_ppo_act_gauss_graph (n_params
-        counts the log_std floats, which no layer owns), or None when the
-        layer list is outside what the kernel takes."""
-        import ctypes
-
-        from .. import _lib
-        from .learner import layer_list
-
-        d = layer_list(self)
-        lib = _lib.load(require_gpu=False)  # pure host-side validation
-        if d is None or lib.agx_ppo_act_gauss_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
-            return None
-        return d
-
-    def gauss_learn_descriptor(self):
-        """agx_ppo_graph of the networks for agx_ppo_learn_gauss_graph (with
-        ``log_std`` as its log_std_off), or None when the fused Gaussian
-        learner does not take the layer list: then the autograd learner runs."""
-        import ctypes
-
-        from .. import _lib
-        from .learner import layer_list
-
-        d = layer_list(self)
-        lib = _lib.load(require_gpu=False)  # pure host-side validation
-        if d is None or lib.agx_ppo_gauss_graph_check(ctypes.byref(d), self.log_std) != 0:
-            return None
-        return d
-
 
 @dataclass
 class MultiDiscreteActorCriticSpec(ActorCriticSpec):
@@ -299,8 +303,8 @@ class MultiDiscreteActorCriticSpec(ActorCriticSpec):
     categorical spec with n = L; there are no extra parameters.  The categorical
     kernels (agx_ppo_learn, agx_ppo_learn_graph, agx_ppo_act, the persistent
     rollout and evaluation) never see this spec, K = 1 included: the policy
-    step is agx_ppo_act_multi_graph over ``multi_descriptor()`` and the fused
-    learner agx_ppo_learn_multi_graph over ``multi_learn_descriptor()``."""
+    step is agx_ppo_act_multi_graph over ``act_descriptor()`` and the fused
+    learner agx_ppo_learn_multi_graph over ``learn_descriptor_head()``."""
 
     nvec: tuple = ()
 
@@ -326,35 +330,8 @@ class MultiDiscreteActorCriticSpec(ActorCriticSpec):
 
         return multi_head(self.nvec)
 
-    def multi_descriptor(self):
-        """agx_ppo_graph of the networks for agx_ppo_act_multi_graph, or None
-        when the layer list is outside what the kernel takes."""
-        import ctypes
-
-        from .. import _lib
-        from .learner import layer_list
-
-        d = layer_list(self)
-        lib = _lib.load(require_gpu=False)  # pure host-side validation
-        if d is None or lib.agx_ppo_act_multi_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
-            return None
-        return d
-
-    def multi_learn_descriptor(self):
-        """agx_ppo_graph of the networks for agx_ppo_learn_multi_graph (with
-        ``multi_head()`` as its head), or None when the fused
-        multi-categorical learner does not take the layer list: then the
-        autograd learner runs."""
-        import ctypes
-
-        from .. import _lib
-        from .learner import layer_list
-
-        d = layer_list(self)
-        lib = _lib.load(require_gpu=False)  # pure host-side validation
-        if d is None or lib.agx_ppo_multi_graph_check(ctypes.byref(d), self.multi_head()) != 0:
-            return None
-        return d
+    multi_descriptor = ActorCriticSpec.act_descriptor  # the names the head came with
+    multi_learn_descriptor = ActorCriticSpec.learn_descriptor_head
 
 
 @dataclass
@@ -365,8 +342,8 @@ class MultiBinaryActorCriticSpec(ActorCriticSpec):
     parameter order and the initial draws are those of the categorical spec
     with n actions; there are no extra parameters.  The categorical kernels
     never see this spec: the policy step is agx_ppo_act_bern_graph over
-    ``bern_descriptor()`` and the fused learner agx_ppo_learn_bern_graph over
-    ``bern_learn_descriptor()``.  ``action_dtype``: the space's numpy dtype
+    ``act_descriptor()`` and the fused learner agx_ppo_learn_bern_graph over
+    ``learn_descriptor_head()``.  ``action_dtype``: the space's numpy dtype
     name, what the env is handed its 0 / 1 actions in."""
 
     action_dtype: str = "int8"
@@ -385,34 +362,8 @@ class MultiBinaryActorCriticSpec(ActorCriticSpec):
     def shape_key(self) -> tuple:
         return super().shape_key() + (self.head, self.action_dtype)
 
-    def bern_descriptor(self):
-        """agx_ppo_graph of the networks for agx_ppo_act_bern_graph, or None
-        when the layer list is outside what the kernel takes."""
-        import ctypes
-
-        from .. import _lib
-        from .learner import layer_list
-
-        d = layer_list(self)
-        lib = _lib.load(require_gpu=False)  # pure host-side validation
-        if d is None or lib.agx_ppo_act_bern_graph_workspace_bytes(ctypes.byref(d), 1, 1) == 0:
-            return None
-        return d
-
-    def bern_learn_descriptor(self):
-        """agx_ppo_graph of the networks for agx_ppo_learn_bern_graph, or None
-        when the fused Bernoulli learner does not take the layer list: then
-        the autograd learner runs."""
-        import ctypes
-
-        from .. import _lib
-        from .learner import layer_list
-
-        d = layer_list(self)
-        lib = _lib.load(require_gpu=False)  # pure host-side validation
-        if d is None or lib.agx_ppo_bern_graph_check(ctypes.byref(d)) != 0:
-            return None
-        return d
+    bern_descriptor = ActorCriticSpec.act_descriptor  # the names the head came with
+    bern_learn_descriptor = ActorCriticSpec.learn_descriptor_head
 
 
 def bernoulli_head(logits: torch.Tensor, action: torch.Tensor, mask: torch.Tensor | None = None):

@@ -63,6 +63,7 @@ from __future__ import annotations
 
 import math
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -165,10 +166,52 @@ class _PPOBernLossFn(torch.autograd.Function):
         return (g1.view(sl) * gl, g2.view(sv) * gl) + (None,) * 11
 
 
+@dataclass
+class Head:
+    """What the host side needs to know of a non-categorical action head; the
+    entry points are agx_ppo_act_<stem>_graph, agx_ppo_rollout_<stem>_graph_
+    persistent, agx_ppo_eval_<stem>_graph_persistent, agx_ppo_<stem>_graph_check
+    and agx_ppo_learn_<stem>_graph, each taking ``lead(spec)`` right after the
+    network descriptor."""
+
+    stem: str
+    lead: object          # spec -> the arguments after the descriptor
+    dtype: torch.dtype    # a stored action's element
+    width: object         # spec -> action columns per row
+    clip: bool            # the launches take (clip_low, clip_high) for the env's copy
+    masks: bool           # the per-step launch takes a legal-action mask
+    fused_env: str        # the fused learner's environment switch ...
+    fused_default: bool   # ... what holds while it is unset (only "0" / "1" flips it) ...
+    multi_fused: bool     # ... and whether the ``multi_fused`` keyword switches it on too
+
+    def __post_init__(self) -> None:
+        self.act = f"agx_ppo_act_{self.stem}_graph"  # the per-step entry point (the name each step looks up)
+
+    def fused_on(self, pop) -> bool:
+        flipped = os.environ.get(self.fused_env) == ("0" if self.fused_default else "1")
+        return (self.fused_default != flipped) or (self.multi_fused and pop.multi_fused)
+
+
+HEADS = {  # keyed by spec.head
+    "gaussian": Head("gauss", lambda s: (s.log_std,), torch.float32, lambda s: s.n_actions, True, False,
+                     "AGX_GAUSS_FUSED", True, False),
+    "multidiscrete": Head("multi", lambda s: (s.multi_head(),), torch.int64, lambda s: len(s.nvec), False, True,
+                          "AGX_MULTI_FUSED", False, True),
+    "multibinary": Head("bern", lambda s: (), torch.int64, lambda s: s.n_actions, False, True,
+                        "AGX_BERN_FUSED", True, False),
+}
+
+
 class PPOPopulation:
-    # a MultiBinary population's descriptors, made on first use (bern_descriptor, bern_learn_descriptor)
-    _bern = None
-    _blearn = None
+    # a non-categorical population's descriptors and head arguments, made on first use
+    _hdesc = None
+    _hlearn = None
+    _mhead = None
+
+    @property
+    def head(self) -> Head | None:
+        """The population's entry of HEADS; None: the categorical head."""
+        return HEADS.get(getattr(self.spec, "head", "categorical"))
 
     @property
     def multibinary(self) -> bool:
@@ -184,8 +227,8 @@ class PPOPopulation:
 
     @property
     def act_width(self) -> int:
-        """Stored action columns per row: K components, n bits, else 1."""
-        return (len(self.spec.nvec) if self.multidiscrete else self.spec.n_actions if self.multibinary else 1)
+        """Stored action columns per row: A dimensions, K components, n bits, else 1."""
+        return 1 if self.head is None else self.head.width(self.spec)
 
     def __init__(self, spec: ActorCriticSpec, pop_size: int, num_envs: int, *, learn_step=2048,
                  batch_size=128, lr=1e-3, gamma=0.99, gae_lambda=0.95, clip_coef=0.2, ent_coef=0.01,
@@ -272,11 +315,6 @@ class PPOPopulation:
         self._desc = None
         self._gdesc = None
         self._edesc = None
-        self._gauss = None
-        self._glearn = None
-        self._mlearn = None
-        self._multi = None
-        self._mhead = None
         self._alloc_rollout()
         self.env_base_d = torch.tensor([i * self.N for i in self.agent_ids], dtype=torch.int64, device=self.device)
         self.learn_steps = 0
@@ -316,24 +354,11 @@ class PPOPopulation:
         agent's draws do not depend on which other agents share its population.
         A Gaussian population: one agx_ppo_act_gauss_graph launch, float
         actions [P, N, A] (``counter`` None: the next rollout counter)."""
-        if self.gaussian:
-            from .learner import policy_step_gauss
-
+        if self.head is not None:  # one agx_ppo_act_<stem>_graph launch, actions [P, N, act_width]
             if counter is None:
                 self.act_counter += 1
                 counter = self.act_counter
-            P, N = self.P, self.N
-            action = torch.empty(P, N, self.spec.n_actions, dtype=torch.float32, device=self.device)
-            logp, ent, value = (torch.empty(P, N, dtype=torch.float32, device=self.device) for _ in range(3))
-            policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), N * self.spec.obs_dim, sample=True,
-                              counter=int(counter), actions=action, log_probs=logp, values=value, entropy=ent,
-                              out_agent_stride=N)
-            return action, logp, ent, value
-        if self.vector_int:  # one agx_ppo_act_multi_graph / _bern_graph launch, int64 actions [P, N, K]
-            if counter is None:
-                self.act_counter += 1
-                counter = self.act_counter
-            return self._multi_step(obs, sample=True, counter=int(counter))
+            return self._head_step(obs, sample=True, counter=int(counter))
         logits, value = self.spec.forward(self.params.data, obs)
         logp_all, ent = categorical(logits)
         if counter is None:
@@ -389,131 +414,99 @@ class PPOPopulation:
             self._edesc = graph_descriptor(self.spec) or False
         return self._edesc or None
 
-    def gauss_descriptor(self):
-        """agx_ppo_graph of a Gaussian population's networks for
-        agx_ppo_act_gauss_graph.  There is no other policy step for a Box
-        population: a layer list the kernel does not take is an error."""
-        if not self.gaussian:
+    def head_descriptor(self):
+        """agx_ppo_graph of a Gaussian / MultiDiscrete / MultiBinary population's
+        networks for agx_ppo_act_<stem>_graph.  There is no other policy step
+        for such a population: a layer list the kernel does not take is an
+        error."""
+        if self.head is None:
             return None
-        if self._gauss is None:
-            self._gauss = self.spec.gauss_descriptor()
-            if self._gauss is None:
-                raise _lib.AgxError("agx_ppo_act_gauss_graph does not take this network: " +
+        if self._hdesc is None:
+            self._hdesc = self.spec.act_descriptor()
+            if self._hdesc is None:
+                raise _lib.AgxError(f"agx_ppo_act_{self.head.stem}_graph does not take this network: " +
                                     _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
-        return self._gauss
+        return self._hdesc
 
-    def multi_descriptor(self):
-        """agx_ppo_graph of a MultiDiscrete population's networks for
-        agx_ppo_act_multi_graph.  There is no other policy step for such a
-        population: a layer list the kernel does not take is an error."""
-        if not self.multidiscrete:
-            return None
-        if self._multi is None:
-            self._multi = self.spec.multi_descriptor()
-            if self._multi is None:
-                raise _lib.AgxError("agx_ppo_act_multi_graph does not take this network: " +
-                                    _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
-        return self._multi
-
-    def bern_descriptor(self):
-        """agx_ppo_graph of a MultiBinary population's networks for
-        agx_ppo_act_bern_graph.  There is no other policy step for such a
-        population: a layer list the kernel does not take is an error."""
-        if not self.multibinary:
-            return None
-        if self._bern is None:
-            self._bern = self.spec.bern_descriptor()
-            if self._bern is None:
-                raise _lib.AgxError("agx_ppo_act_bern_graph does not take this network: " +
-                                    _lib.load(require_gpu=False).agx_last_error().decode(errors="replace"))
-        return self._bern
+    def head_args(self) -> tuple:
+        """What the head's entry points take after the descriptor:
+        ``spec.log_std``, ``multi_head()``, or nothing."""
+        return (self.multi_head(),) if self.multidiscrete else self.head.lead(self.spec)
 
     def multi_head(self):
-        """agx_multi_head of the spec's nvec (made once)."""
+        """agx_multi_head of a MultiDiscrete spec's nvec (made once)."""
         if self._mhead is None:
             self._mhead = self.spec.multi_head()
         return self._mhead
 
-    @torch.no_grad()
-    def _multi_step(self, obs: torch.Tensor, *, sample: bool, counter: int, action_mask=None):
-        """obs [P, N, D] -> (actions int64 [P, N, K], log_prob, entropy, value
-        [P, N]) of a MultiDiscrete population; action_mask uint8 [P, N, L].  A
-        MultiBinary population: 0 / 1 actions [P, N, n], action_mask [P, N, n]."""
-        from .learner import policy_step_vector
+    # head_descriptor() / head_learn_descriptor() under the names each head came with: None for any other head
+    def gauss_descriptor(self):
+        return self.head_descriptor() if self.gaussian else None
 
-        P, N, L = self.P, self.N, self.spec.n_actions
-        action = torch.empty(P, N, self.act_width, dtype=torch.int64, device=self.device)
-        logp, ent, value = (torch.empty(P, N, dtype=torch.float32, device=self.device) for _ in range(3))
-        policy_step_vector(self, obs.contiguous(), N * self.spec.obs_dim, sample=sample,
-                           counter=counter, actions=action, log_probs=logp, values=value, entropy=ent,
-                           out_agent_stride=N, action_mask=action_mask, mask_agent_stride=N * L)
-        return action, logp, ent, value
+    def multi_descriptor(self):
+        return self.head_descriptor() if self.multidiscrete else None
+
+    def bern_descriptor(self):
+        return self.head_descriptor() if self.multibinary else None
 
     def gauss_learn_descriptor(self):
-        """agx_ppo_graph of a Gaussian population's networks for the fused
-        learner (agx_ppo_learn_gauss_graph, log_std at ``spec.log_std``); None:
-        not a Gaussian population, ``fused`` off, AGX_GAUSS_FUSED=0, or a layer
-        list agx_ppo_gauss_graph_check rejects — then the autograd learner runs."""
-        if not self.gaussian or not self.fused or os.environ.get("AGX_GAUSS_FUSED", "1") == "0":
-            return None
-        if self._glearn is None:
-            self._glearn = self.spec.gauss_learn_descriptor() or False
-        return self._glearn or None
+        return self.head_learn_descriptor() if self.gaussian else None
 
     def multi_learn_descriptor(self):
-        """agx_ppo_graph of a MultiDiscrete population's networks for the
-        fused learner (agx_ppo_learn_multi_graph, ``multi_head()`` by value);
-        None: not a MultiDiscrete population, ``fused`` off, the switch off
-        (neither ``multi_fused=True`` nor AGX_MULTI_FUSED=1), or a layer list
-        agx_ppo_multi_graph_check rejects — then the autograd learner runs."""
-        if (not self.multidiscrete or not self.fused
-                or not (self.multi_fused or os.environ.get("AGX_MULTI_FUSED", "0") == "1")):
-            return None
-        if self._mlearn is None:
-            self._mlearn = self.spec.multi_learn_descriptor() or False
-        return self._mlearn or None
+        return self.head_learn_descriptor() if self.multidiscrete else None
 
     def bern_learn_descriptor(self):
-        """agx_ppo_graph of a MultiBinary population's networks for the fused
-        learner (agx_ppo_learn_bern_graph); None: not a MultiBinary
-        population, ``fused`` off, AGX_BERN_FUSED=0, or a layer list
-        agx_ppo_bern_graph_check rejects — then the autograd learner runs."""
-        if not self.multibinary or not self.fused or os.environ.get("AGX_BERN_FUSED", "1") == "0":
+        return self.head_learn_descriptor() if self.multibinary else None
+
+    @torch.no_grad()
+    def _head_step(self, obs: torch.Tensor, *, sample: bool, counter: int, action_mask=None):
+        """obs [P, N, D] -> (actions [P, N, act_width], log_prob, entropy, value
+        [P, N]) of a non-categorical population: float actions [P, N, A]
+        (Gaussian), int64 choices [P, N, K] (MultiDiscrete) or 0 / 1 bits
+        [P, N, n] (MultiBinary); action_mask uint8 [P, N, L] for the int heads."""
+        from .learner import policy_step_head
+
+        P, N, L = self.P, self.N, self.spec.n_actions
+        action = torch.empty(P, N, self.act_width, dtype=self.head.dtype, device=self.device)
+        logp, ent, value = (torch.empty(P, N, dtype=torch.float32, device=self.device) for _ in range(3))
+        policy_step_head(self, obs.contiguous(), N * self.spec.obs_dim, sample=sample, counter=counter,
+                         actions=action, log_probs=logp, values=value, entropy=ent, out_agent_stride=N,
+                         action_mask=action_mask, mask_agent_stride=N * L)
+        return action, logp, ent, value
+
+    def head_learn_descriptor(self):
+        """agx_ppo_graph of such a population's networks for its fused learner
+        (agx_ppo_learn_<stem>_graph, ``head_args()`` after the descriptor);
+        None: a categorical population, ``fused`` off, the head's switch off
+        (AGX_GAUSS_FUSED=0, AGX_BERN_FUSED=0; neither ``multi_fused=True`` nor
+        AGX_MULTI_FUSED=1), or a layer list agx_ppo_<stem>_graph_check rejects
+        — then the autograd learner runs."""
+        if self.head is None or not self.fused or not self.head.fused_on(self):
             return None
-        if self._blearn is None:
-            self._blearn = self.spec.bern_learn_descriptor() or False
-        return self._blearn or None
+        if self._hlearn is None:
+            self._hlearn = self.spec.learn_descriptor_head() or False
+        return self._hlearn or None
 
     def _fused_learner(self) -> bool:
         """True when learn() runs a fused HIP learner (any head)."""
-        return (self.learn_descriptor() is not None or self.gauss_learn_descriptor() is not None
-                or self.multi_learn_descriptor() is not None or self.bern_learn_descriptor() is not None)
+        return self.learn_descriptor() is not None or self.head_learn_descriptor() is not None
 
     @torch.no_grad()
     def act_into(self, t: int, actions_flat: torch.Tensor | None = None) -> None:
         """Rollout policy step for slot t: reads obs[:, t], writes actions /
         log_probs / values[:, t] in place (and a contiguous [P*N] copy of the
         actions for the host env step; [P*N*A] floats for a Gaussian population)."""
-        if self.gaussian:
-            from .learner import policy_step_gauss
-
-            self.act_counter += 1
-            TN = self.T * self.N
-            policy_step_gauss(self, self.gauss_descriptor(), self.obs[:, t], TN * self.spec.obs_dim, sample=True,
-                              counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
-                              values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat)
-            return
-        if self.vector_int:  # int64 [P*N*K] staging; slot t's stored masks, when the population keeps them
-            from .learner import policy_step_vector
+        if self.head is not None:  # the staging in the head's dtype; slot t's stored masks, when kept
+            from .learner import policy_step_head
 
             self.act_counter += 1
             TN = self.T * self.N
             masks = self.action_masks
-            policy_step_vector(self, self.obs[:, t], TN * self.spec.obs_dim, sample=True,
-                               counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
-                               values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat,
-                               action_mask=None if masks is None else masks[:, t],
-                               mask_agent_stride=TN * self.spec.n_actions)
+            policy_step_head(self, self.obs[:, t], TN * self.spec.obs_dim, sample=True,
+                             counter=self.act_counter, actions=self.actions[:, t], log_probs=self.log_probs[:, t],
+                             values=self.values[:, t], out_agent_stride=TN, actions_flat=actions_flat,
+                             action_mask=None if masks is None else masks[:, t],
+                             mask_agent_stride=TN * self.spec.n_actions)
             return
         desc = self.fused_descriptor()
         if desc is None and self.learn_descriptor() is not None:  # a mutated shape: the runtime-shape kernel
@@ -590,15 +583,11 @@ class PPOPopulation:
     def values_of(self, obs: torch.Tensor) -> torch.Tensor:
         """The critic's values [P, N] of obs [P, N, D] from a Gaussian
         (or MultiDiscrete / MultiBinary) population's policy-step kernel (sample = 0, values only)."""
-        from .learner import policy_step_gauss, policy_step_vector
+        from .learner import policy_step_head
 
         value = torch.empty(self.P, self.N, dtype=torch.float32, device=self.device)
-        if self.vector_int:
-            policy_step_vector(self, obs.contiguous(), self.N * self.spec.obs_dim,
-                               sample=False, counter=0, values=value, out_agent_stride=self.N)
-            return value
-        policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim, sample=False,
-                          counter=0, values=value, out_agent_stride=self.N)
+        policy_step_head(self, obs.contiguous(), self.N * self.spec.obs_dim, sample=False, counter=0, values=value,
+                         out_agent_stride=self.N)
         return value
 
     # ------------------------------------------------------------------ #
@@ -901,15 +890,8 @@ class PPOPopulation:
     def evaluate(self, obs: torch.Tensor) -> torch.Tensor:
         """Greedy actions (mode of the categorical; the mean of a Gaussian
         policy, [P, N, A]) for fitness evaluation."""
-        if self.gaussian:
-            from .learner import policy_step_gauss
-
-            action = torch.empty(self.P, self.N, self.spec.n_actions, dtype=torch.float32, device=self.device)
-            policy_step_gauss(self, self.gauss_descriptor(), obs.contiguous(), self.N * self.spec.obs_dim,
-                              sample=False, counter=0, actions=action, out_agent_stride=self.N)
-            return action
-        if self.vector_int:  # the first arg-max of every component, [P, N, K]; the mode of every bit, [P, N, n]
-            return self._multi_step(obs, sample=False, counter=0)[0]
+        if self.head is not None:  # the mean; the first arg-max of every component; the mode of every bit
+            return self._head_step(obs, sample=False, counter=0)[0]
         logits, _ = self.spec.forward(self.params.data, obs)
         return torch.argmax(logits, dim=-1)
 

@@ -182,15 +182,21 @@ def _packed(P: int, N: int, D: int, owner=None, obs_dtype=torch.float32, **kw):
     return buf, obs, rew, done
 
 
+def head_persistent(pop, kind: str, before: tuple, after: tuple, clip=None) -> None:
+    """agx_ppo_<kind>_<stem>_graph_persistent (kind "rollout" or "eval") of
+    ``pop``'s head (ppo_pop.HEADS): the descriptor and the head's own arguments
+    in front, then ``before``, the Gaussian head's clip bounds, ``after``."""
+    lib, head = _lib.load(), pop.head
+    name = f"agx_ppo_{kind}_{head.stem}_graph_persistent"
+    bounds = tuple(_lib.ptr(t) for t in (clip or (None, None))) if head.clip else ()
+    _lib.check(getattr(lib, name)(ctypes.byref(pop.head_descriptor()), *pop.head_args(), *before, *bounds, *after),
+               name)
+
+
 def head_max_workgroups(pop) -> int:
     """Co-resident workgroups of the persistent rollout kernel of ``pop``'s
     head (each head's kernel has its own occupancy)."""
-    lib = _lib.load()
-    if pop.gaussian:
-        return int(lib.agx_ppo_rollout_gauss_graph_max_workgroups())
-    if pop.multibinary:
-        return int(lib.agx_ppo_rollout_bern_graph_max_workgroups())
-    return int(lib.agx_ppo_rollout_multi_graph_max_workgroups())
+    return int(getattr(_lib.load(), f"agx_ppo_rollout_{pop.head.stem}_graph_max_workgroups")())
 
 
 class PopulationRunner:
@@ -215,7 +221,7 @@ class PopulationRunner:
                                      lib.agx_ppo_rollout_graph_max_workgroups())
         # a Gaussian / MultiDiscrete / MultiBinary population: the head's own persistent
         # launch (no legal-action masks: the runner stages none)
-        self.head_persistent = bool(paced and (pop.gaussian or pop.vector_int) and pop.action_masks is None and
+        self.head_persistent = bool(paced and pop.head is not None and pop.action_masks is None and
                                     pop.obs.dtype == torch.float32 and
                                     lib.agx_ppo_rollout_graph_workgroups(P, N) <= head_max_workgroups(pop))
         if self.persistent or self.graph_persistent or self.head_persistent:
@@ -255,18 +261,14 @@ class PopulationRunner:
         [P*N*A] for a Gaussian (Box-action) population, or int64 [P*N*K] for a
         MultiDiscrete one."""
         pop = self.pop
-        if pop.gaussian:
-            return torch.zeros(pop.P * pop.N * pop.spec.n_actions, dtype=torch.float32, **kw)
-        if pop.vector_int:  # a MultiBinary population: one column per bit
-            return torch.zeros(pop.P * pop.N * pop.act_width, dtype=torch.int64, **kw)
-        return torch.zeros(pop.P * pop.N, dtype=torch.int64, **kw)
+        dtype = torch.int64 if pop.head is None else pop.head.dtype  # staging dtype: where the heads differ
+        return torch.zeros(pop.P * pop.N * pop.act_width, dtype=dtype, **kw)
 
     def _coherent_actions(self) -> torch.Tensor:
         """_action_staging in coherent host memory (a persistent launch's)."""
         pop = self.pop
-        if pop.gaussian:
-            return _coherent(self, pop.P * pop.N * pop.spec.n_actions * 4).view(torch.float32)
-        return _coherent(self, pop.P * pop.N * pop.act_width * 8).view(torch.int64)
+        dtype = torch.int64 if pop.head is None else pop.head.dtype
+        return _coherent(self, pop.P * pop.N * pop.act_width * dtype.itemsize).view(dtype)
 
     def _ctl_bytes(self) -> int:
         lib, P, N = _lib.load(), self.pop.P, self.pop.N
@@ -327,7 +329,7 @@ class PopulationRunner:
         # numpy views of the staging made once (Tensor.numpy() costs ~1-3 us a call)
         if self._np is None:
             act = self.act_h.numpy()
-            if self.pop.gaussian or self.pop.vector_int:  # the env takes [P*N, A] floats / [P*N, K] choices
+            if self.pop.head is not None:  # the env takes [P*N, A] floats / [P*N, K] choices
                 act = act.reshape(self.pop.P * self.pop.N, -1)
             # a MultiBinary population: the env takes its 0 / 1 bits in the space's dtype
             self._act_cast = self.pop.spec.action_dtype if self.pop.multibinary else None
@@ -432,33 +434,15 @@ class PopulationRunner:
         (Gaussian) the clip bounds are taken BEFORE the launch: an allocation
         can wait for the device, which from the launch on waits for this
         thread."""
+        from .learner import act_workspace
+
         pop = self.pop
-        P, N, T = pop.P, pop.N, pop.T
-        tail = (self.args_h.data_ptr(), ctl, self.timeout_s)
-        if pop.gaussian:
-            from .learner import gauss_act_workspace
-
-            gdesc = pop.gauss_descriptor()
-            ws = gauss_act_workspace(pop, gdesc)[1]
-            lo, hi = pop.action_clip() or (None, None)
-            _lib.check(lib.agx_ppo_rollout_gauss_graph_persistent(
-                ctypes.byref(gdesc), pop.spec.log_std, P, N, pop.params.data.data_ptr(), self._ios, T + 1, base,
-                pop.act_seed, pop.act_counter, _lib.ptr(lo), _lib.ptr(hi), *tail, ws.data_ptr(), _lib.stream()),
-                "agx_ppo_rollout_gauss_graph_persistent")
-            return
-        from .learner import vector_act_workspace
-
-        ws = vector_act_workspace(pop)[1]
-        if pop.multibinary:
-            _lib.check(lib.agx_ppo_rollout_bern_graph_persistent(
-                ctypes.byref(pop.bern_descriptor()), P, N, pop.params.data.data_ptr(), self._ios, T + 1, base,
-                pop.act_seed, pop.act_counter, *tail, ws.data_ptr(), _lib.stream()),
-                "agx_ppo_rollout_bern_graph_persistent")
-        else:
-            _lib.check(lib.agx_ppo_rollout_multi_graph_persistent(
-                ctypes.byref(pop.multi_descriptor()), pop.multi_head(), P, N, pop.params.data.data_ptr(), self._ios,
-                T + 1, base, pop.act_seed, pop.act_counter, *tail, ws.data_ptr(), _lib.stream()),
-                "agx_ppo_rollout_multi_graph_persistent")
+        ws = act_workspace(pop, pop.head_descriptor(), pop.head.stem)[1]
+        head_persistent(pop, "rollout",
+                        (pop.P, pop.N, pop.params.data.data_ptr(), self._ios, pop.T + 1, base, pop.act_seed,
+                         pop.act_counter),
+                        (self.args_h.data_ptr(), ctl, self.timeout_s, ws.data_ptr(), _lib.stream()),
+                        clip=pop.action_clip())
 
     def _mark_stats(self) -> None:
         """Event after the rollout's last episode-accounting write: the
@@ -521,17 +505,11 @@ class PopulationRunner:
             self.episodes_env += d.long()
             self.scores.masked_fill_(d, 0.0)
         gdesc = pop.learn_descriptor()
-        if pop.gaussian:  # the bootstrap value from the Gaussian policy-step kernel (sample = 0, values only)
-            from .learner import policy_step_gauss
+        if pop.head is not None:  # the bootstrap value from the head's policy-step kernel (sample = 0, values only)
+            from .learner import policy_step_head
 
-            policy_step_gauss(pop, pop.gauss_descriptor(), self.last_obs, N * pop.spec.obs_dim, sample=False,
-                              counter=0, values=self.last_value, out_agent_stride=N)
-            self.last_value_valid = True
-        elif pop.vector_int:  # ... or from the multi-categorical / Bernoulli one
-            from .learner import policy_step_vector
-
-            policy_step_vector(pop, self.last_obs, N * pop.spec.obs_dim, sample=False,
-                               counter=0, values=self.last_value, out_agent_stride=N)
+            policy_step_head(pop, self.last_obs, N * pop.spec.obs_dim, sample=False, counter=0,
+                             values=self.last_value, out_agent_stride=N)
             self.last_value_valid = True
         elif gdesc is not None:  # a mutated shape: the bootstrap value from the runtime-shape kernel too
             from .learner import policy_step_graph
@@ -852,15 +830,11 @@ class _EvalDriver:
             from .learner import graph_act_workspace
 
             graph_act_workspace(self.pop, self.gdesc)
-        elif pop.gaussian:
-            from .learner import gauss_act_workspace
+        elif pop.head is not None:
+            from .learner import act_workspace
 
-            gauss_act_workspace(pop, pop.gauss_descriptor())
-        elif pop.vector_int:
-            from .learner import vector_act_workspace
-
-            vector_act_workspace(pop)
-        self._clip = pop.action_clip() if pop.gaussian else None  # made now: nothing may allocate while a launch waits
+            act_workspace(pop, pop.head_descriptor(), pop.head.stem)
+        self._clip = pop.action_clip()  # a Box population's, now: nothing may allocate while a launch waits
         self.obs = None
         self.stream = None  # a dedicated non-blocking stream, assigned by run_lockstep
         self._pipelined = False
@@ -922,21 +896,12 @@ class _EvalDriver:
 
     def _launch_head(self, lib, n: int) -> None:
         pop = self.pop
-        head = (self.P, self.N, pop.params.data.data_ptr(), self.obs_h.data_ptr(), self.act_h.data_ptr())
-        tail = (pop.env_base_d.data_ptr(), n, 0, pop.act_seed, self.counter0 + self.step, self.args_h.data_ptr(),
-                self.ctl_h.data_ptr(), self.runner.timeout_s, pop._act_ws[1].data_ptr(), self.stream.cuda_stream)
-        if pop.gaussian:
-            lo, hi = self._clip or (None, None)
-            _lib.check(lib.agx_ppo_eval_gauss_graph_persistent(ctypes.byref(pop.gauss_descriptor()), pop.spec.log_std,
-                                                               *head, _lib.ptr(lo), _lib.ptr(hi), *tail),
-                       "agx_ppo_eval_gauss_graph_persistent")
-        elif pop.multibinary:
-            _lib.check(lib.agx_ppo_eval_bern_graph_persistent(ctypes.byref(pop.bern_descriptor()), *head, *tail),
-                       "agx_ppo_eval_bern_graph_persistent")
-        else:
-            _lib.check(lib.agx_ppo_eval_multi_graph_persistent(ctypes.byref(pop.multi_descriptor()), pop.multi_head(),
-                                                               *head, *tail),
-                       "agx_ppo_eval_multi_graph_persistent")
+        head_persistent(pop, "eval",
+                        (self.P, self.N, pop.params.data.data_ptr(), self.obs_h.data_ptr(), self.act_h.data_ptr()),
+                        (pop.env_base_d.data_ptr(), n, 0, pop.act_seed, self.counter0 + self.step,
+                         self.args_h.data_ptr(), self.ctl_h.data_ptr(), self.runner.timeout_s,
+                         pop._act_ws[1].data_ptr(), self.stream.cuda_stream),
+                        clip=self._clip)
 
     def request(self) -> None:
         """Start the policy step of vector step self.step."""
@@ -955,16 +920,11 @@ class _EvalDriver:
         self.obs_h.numpy()[:] = np.asarray(self.obs).reshape(-1)
         self.obs_d.view(-1).copy_(self.obs_h, non_blocking=True)
         counter = self.counter0 + self.step
-        if pop.gaussian:  # a Box population: the env's copy clipped to the bounds (ppo.py:604-614)
-            from .learner import policy_step_gauss
+        if pop.head is not None:  # the staging in the head's dtype; a Box population's copy clipped (ppo.py:604-614)
+            from .learner import policy_step_head
 
-            policy_step_gauss(pop, pop.gauss_descriptor(), self.obs_d, N * D, sample=True, counter=counter,
-                              out_agent_stride=N, actions_flat=self.act_d, clip=pop.action_clip())
-        elif pop.vector_int:  # a MultiDiscrete / MultiBinary population: int64 [P*N*K] staging
-            from .learner import policy_step_vector
-
-            policy_step_vector(pop, self.obs_d, N * D, sample=True, counter=counter,
-                               out_agent_stride=N, actions_flat=self.act_d)
+            policy_step_head(pop, self.obs_d, N * D, sample=True, counter=counter, out_agent_stride=N,
+                             actions_flat=self.act_d, clip=pop.action_clip())
         elif self.edescs is not None:  # the evaluation layer list (as the multi launch samples)
             from .learner import policy_step_graph
 
@@ -1017,7 +977,7 @@ class _EvalDriver:
             reward = rew_n
         else:
             act = self.act_h.numpy().copy()
-            vec = self.pop.gaussian or self.pop.vector_int  # [P*N, A] floats / [P*N, K] choices
+            vec = self.pop.head is not None  # [P*N, A] floats / [P*N, K] choices
             if self.pop.multibinary:  # 0 / 1 bits in the space's dtype
                 act = act.astype(self.pop.spec.action_dtype)
             self.obs, reward, term, trunc, _ = self.env.step(act.reshape(self.P * self.N, -1) if vec else act)

@@ -61,7 +61,7 @@ def _pair(a, b, calls: int, warmup: int) -> tuple[dict, dict]:
 def policy_step(P=8, N=128, A=6) -> dict:
     from agilerl_amd.algorithms.ppo import spec_from_net_config
     from agilerl_amd.envs import Box, Discrete
-    from agilerl_amd.population.learner import graph_descriptor, policy_step_gauss, policy_step_graph
+    from agilerl_amd.population.learner import graph_descriptor, policy_step_graph, policy_step_head
     from agilerl_amd.population.ppo_pop import PPOPopulation
 
     obs_space = Box(-np.inf, np.inf, (8,))
@@ -73,9 +73,8 @@ def policy_step(P=8, N=128, A=6) -> dict:
 
     def run_gauss():
         counter[0] += 1
-        policy_step_gauss(gauss, gauss.gauss_descriptor(), obs, N * 8, sample=True, counter=counter[0],
-                          actions=gauss.actions[:, 0], log_probs=gauss.log_probs[:, 0], values=gauss.values[:, 0],
-                          out_agent_stride=gauss.T * N)
+        policy_step_head(gauss, obs, N * 8, sample=True, counter=counter[0], actions=gauss.actions[:, 0],
+                         log_probs=gauss.log_probs[:, 0], values=gauss.values[:, 0], out_agent_stride=gauss.T * N)
 
     def run_cat():
         counter[0] += 1
@@ -158,7 +157,7 @@ def fused_learn(P=8, N=128, S=2048, A=6) -> dict:
     cat._fused = GraphLearner(cat)
 
     def run_torch():
-        box.fused = False  # gauss_learn_descriptor() is None: _learn_torch
+        box.fused = False  # head_learn_descriptor() is None: _learn_torch
         try:
             box.learn()
         finally:

@@ -72,29 +72,28 @@ def _spaces(n):
 
 def policy_step(n, P=8, N=128) -> dict:
     from agilerl_amd.algorithms.ppo import spec_from_net_config
-    from agilerl_amd.population.learner import (graph_descriptor, policy_step_bern, policy_step_graph,
-                                                policy_step_multi)
+    from agilerl_amd.population.learner import graph_descriptor, policy_step_graph, policy_step_head
     from agilerl_amd.population.ppo_pop import PPOPopulation
 
     obs_space, binary, discrete, stand_in = _spaces(n)
     bern = PPOPopulation(spec_from_net_config(obs_space, binary, None), P, N, learn_step=2 * N)
     cat = PPOPopulation(spec_from_net_config(obs_space, discrete, None), P, N, learn_step=2 * N)
-    cdesc, bdesc = graph_descriptor(cat.spec), bern.bern_descriptor()
+    cdesc = graph_descriptor(cat.spec)
     obs = torch.randn(P, N, 8, device="cuda")
     counter = [0]
 
-    def step(fn, pop, desc):
+    def step(fn, pop, *desc):
         def go():
             counter[0] += 1
-            fn(pop, desc, obs, N * 8, sample=True, counter=counter[0], actions=pop.actions[:, 0],
+            fn(pop, *desc, obs, N * 8, sample=True, counter=counter[0], actions=pop.actions[:, 0],
                log_probs=pop.log_probs[:, 0], values=pop.values[:, 0], out_agent_stride=pop.T * N)
         return go
 
-    fns = {"agx_ppo_act_bern_graph": step(policy_step_bern, bern, bdesc),
+    fns = {"agx_ppo_act_bern_graph": step(policy_step_head, bern),
            "agx_ppo_act_graph": step(policy_step_graph, cat, cdesc)}
     if stand_in is not None:
         multi = PPOPopulation(spec_from_net_config(obs_space, stand_in, None), P, N, learn_step=2 * N)
-        fns["agx_ppo_act_multi_graph_2x16"] = step(policy_step_multi, multi, multi.multi_descriptor())
+        fns["agx_ppo_act_multi_graph_2x16"] = step(policy_step_head, multi)
     out = _group(fns, calls=2000, warmup=200)
     out.update(what="policy step per vector step", shape=f"{P} agents x {N} envs, n = {n} bits, default networks",
                ratio_to_categorical=_ratio(out["agx_ppo_act_bern_graph"], out["agx_ppo_act_graph"]))
@@ -126,7 +125,7 @@ def fused_learn(n, P=8, N=128, S=2048) -> dict:
     cat._fused = GraphLearner(cat)
 
     def run_torch():
-        bern.fused = False  # bern_learn_descriptor() is None: _learn_torch
+        bern.fused = False  # head_learn_descriptor() is None: _learn_torch
         try:
             bern.learn()
         finally:

@@ -65,7 +65,7 @@ def _pair(a, b, calls: int, warmup: int) -> tuple[dict, dict]:
 def policy_step(nvec, P=8, N=128) -> dict:
     from agilerl_amd.algorithms.ppo import spec_from_net_config
     from agilerl_amd.envs import Box, Discrete, MultiDiscrete
-    from agilerl_amd.population.learner import graph_descriptor, policy_step_graph, policy_step_multi
+    from agilerl_amd.population.learner import graph_descriptor, policy_step_graph, policy_step_head
     from agilerl_amd.population.ppo_pop import PPOPopulation
 
     obs_space = Box(-np.inf, np.inf, (8,))
@@ -73,14 +73,13 @@ def policy_step(nvec, P=8, N=128) -> dict:
     multi = PPOPopulation(spec_from_net_config(obs_space, MultiDiscrete(nvec), None), P, N, learn_step=2 * N)
     cat = PPOPopulation(spec_from_net_config(obs_space, Discrete(L), None), P, N, learn_step=2 * N)
     cdesc = graph_descriptor(cat.spec)
-    mdesc = multi.multi_descriptor()
     obs = torch.randn(P, N, 8, device="cuda")
     counter = [0]
 
     def run_multi():
         counter[0] += 1
-        policy_step_multi(multi, mdesc, obs, N * 8, sample=True, counter=counter[0], actions=multi.actions[:, 0],
-                          log_probs=multi.log_probs[:, 0], values=multi.values[:, 0], out_agent_stride=multi.T * N)
+        policy_step_head(multi, obs, N * 8, sample=True, counter=counter[0], actions=multi.actions[:, 0],
+                         log_probs=multi.log_probs[:, 0], values=multi.values[:, 0], out_agent_stride=multi.T * N)
 
     def run_cat():
         counter[0] += 1
@@ -166,7 +165,7 @@ def fused_learn(nvec, P=8, N=128, S=2048) -> dict:
     cat._fused = GraphLearner(cat)
 
     def run_torch():
-        multi.fused = False  # multi_learn_descriptor() is None: _learn_torch
+        multi.fused = False  # head_learn_descriptor() is None: _learn_torch
         try:
             multi.learn()
         finally:
