@@ -95,15 +95,4 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // the device's CU count, queried once (runtime.hip)
 int cu_count();
 
-// The gather prologue of both fused PPO learners (defined in learner.hip):
-// permuted, advantage-normalised, minibatch-ordered copy of the rollout.
-__global__ void ppo_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
-                                  const float *__restrict__ old_logp, const float *__restrict__ adv,
-                                  const float *__restrict__ ret, const float *__restrict__ old_v,
-                                  const double *__restrict__ adv_stats, const long long *__restrict__ perms,
-                                  const unsigned char *__restrict__ masks, int A, long long S, int D, int P,
-                                  float *__restrict__ gobs, int *__restrict__ gact, unsigned *__restrict__ gmask,
-                                  float *__restrict__ grow, unsigned *__restrict__ counters, int ncounters,
-                                  const int *__restrict__ epochs_p, unsigned *__restrict__ err);
-
 }  // namespace agx

@@ -30,8 +30,11 @@
 // (shared with the policy step, graph_rollout.hip); this unit is the backward,
 // the learn kernels and their host side.
 //
-// HEAD (a compile-time parameter of the three kernels): kCat, the categorical
-// head of a Discrete action space; kGauss and kMulti below.
+// HEAD (a compile-time parameter of the learn kernels, ppo_learn_graph_kernel
+// and the two forms of ppo_learn_graph_part_kernel): kCat, the categorical
+// head of a Discrete action space; kGauss, kMulti and kBern below.  The gather
+// prologue is ppo_gather.h's kernel over the head's action packer; what else
+// the host path knows of a head is HeadTraits.
 //
 // kGauss: the diagonal-Gaussian
 // head of a Box action space (include/agx_gauss.h).  The actor's output is the
@@ -61,6 +64,8 @@
 #include "bern_head.h"
 #include "gauss_head.h"
 #include "graph_net.h"
+#include "multi_head_check.h"
+#include "ppo_gather.h"
 #include "ppo_loss_sample.h"
 
 namespace agx {
@@ -1931,19 +1936,72 @@ __global__ __launch_bounds__(kGT) void ppo_learn_graph_part_kernel(const GArgs g
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct GraphWs {
-    size_t gobs, gact, gmask, grow, agents, total;
+// What a head's entry points pass besides the net (validated by their checks)
+struct HeadArg {
+    long long lso = -1;      // kGauss: log_std's offset in the parameter row
+    agx_multi_head multi{};  // kMulti: the components, those past K zeroed
 };
-// aw: 4-byte words of a row's gathered action (1: the categorical index; A: a Gaussian head's floats)
+// What the host path knows of a head: the parameters no layer owns (plan_graph's
+// `extra`), the gather's action packer (ppo_gather.h; its words() sizes gact),
+// and what the head writes into GArgs.
+struct PlainHead {  // the categorical network as it is
+    static int extra(const agx_ppo_graph *) { return 0; }
+    static void fill(GArgs &a, const HeadArg &) { a.lso = -1; }
+};
+template <Head HEAD>
+struct HeadTraits;
+template <>
+struct HeadTraits<kCat> : PlainHead {
+    using Pack = CatPack;
+    static Pack pack(const HeadArg &) { return {}; }
+};
+template <>
+struct HeadTraits<kBern> : PlainHead {
+    using Pack = BernPack;
+    static Pack pack(const HeadArg &) { return {}; }
+};
+template <>
+struct HeadTraits<kGauss> {
+    static int extra(const agx_ppo_graph *net) { return net->n_actions; }  // log_std
+    static void fill(GArgs &a, const HeadArg &h) { a.lso = h.lso; }
+    using Pack = GaussPack;
+    static Pack pack(const HeadArg &) { return {}; }
+};
+template <>
+struct HeadTraits<kMulti> : PlainHead {
+    static void fill(GArgs &a, const HeadArg &h) {
+        PlainHead::fill(a, h);
+        a.mk = h.multi.K;
+        for (int k = 0; k < h.multi.K; ++k) a.mn[k >> 2] |= (unsigned)h.multi.nvec[k] << (8 * (k & 3));
+    }
+    using Pack = MultiPack;
+    static Pack pack(const HeadArg &h) { return {h.multi}; }
+};
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// The gather's output in either workspace, from byte `at` (a multiple of 256).
+// aw: 4-byte words of a row's gathered action (Pack::words)
+struct GatherWs {
+    size_t gobs, gact, gmask, grow, end;
+};
+GatherWs gather_ws(size_t at, const GArgs &a, int64_t P, int64_t S, int64_t epochs, int aw) {
+    GatherWs w;
+    const size_t per = (size_t)epochs * P * S;
+    w.gobs = at;
+    w.gact = w.gobs + up256(per * a.D * 4);
+    w.gmask = w.gact + up256(per * 4 * aw);
+    w.grow = w.gmask + up256(per * 4);
+    w.end = w.grow + up256(per * 4 * 4);
+    return w;
+}
+struct GraphWs {
+    GatherWs g;
+    size_t agents, total;
+};
 GraphWs graph_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int aw) {
     GraphWs w;
-    const size_t per = (size_t)epochs * P * S;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    w.gobs = 0;
-    w.gact = up(per * a.D * 4);
-    w.gmask = w.gact + up(per * 4 * aw);
-    w.grow = w.gmask + up(per * 4);
-    w.agents = w.grow + up(per * 4 * 4);
+    w.g = gather_ws(0, a, P, S, epochs, aw);
+    w.agents = w.g.end;
     w.total = w.agents + (size_t)P * a.ws_agent * 4;
     return w;
 }
@@ -1984,7 +2042,7 @@ size_t few_lds_budget() {
 // (0: the plan does not fit, or the graph is invalid)
 template <Head HEAD>
 size_t plan_few(const agx_ppo_graph *net, GArgs &a) {
-    if (plan_graph(net, kFR, a, HEAD == kGauss ? net->n_actions : 0) != AGX_OK) return 0;
+    if (plan_graph(net, kFR, a, HeadTraits<HEAD>::extra(net)) != AGX_OK) return 0;
     auto ldof = [](int w) { return (w + 15) / 16 * 16 + 4; };
     long long off = 0;
     int ldmax = 0;
@@ -2066,186 +2124,35 @@ Split graph_split(const agx_ppo_graph *net, int64_t P, int64_t batch) {
     return sp;
 }
 struct PartWs {
-    size_t cnt, gobs, gact, gmask, grow, scratch, wt, slabs, sums, total;
+    size_t cnt;  // the counters the gather zeroes: [cnt, g.gobs)
+    GatherWs g;
+    size_t scratch, wt, slabs, sums, total;
     long long nslab;
 };
 PartWs part_ws(const GArgs &a, int64_t P, int64_t S, int64_t epochs, int K, int aw) {
     PartWs w;
-    const size_t per = (size_t)epochs * P * S;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     w.cnt = 0;
-    w.gobs = up(((size_t)4 * P + 1 + (size_t)kMaxGK * P) * 4);
-    w.gact = w.gobs + up(per * a.D * 4);
-    w.gmask = w.gact + up(per * 4 * aw);
-    w.grow = w.gmask + up(per * 4);
-    w.scratch = w.grow + up(per * 4 * 4);
-    w.wt = w.scratch + up((size_t)P * K * a.ws_part * 4);
+    w.g = gather_ws(up256(((size_t)4 * P + 1 + (size_t)kMaxGK * P) * 4), a, P, S, epochs, aw);
+    w.scratch = w.g.end;
+    w.wt = w.scratch + up256((size_t)P * K * a.ws_part * 4);
     w.nslab = ((long long)(a.n + 3) / 4 * 4 + 4 + 2 * kGW * K + 63) / 64 * 64;
-    w.slabs = w.wt + up((size_t)P * a.wt_agent * 4);
-    w.sums = w.slabs + up((size_t)P * 2 * K * w.nslab * 4);
+    w.slabs = w.wt + up256((size_t)P * a.wt_agent * 4);
+    w.sums = w.slabs + up256((size_t)P * 2 * K * w.nslab * 4);
     w.total = w.sums + (size_t)P * 2 * w.nslab * 4;
     return w;
 }
 
-// ppo_gather_kernel (learner.hip) for a Gaussian head: the rollout's float
-// actions [P][S][A] gathered in minibatch order to gact [E P][S][A]; the
-// observations, the advantage normalisation, the rollout rows, the counters
-// and the permutation check as there.
-__global__ void ppo_gauss_gather_kernel(const float *__restrict__ obs, const float *__restrict__ act,
-                                        const float *__restrict__ old_logp, const float *__restrict__ adv,
-                                        const float *__restrict__ ret, const float *__restrict__ old_v,
-                                        const double *__restrict__ adv_stats, const long long *__restrict__ perms,
-                                        int A, long long S, int D, int P, float *__restrict__ gobs,
-                                        float *__restrict__ gact, float *__restrict__ grow,
-                                        unsigned *__restrict__ counters, int ncounters,
-                                        const int *__restrict__ epochs_p, unsigned *__restrict__ err) {
-    const int ep = blockIdx.y;  // e * P + p
-    const int p = ep % P;
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int i = threadIdx.x; i < ncounters; i += blockDim.x) counters[i] = 0u;
-    if (j >= S) return;
-    if (epochs_p && ep / P >= epochs_p[p]) return;
-    long long src = perms[(size_t)ep * S + j];
-    if (src < 0 || src >= S) {
-        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        src = 0;
-    }
-    const size_t sp = (size_t)p * S + src, dst = (size_t)ep * S + j;
-    for (int d = 0; d < D; ++d) gobs[dst * D + d] = obs[sp * D + d];
-    for (int d = 0; d < A; ++d) gact[dst * A + d] = act[sp * A + d];
-    float *gr = grow + (size_t)ep * 4 * S;
-    double a = adv[sp];
-    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
-    gr[j] = old_logp[sp];
-    gr[S + j] = (float)a;
-    gr[2 * S + j] = ret[sp];
-    gr[3 * S + j] = old_v[sp];
-}
-
-// ppo_gather_kernel (learner.hip) for a multi-categorical head: the rollout's
-// int64 actions [P][S][K] packed into one target word per row (bit off_k + a_k
-// set for every component, a_k clamped into [0, n_k): never a bit outside the
-// component) and the flat masks [P][S][L] into the categorical gather's word
-// (bit j = logit j legal), both in minibatch order; the observations, the
-// advantage normalisation, the rollout rows, the counters and the permutation
-// check as there.
-__global__ void ppo_multi_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
-                                        const float *__restrict__ old_logp, const float *__restrict__ adv,
-                                        const float *__restrict__ ret, const float *__restrict__ old_v,
-                                        const double *__restrict__ adv_stats, const long long *__restrict__ perms,
-                                        const unsigned char *__restrict__ masks, const agx_multi_head head, int L,
-                                        long long S, int D, int P, float *__restrict__ gobs,
-                                        unsigned *__restrict__ gtgt, unsigned *__restrict__ gmask,
-                                        float *__restrict__ grow, unsigned *__restrict__ counters, int ncounters,
-                                        const int *__restrict__ epochs_p, unsigned *__restrict__ err) {
-    const int ep = blockIdx.y;  // e * P + p
-    const int p = ep % P;
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.y == 0)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncounters; i += gridDim.x * blockDim.x)
-            counters[i] = 0u;
-    if (j >= S) return;
-    if (epochs_p && ep / P >= epochs_p[p]) return;
-    long long src = perms[(size_t)ep * S + j];
-    if (src < 0 || src >= S) {
-        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        src = 0;
-    }
-    const size_t sp = (size_t)p * S + src, dst = (size_t)ep * S + j;
-    for (int d = 0; d < D; ++d) gobs[dst * D + d] = obs[sp * D + d];
-    const int K = head.K;
-    unsigned tgt = 0;
-    int off = 0;
-    for (int k = 0; k < K; ++k) {
-        const int n = head.nvec[k];
-        long long a = act[sp * K + k];
-        a = a < 0 ? 0 : (a >= n ? n - 1 : a);
-        tgt |= 1u << (off + (int)a);
-        off += n;
-    }
-    gtgt[dst] = tgt;
-    if (masks) {  // [P][S][L] u8 -> one bit per logit
-        unsigned bits = 0;
-        for (int a = 0; a < L; ++a) bits |= (masks[sp * L + a] != 0 ? 1u : 0u) << a;
-        gmask[dst] = bits;
-    }
-    float *gr = grow + (size_t)ep * 4 * S;
-    double a = adv[sp];
-    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
-    gr[j] = old_logp[sp];
-    gr[S + j] = (float)a;
-    gr[2 * S + j] = ret[sp];
-    gr[3 * S + j] = old_v[sp];
-}
-
-// ppo_multi_gather_kernel for a Bernoulli head: the rollout's int64 actions
-// [P][S][n] packed into one target word per row (bit j = a_j != 0) and the
-// flat masks [P][S][n] into the categorical gather's word; the rest as there.
-__global__ void ppo_bern_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
-                                       const float *__restrict__ old_logp, const float *__restrict__ adv,
-                                       const float *__restrict__ ret, const float *__restrict__ old_v,
-                                       const double *__restrict__ adv_stats, const long long *__restrict__ perms,
-                                       const unsigned char *__restrict__ masks, int n, long long S, int D, int P,
-                                       float *__restrict__ gobs, unsigned *__restrict__ gtgt,
-                                       unsigned *__restrict__ gmask, float *__restrict__ grow,
-                                       unsigned *__restrict__ counters, int ncounters,
-                                       const int *__restrict__ epochs_p, unsigned *__restrict__ err) {
-    const int ep = blockIdx.y;  // e * P + p
-    const int p = ep % P;
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.y == 0)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncounters; i += gridDim.x * blockDim.x)
-            counters[i] = 0u;
-    if (j >= S) return;
-    if (epochs_p && ep / P >= epochs_p[p]) return;
-    long long src = perms[(size_t)ep * S + j];
-    if (src < 0 || src >= S) {
-        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        src = 0;
-    }
-    const size_t sp = (size_t)p * S + src, dst = (size_t)ep * S + j;
-    for (int d = 0; d < D; ++d) gobs[dst * D + d] = obs[sp * D + d];
-    unsigned tgt = 0;
-    for (int a = 0; a < n; ++a) tgt |= (act[sp * n + a] != 0 ? 1u : 0u) << a;
-    gtgt[dst] = tgt;
-    if (masks) {  // [P][S][n] u8 -> one bit per logit
-        unsigned bits = 0;
-        for (int a = 0; a < n; ++a) bits |= (masks[sp * n + a] != 0 ? 1u : 0u) << a;
-        gmask[dst] = bits;
-    }
-    float *gr = grow + (size_t)ep * 4 * S;
-    double a = adv[sp];
-    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
-    gr[j] = old_logp[sp];
-    gr[S + j] = (float)a;
-    gr[2 * S + j] = ret[sp];
-    gr[3 * S + j] = old_v[sp];
-}
-
 // A head the multi-categorical learner takes: a layer list agx_ppo_graph_check
-// admits, K >= 1 components of n_k >= 1 choices, sum n_k == net->n_actions.
-// -> the head with the components past K zeroed (the kernels never read them)
-int multi_check(const char *who, const agx_ppo_graph *net, const agx_multi_head &h, agx_multi_head *out = nullptr) {
+// admits and a head that fits it (multi_head_check.h).
+// -> h.multi: the head with the components past K zeroed (the kernels never read them)
+int multi_check(const char *who, const agx_ppo_graph *net, const agx_multi_head &head, HeadArg &h) {
     GArgs a{};
     AGX_REQUIRE(net, "%s: null graph", who);
-    const int rc = plan_graph(net, 1, a);
-    if (rc != AGX_OK) return rc;
-    AGX_REQUIRE(h.K >= 1 && h.K <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d components (1..%d)", who, h.K,
-                AGX_PPO_GRAPH_MAX_ACTIONS);
-    int L = 0;
-    for (int k = 0; k < h.K; ++k) {
-        AGX_REQUIRE(h.nvec[k] >= 1 && h.nvec[k] <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: component %d has %d choices (1..%d)",
-                    who, k, h.nvec[k], AGX_PPO_GRAPH_MAX_ACTIONS);
-        L += h.nvec[k];
-    }
-    AGX_REQUIRE(L <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d logits (1..%d)", who, L, AGX_PPO_GRAPH_MAX_ACTIONS);
-    AGX_REQUIRE(L == net->n_actions, "%s: nvec sums to %d, the actor's output has %d logits", who, L, net->n_actions);
-    if (out) {
-        *out = agx_multi_head{};
-        out->K = h.K;
-        for (int k = 0; k < h.K; ++k) out->nvec[k] = h.nvec[k];
-    }
+    if (int rc = plan_graph(net, 1, a)) return rc;
+    const int L = head_width(head, who);
+    if (L < 0) return AGX_EINVAL;
+    if (int rc = head_fits(net, L, who)) return rc;
+    h.multi = head_arg(head);
     return AGX_OK;
 }
 
@@ -2298,8 +2205,10 @@ size_t learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t 
     GArgs a{};
     if (P <= 0 || S <= 0 || epochs <= 0 || batch <= 0) return 0;
     const int64_t bb = batch < S ? batch : S;
-    const int extra = HEAD == kGauss ? net->n_actions : 0, aw = HEAD == kGauss ? net->n_actions : 1;
+    using T = HeadTraits<HEAD>;
+    const int extra = T::extra(net);
     if (plan_graph(net, bb, a, extra) != AGX_OK) return 0;
+    const int aw = T::Pack::words(a.A);
     size_t total = graph_ws(a, P, S, epochs, aw).total;
     const Split sp = graph_split<HEAD>(net, P, bb);
     if (sp.K > 1) {  // room for either kernel: the split may change with the call's batch
@@ -2316,13 +2225,12 @@ long long *&g_graph_stamps() {
     return p;
 }
 
-// agx_ppo_learn_graph (kGauss: agx_ppo_learn_gauss_graph, log_std at lso;
-// kMulti: agx_ppo_learn_multi_graph, the components of `head`; both validated
-// by the caller; kBern: agx_ppo_learn_bern_graph); `what` names the entry point
-// in errors
+// The learn call of a head's entry point `what` (named in errors); h: validated by the caller
 template <Head HEAD>
-int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const agx_ppo_learn_args *x,
-                void *workspace, void *stream, const agx_multi_head *head = nullptr) {
+int learn_graph(const char *what, const agx_ppo_graph *net, const HeadArg &h, const agx_ppo_learn_args *x,
+                void *workspace, void *stream) {
+    using T = HeadTraits<HEAD>;
+    using Pack = typename T::Pack;
     AGX_REQUIRE(x->params && x->exp_avg && x->exp_avg_sq && x->adam_step && x->lr && x->obs && x->actions &&
                     x->old_logp && x->adv && x->ret && x->old_value && x->perms,
                 "%s: null pointer", what);
@@ -2334,62 +2242,35 @@ int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const
     const Split sp = graph_split<HEAD>(net, P, bb);
     const int K = sp.K, R = sp.R, Q = sp.Q;
     GArgs a{};
-    const int extra = HEAD == kGauss ? net->n_actions : 0, aw = HEAD == kGauss ? net->n_actions : 1;
-    const int rc = plan_graph(net, K > 1 ? R : bb, a, extra);
+    const int rc = plan_graph(net, K > 1 ? R : bb, a, T::extra(net));
     if (rc != AGX_OK) return rc;
     if (sp.few) AGX_REQUIRE(plan_few<HEAD>(net, a) == sp.dyn, "%s: few-row plan changed", what);
-    a.lso = lso;
-    if constexpr (HEAD == kMulti) {
-        a.mk = head->K;
-        for (int k = 0; k < head->K; ++k) a.mn[k >> 2] |= (unsigned)head->nvec[k] << (8 * (k & 3));
-    }
+    T::fill(a, h);
+    const int aw = Pack::words(a.A);
     char *ws = static_cast<char *>(workspace);
     hipStream_t s = as_stream(stream);
-    size_t o_gobs, o_gact, o_gmask, o_grow;
     unsigned *counters = nullptr;
     int ncounters = 0;
     PartWs pw{};
     GraphWs w{};
     if (K > 1) {
         pw = part_ws(a, P, S, epochs, K, aw);
-        o_gobs = pw.gobs, o_gact = pw.gact, o_gmask = pw.gmask, o_grow = pw.grow;
         counters = reinterpret_cast<unsigned *>(ws + pw.cnt);
-        ncounters = (int)(pw.gobs / sizeof(unsigned));
+        ncounters = (int)(pw.g.gobs / sizeof(unsigned));
     } else {
         w = graph_ws(a, P, S, epochs, aw);
-        o_gobs = w.gobs, o_gact = w.gact, o_gmask = w.gmask, o_grow = w.grow;
     }
-    float *gobs = reinterpret_cast<float *>(ws + o_gobs);
-    int *gact = reinterpret_cast<int *>(ws + o_gact);
-    unsigned *gmask = x->action_masks ? reinterpret_cast<unsigned *>(ws + o_gmask) : nullptr;
-    float *grow = reinterpret_cast<float *>(ws + o_grow);
+    const GatherWs &gw = K > 1 ? pw.g : w.g;
+    float *gobs = reinterpret_cast<float *>(ws + gw.gobs);
+    int *gact = reinterpret_cast<int *>(ws + gw.gact);
+    unsigned *gmask = x->action_masks ? reinterpret_cast<unsigned *>(ws + gw.gmask) : nullptr;
+    float *grow = reinterpret_cast<float *>(ws + gw.grow);
     dim3 ggrid((unsigned)ceil_div(S, 256), (unsigned)(epochs * P));
-    if constexpr (HEAD == kGauss)
-        ppo_gauss_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const float *>(x->actions), x->old_logp,
-                                                      x->adv, x->ret, x->old_value, x->adv_stats,
-                                                      reinterpret_cast<const long long *>(x->perms), a.A, S, a.D,
-                                                      (int)P, gobs, reinterpret_cast<float *>(gact), grow, counters,
-                                                      ncounters, x->epochs_per_agent, x->error_word);
-    else if constexpr (HEAD == kMulti)
-        ppo_multi_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
-                                                      x->adv, x->ret, x->old_value, x->adv_stats,
-                                                      reinterpret_cast<const long long *>(x->perms), x->action_masks,
-                                                      *head, a.A, S, a.D, (int)P, gobs,
-                                                      reinterpret_cast<unsigned *>(gact), gmask, grow, counters,
-                                                      ncounters, x->epochs_per_agent, x->error_word);
-    else if constexpr (HEAD == kBern)
-        ppo_bern_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
-                                                     x->adv, x->ret, x->old_value, x->adv_stats,
-                                                     reinterpret_cast<const long long *>(x->perms), x->action_masks,
-                                                     a.A, S, a.D, (int)P, gobs, reinterpret_cast<unsigned *>(gact),
-                                                     gmask, grow, counters, ncounters, x->epochs_per_agent,
-                                                     x->error_word);
-    else
-        ppo_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
-                                                x->adv, x->ret, x->old_value, x->adv_stats,
-                                                reinterpret_cast<const long long *>(x->perms), x->action_masks, a.A,
-                                                S, a.D, (int)P, gobs, gact, gmask, grow, counters, ncounters,
-                                                x->epochs_per_agent, x->error_word);
+    ppo_gather_kernel<Pack><<<ggrid, 256, 0, s>>>(
+        x->obs, reinterpret_cast<const typename Pack::Elem *>(x->actions), x->old_logp, x->adv, x->ret, x->old_value,
+        x->adv_stats, reinterpret_cast<const long long *>(x->perms), x->action_masks, a.A, T::pack(h), S, a.D, (int)P,
+        gobs, reinterpret_cast<typename Pack::Word *>(gact), gmask, grow, counters, ncounters, x->epochs_per_agent,
+        x->error_word);
     const int rc2 = check_launch(what);
     if (rc2) return rc2;
     a.ws = reinterpret_cast<float *>(ws + (K > 1 ? pw.scratch : w.agents));
@@ -2451,6 +2332,23 @@ int learn_graph(const char *what, const agx_ppo_graph *net, long long lso, const
     return check_launch(what);
 }
 
+// The entry points of a head: its check (check(h): the head's rules, filling h), then the query / the call
+template <Head HEAD, class Check>
+size_t checked_workspace_bytes(Check check, const agx_ppo_graph *net, int64_t P, int64_t S, int64_t epochs,
+                               int64_t batch) {
+    HeadArg h;
+    if (check(h) != AGX_OK) return 0;
+    return learn_graph_workspace_bytes<HEAD>(net, P, S, epochs, batch);
+}
+template <Head HEAD, class Check>
+int checked_learn(const char *what, Check check, const agx_ppo_graph *net, const agx_ppo_learn_args *x,
+                  void *workspace, void *stream) {
+    AGX_REQUIRE(net && x && workspace, "%s: null net / args / workspace", what);
+    HeadArg h;
+    if (int rc = check(h)) return rc;
+    return learn_graph<HEAD>(what, net, h, x, workspace, stream);
+}
+
 }  // namespace
 }  // namespace agx
 
@@ -2468,13 +2366,12 @@ extern "C" int agx_ppo_graph_check(const agx_ppo_graph *net) {
 
 extern "C" size_t agx_ppo_learn_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S,
                                                       int64_t epochs, int64_t batch) {
-    return learn_graph_workspace_bytes<kCat>(net, P, S, epochs, batch);
+    return checked_workspace_bytes<kCat>([](HeadArg &) { return AGX_OK; }, net, P, S, epochs, batch);
 }
 
 extern "C" int agx_ppo_learn_graph(const agx_ppo_graph *net, const agx_ppo_learn_args *x, void *workspace,
                                    void *stream) {
-    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_graph: null net / args / workspace");
-    return learn_graph<kCat>("agx_ppo_learn_graph", net, -1, x, workspace, stream);
+    return checked_learn<kCat>("agx_ppo_learn_graph", [](HeadArg &) { return AGX_OK; }, net, x, workspace, stream);
 }
 
 extern "C" int agx_ppo_gauss_graph_check(const agx_ppo_graph *net, int64_t log_std_off) {
@@ -2483,36 +2380,36 @@ extern "C" int agx_ppo_gauss_graph_check(const agx_ppo_graph *net, int64_t log_s
 
 extern "C" size_t agx_ppo_learn_gauss_graph_workspace_bytes(const agx_ppo_graph *net, int64_t log_std_off, int64_t P,
                                                             int64_t S, int64_t epochs, int64_t batch) {
-    if (gauss_check(net, log_std_off) != AGX_OK) return 0;
-    return learn_graph_workspace_bytes<kGauss>(net, P, S, epochs, batch);
+    return checked_workspace_bytes<kGauss>([&](HeadArg &) { return gauss_check(net, log_std_off); }, net, P, S, epochs,
+                                           batch);
 }
 
 extern "C" int agx_ppo_learn_gauss_graph(const agx_ppo_graph *net, int64_t log_std_off, const agx_ppo_learn_args *x,
                                          void *workspace, void *stream) {
-    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_gauss_graph: null net / args / workspace");
-    const int rc = gauss_check(net, log_std_off);
-    if (rc != AGX_OK) return rc;
-    AGX_REQUIRE(!x->action_masks, "agx_ppo_learn_gauss_graph: action masks do not apply to a Gaussian head");
-    return learn_graph<kGauss>("agx_ppo_learn_gauss_graph", net, log_std_off, x, workspace, stream);
+    auto check = [&](HeadArg &h) -> int {
+        if (int rc = gauss_check(net, log_std_off)) return rc;
+        AGX_REQUIRE(!x->action_masks, "agx_ppo_learn_gauss_graph: action masks do not apply to a Gaussian head");
+        h.lso = log_std_off;
+        return AGX_OK;
+    };
+    return checked_learn<kGauss>("agx_ppo_learn_gauss_graph", check, net, x, workspace, stream);
 }
 
 extern "C" int agx_ppo_multi_graph_check(const agx_ppo_graph *net, agx_multi_head head) {
-    return multi_check("agx_ppo_multi_graph_check", net, head);
+    HeadArg h;
+    return multi_check("agx_ppo_multi_graph_check", net, head, h);
 }
 
 extern "C" size_t agx_ppo_learn_multi_graph_workspace_bytes(const agx_ppo_graph *net, agx_multi_head head, int64_t P,
                                                             int64_t S, int64_t epochs, int64_t batch) {
-    if (multi_check("agx_ppo_learn_multi_graph_workspace_bytes", net, head) != AGX_OK) return 0;
-    return learn_graph_workspace_bytes<kMulti>(net, P, S, epochs, batch);
+    auto check = [&](HeadArg &h) { return multi_check("agx_ppo_learn_multi_graph_workspace_bytes", net, head, h); };
+    return checked_workspace_bytes<kMulti>(check, net, P, S, epochs, batch);
 }
 
 extern "C" int agx_ppo_learn_multi_graph(const agx_ppo_graph *net, agx_multi_head head, const agx_ppo_learn_args *x,
                                          void *workspace, void *stream) {
-    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_multi_graph: null net / args / workspace");
-    agx_multi_head hd;
-    const int rc = multi_check("agx_ppo_learn_multi_graph", net, head, &hd);
-    if (rc != AGX_OK) return rc;
-    return learn_graph<kMulti>("agx_ppo_learn_multi_graph", net, -1, x, workspace, stream, &hd);
+    auto check = [&](HeadArg &h) { return multi_check("agx_ppo_learn_multi_graph", net, head, h); };
+    return checked_learn<kMulti>("agx_ppo_learn_multi_graph", check, net, x, workspace, stream);
 }
 
 extern "C" int agx_ppo_bern_graph_check(const agx_ppo_graph *net) {
@@ -2523,14 +2420,12 @@ extern "C" int agx_ppo_bern_graph_check(const agx_ppo_graph *net) {
 
 extern "C" size_t agx_ppo_learn_bern_graph_workspace_bytes(const agx_ppo_graph *net, int64_t P, int64_t S,
                                                            int64_t epochs, int64_t batch) {
-    if (agx_ppo_bern_graph_check(net) != AGX_OK) return 0;
-    return learn_graph_workspace_bytes<kBern>(net, P, S, epochs, batch);
+    return checked_workspace_bytes<kBern>([&](HeadArg &) { return agx_ppo_bern_graph_check(net); }, net, P, S, epochs,
+                                          batch);
 }
 
 extern "C" int agx_ppo_learn_bern_graph(const agx_ppo_graph *net, const agx_ppo_learn_args *x, void *workspace,
                                         void *stream) {
-    AGX_REQUIRE(net && x && workspace, "agx_ppo_learn_bern_graph: null net / args / workspace");
-    const int rc = agx_ppo_bern_graph_check(net);
-    if (rc != AGX_OK) return rc;
-    return learn_graph<kBern>("agx_ppo_learn_bern_graph", net, -1, x, workspace, stream);
+    return checked_learn<kBern>("agx_ppo_learn_bern_graph", [&](HeadArg &) { return agx_ppo_bern_graph_check(net); },
+                                net, x, workspace, stream);
 }

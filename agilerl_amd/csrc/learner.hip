@@ -49,6 +49,7 @@
 #include <type_traits>
 
 #include "agx_common.h"
+#include "ppo_gather.h"
 #include "rollout.h"
 
 namespace agx {
@@ -2082,56 +2083,6 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
 }
 
 // ---------------------------------------------------------------------------
-// prologue: permute the rollout SoA into minibatch order, normalise advantages
-// ---------------------------------------------------------------------------
-__global__ void ppo_gather_kernel(const float *__restrict__ obs, const long long *__restrict__ act,
-                                  const float *__restrict__ old_logp, const float *__restrict__ adv,
-                                  const float *__restrict__ ret, const float *__restrict__ old_v,
-                                  const double *__restrict__ adv_stats, const long long *__restrict__ perms,
-                                  const unsigned char *__restrict__ masks, int A,
-                                  long long S, int D, int P, float *__restrict__ gobs, int *__restrict__ gact,
-                                  unsigned *__restrict__ gmask, float *__restrict__ grow,
-                                  unsigned *__restrict__ counters, int ncounters, const int *__restrict__ epochs_p,
-                                  unsigned *__restrict__ err) {
-    const int ep = blockIdx.y;  // e * P + p
-    const int p = ep % P;
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    // the learner's arrival counters + timeout word (stream-ordered before it;
-    // replaces a separate memset launch) and its tagged hand-off words, spread
-    // over the blocks of the first (epoch, agent) row
-    if (blockIdx.y == 0)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncounters; i += gridDim.x * blockDim.x)
-            counters[i] = 0u;
-    if (j >= S) return;
-    // epochs beyond an agent's own update_epochs: the learner never reads
-    // them, and their perms rows are not part of the contract (agx.h)
-    if (epochs_p && ep / P >= epochs_p[p]) return;
-    long long src = perms[(size_t)ep * S + j];
-    if (src < 0 || src >= S) {
-        // a host-side slip must not become a device fault: flag it in the
-        // caller's sticky error word (bit 2; PPOPopulation.check_errors raises
-        // AgxError) and gather row 0 in its place
-        if (err) __hip_atomic_fetch_or(err, AGX_LEARN_ERR_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        src = 0;
-    }
-    const size_t sp = (size_t)p * S + src;
-    for (int d = 0; d < D; ++d) gobs[((size_t)ep * S + j) * D + d] = obs[sp * D + d];
-    gact[(size_t)ep * S + j] = (int)act[sp];
-    if (masks) {  // [P][S][A] u8 -> one bit per action
-        unsigned bits = 0;
-        for (int a = 0; a < A; ++a) bits |= (masks[sp * A + a] != 0 ? 1u : 0u) << a;
-        gmask[(size_t)ep * S + j] = bits;
-    }
-    float *gr = grow + (size_t)ep * 4 * S;
-    double a = adv[sp];
-    if (adv_stats) a = (a - adv_stats[2 * p]) * (1.0 / (adv_stats[2 * p + 1] + 1e-8));  // == adv_normalize_kernel
-    gr[j] = old_logp[sp];
-    gr[S + j] = (float)a;
-    gr[2 * S + j] = ret[sp];
-    gr[3 * S + j] = old_v[sp];
-}
-
-// ---------------------------------------------------------------------------
 // rollout policy step
 // ---------------------------------------------------------------------------
 // One policy step of workgroup (p, n0).  resident: the parameters (and the
@@ -2539,11 +2490,11 @@ extern "C" int agx_ppo_learn(const agx_ppo_net *net, const agx_ppo_learn_args *x
     AGX_REQUIRE(Q * K <= 65535, "agx_ppo_learn: too many workgroups");
     // counters + timeout word: one 16-byte-multiple block at the workspace start, zeroed by the gather
     dim3 ggrid((unsigned)ceil_div(S, 256), (unsigned)(epochs * P));
-    ppo_gather_kernel<<<ggrid, 256, 0, s>>>(x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp,
-                                            x->adv, x->ret, x->old_value, x->adv_stats,
-                                            reinterpret_cast<const long long *>(x->perms), x->action_masks, pl.A, S,
-                                            pl.D, (int)P, gobs, gact, gmask, grow, reinterpret_cast<unsigned *>(ws),
-                                            (int)(w.gobs / sizeof(unsigned)), x->epochs_per_agent, x->error_word);
+    ppo_gather_kernel<CatPack><<<ggrid, 256, 0, s>>>(
+        x->obs, reinterpret_cast<const long long *>(x->actions), x->old_logp, x->adv, x->ret, x->old_value,
+        x->adv_stats, reinterpret_cast<const long long *>(x->perms), x->action_masks, pl.A, CatPack{}, S, pl.D, (int)P,
+        gobs, gact, gmask, grow, reinterpret_cast<unsigned *>(ws), (int)(w.gobs / sizeof(unsigned)),
+        x->epochs_per_agent, x->error_word);
     const int rc2 = check_launch("agx_ppo_learn gather");
     if (rc2) return rc2;
     LearnArgs a;

@@ -24,6 +24,7 @@
 #include "../../include/agx_multi.h"
 #include "graph_net.h"
 #include "head_policy.h"
+#include "multi_head_check.h"
 #include "ppo_loss_sample.h"
 #include "rollout.h"
 
@@ -246,41 +247,12 @@ __global__ __launch_bounds__(256) void ppo_multi_loss_kernel(
     finish_group<64>(acc, k, m, lane, stats);
 }
 
-// K, nvec and L = sum nvec of a head -> L, or -1 with the error set
-int head_width(const agx_multi_head &h, const char *who) {
-    if (h.K < 1 || h.K > AGX_PPO_GRAPH_MAX_ACTIONS) {
-        set_error("%s: %d components (1..%d)", who, h.K, AGX_PPO_GRAPH_MAX_ACTIONS);
-        return -1;
-    }
-    int L = 0;
-    for (int k = 0; k < h.K; ++k) {
-        if (h.nvec[k] < 1 || h.nvec[k] > AGX_PPO_GRAPH_MAX_ACTIONS) {
-            set_error("%s: component %d has %d choices (1..%d)", who, k, h.nvec[k], AGX_PPO_GRAPH_MAX_ACTIONS);
-            return -1;
-        }
-        L += h.nvec[k];
-    }
-    if (L > AGX_PPO_GRAPH_MAX_ACTIONS) {
-        set_error("%s: %d logits (1..%d)", who, L, AGX_PPO_GRAPH_MAX_ACTIONS);
-        return -1;
-    }
-    return L;
-}
-
 }  // namespace
 }  // namespace agx
 
 using namespace agx;
 
 namespace {
-// head with the components past K zeroed (they are never read): what the kernels take by value
-agx_multi_head head_arg(const agx_multi_head &head) {
-    agx_multi_head h{};
-    h.K = head.K;
-    for (int k = 0; k < head.K; ++k) h.nvec[k] = head.nvec[k];
-    return h;
-}
-
 // the rules of every multi-categorical entry point for the net and the head -> the plan and the
 // persistent kernel's head
 int multi_plan(const agx_ppo_graph *net, const agx_multi_head &head, GArgs &full, MultiRolloutHead &h,
@@ -288,7 +260,7 @@ int multi_plan(const agx_ppo_graph *net, const agx_multi_head &head, GArgs &full
     const int L = head_width(head, who);
     if (L < 0) return AGX_EINVAL;
     if (int rc = plan_graph(net, 1, full)) return rc;
-    AGX_REQUIRE(L == net->n_actions, "%s: nvec sums to %d, the actor's output has %d logits", who, L, net->n_actions);
+    if (int rc = head_fits(net, L, who)) return rc;
     h.head = head_arg(head);
     return AGX_OK;
 }
