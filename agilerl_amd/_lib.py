@@ -118,6 +118,7 @@ SIGNATURES = {
     "agx_stream_create": (_P, []),
     "agx_host_signal": (_INT, [_P, ctypes.c_uint32]),
     "agx_host_wait": (_INT, [_P, _I, ctypes.c_uint32, _D]),
+    "agx_host_signal_wait": (_INT, [_P, ctypes.c_uint32, _I, ctypes.c_uint32, _D]),
     "agx_host_signal_range": (_INT, [_P, _I, _I, ctypes.c_uint32]),
     "agx_host_wait_range": (_INT, [_P, _I, _I, ctypes.c_uint32, _D]),
     "agx_host_signal_wait_range": (_INT, [_P, _I, _I, ctypes.c_uint32, _I, _I, ctypes.c_uint32, _D]),

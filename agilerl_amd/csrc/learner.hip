@@ -529,7 +529,9 @@ __device__ __forceinline__ int lds_to_flat(int l, int &group) {
 // ---------------------------------------------------------------------------
 // shared forward (X0 in LDS -> y_h in S1, logits in lg, value in val)
 // ---------------------------------------------------------------------------
-template <class C, int SB = kSB>
+// INF (the rollout's policy step): no backward pass follows, so xhat and rstd
+// are not stored; every value that is computed is computed as before
+template <class C, int SB = kSB, bool INF = false>
 struct Fwd {
     static constexpr LearnPlan pl = C::plan;
     static_assert(SB == 8 || SB == 16 || SB == 32, "sub-batch rows");
@@ -571,7 +573,7 @@ struct Fwd {
         }
         const float r0 = 1.f / sqrtf(wrow_sum<W>(v0) / (float)F0 + 1e-5f);
         const float r1 = F1 > 0 ? 1.f / sqrtf(wrow_sum<W>(v1) / (float)(F1 > 0 ? F1 : 1) + 1e-5f) : 0.f;
-        if (sub == 0) {
+        if (!INF && sub == 0) {
             sm[rb + 2 * r] = r0;
             sm[rb + 2 * r + 1] = r1;
         }
@@ -583,7 +585,7 @@ struct Fwd {
         for (int i = 0; i < NC; ++i) {
             const int j = sub + W * i;
             const float xh = W * i < split ? (z[i] - m0) * r0 : (z[i] - m1) * r1;
-            sm[xb + r * ldx + j] = xh;
+            if (!INF) sm[xb + r * ldx + j] = xh;
             const float y = gb >= 0 ? relu(xh * sm[gb + j] + sm[bb + j]) : relu(xh);
             sm[pl.l_s1 + r * pl.ld_s + j] = y;
             if constexpr (OUT) {
@@ -2086,12 +2088,30 @@ __global__ __launch_bounds__(kNT, 1) void ppo_learn_kernel(LearnArgs g) {
 // rollout policy step
 // ---------------------------------------------------------------------------
 // One policy step of workgroup (p, n0).  resident: the parameters (and the
-// zeroed padding of the parameter region) are already in LDS from an earlier
-// step of the same persistent launch; only the activations are re-zeroed.
+// zeroed padding of the parameter region and of x0) are already in LDS from
+// an earlier step of the same persistent launch.
 // st (diagnostic, may be null): s_memrealtime after the host reads landed,
 // after the forward, after the outputs were issued (thread 0 only)
-template <class C>
-__device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resident, long long *st = nullptr) {
+//
+// PS: a step of the persistent kernel, which takes off the path from the
+// host's release to the done word what the next action does not need (the
+// per-step kernel keeps the plain order):
+//  - a resident step does not re-zero the activations.  The zeros of the
+//    launch's first step protect only what no step writes: the padding
+//    columns [D, rup(D,16)) of x0 (the commit writes all kSB rows of columns
+//    [0, D), dead rows as zeros).  Every other column a GEMM reads was written
+//    in the same step by the LayerNorm pass before it (S1 columns [0, eout),
+//    K = eout exactly, so a wider layer's stale columns are never read), every
+//    S2 column the LayerNorm reads by the GEMM before it, lg / val by the
+//    head's row pass;
+//  - the forward stores no xhat / rstd (Fwd's INF);
+//  - `noise` is the lane's Gumbel noise log(-log u), computed before the wait;
+//  - the workgroup's actions go to the host staging from consecutive lanes of
+//    wave 0 (whole 64-byte lines), not from lane 0 of every row group: 1024
+//    scattered 8-byte writes per step delayed the done words behind them.
+template <class C, bool PS = false>
+__device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resident, float noise = 0.f,
+                                         long long *st = nullptr) {
     constexpr LearnPlan pl = C::plan;
     const int p = blockIdx.y, n0 = blockIdx.x * kSB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2120,8 +2140,10 @@ __device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resid
             if (tid + k * kNT < nrow * pl.D) oc[tid + k * kNT] = obv[k];
     }
     if (!g.act) return;
-    for (int i = resident ? pl.param_end + tid : tid; i < pl.act_floats; i += kNT) sm[i] = 0.f;
-    __syncthreads();
+    if (!resident || !PS) {
+        for (int i = resident ? pl.param_end + tid : tid; i < pl.act_floats; i += kNT) sm[i] = 0.f;
+        __syncthreads();
+    }
     if (!resident) load_params<C>(sm, g.params + (size_t)p * pl.n, tid);
 #pragma unroll
     for (int k = 0; k < kObsIt; ++k) {
@@ -2129,7 +2151,7 @@ __device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resid
         if (i < kSB * pl.D) sm[pl.l_x0 + (i / pl.D) * pl.ld_x0 + i % pl.D] = obv[k];
     }
     __syncthreads();
-    Fwd<C> fw{sm};
+    Fwd<C, kSB, PS> fw{sm};
     fw.run();
     if (st && tid == 0) st[1] = (long long)__builtin_amdgcn_s_memrealtime();
     // categorical over 16 lanes per row
@@ -2148,8 +2170,12 @@ __device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resid
     const float H = -row_sum(a < pl.A ? pa * logf(pa + 1e-8f) : 0.f);
     float score = lg;
     if (g.sample) {
-        const unsigned long long env = stream_env(-1, g.env_base, p, g.N, n0 + r);
-        score = a < pl.A ? gumbel_score(lg, a, env, g.seed, g.counter) : -3.0e38f;
+        if constexpr (PS) {
+            score = a < pl.A ? lg - noise : -3.0e38f;  // gumbel_score's bits
+        } else {
+            const unsigned long long env = stream_env(-1, g.env_base, p, g.N, n0 + r);
+            score = a < pl.A ? gumbel_score(lg, a, env, g.seed, g.counter) : -3.0e38f;
+        }
     }
     const float best = row_max(score);
     const unsigned long long ball = __ballot(score == best);
@@ -2162,9 +2188,22 @@ __device__ __forceinline__ void act_body(const ActArgs &g, float *sm, bool resid
         if (g.logp_out) g.logp_out[o] = lgc - lse;
         if (g.ent_out) g.ent_out[o] = H;
         if (g.value_out) g.value_out[o] = sm[pl.l_val + r];
-        if (g.act_flat)  // host memory: system-scope (write-through) store
-            __hip_atomic_store(g.act_flat + (size_t)p * g.N + n0 + r, (long long)choice, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
+        if (g.act_flat) {  // host memory: system-scope (write-through) store
+            if constexpr (PS)  // through the row's own logit slot, which only this lane read
+                sm[pl.l_lg + r * kMaxA] = __builtin_bit_cast(float, choice);
+            else
+                __hip_atomic_store(g.act_flat + (size_t)p * g.N + n0 + r, (long long)choice, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    if constexpr (PS) {
+        if (g.act_flat) {  // uniform
+            __syncthreads();
+            if (tid < nrow)  // env n0 + tid from lane tid: consecutive int64 words
+                __hip_atomic_store(g.act_flat + (size_t)p * g.N + n0 + tid,
+                                   (long long)__builtin_bit_cast(int, sm[pl.l_lg + tid * kMaxA]), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
     if (st && tid == 0) st[2] = (long long)__builtin_amdgcn_s_memrealtime();
 }
@@ -2202,8 +2241,21 @@ __global__ __launch_bounds__(kNT, 1) void ppo_rollout_persistent_kernel(const Ac
     for (int t = 0; t < nsteps; ++t) {
         long long *st = stamps && blk == 0 && t < 32 ? stamps + 8 * t : nullptr;
         if (st && tid == 0) st[0] = (long long)__builtin_amdgcn_s_memrealtime();
+        // Up to the wait the host is stepping the env.  The argument blocks
+        // were written before the launch, so the step's block is fetched now ...
         if (tid < kArgWords)
             reinterpret_cast<unsigned *>(&s_args)[tid] = reinterpret_cast<const unsigned *>(steps + t)[tid];
+        __syncthreads();
+        const ActArgs g = s_args;
+        // ... and the lane's Gumbel noise (act_body's row / action mapping), which
+        // depends on (env, seed, counter) only, is computed
+        float noise = 0.f;
+        {
+            const int lane = tid & 63, a = lane & 15, r = (tid >> 6) + kNW * (lane >> 4);
+            if (g.act && g.sample && a < pl.A)
+                noise = gumbel_noise(a, stream_env(-1, g.env_base, blockIdx.y, g.N, blockIdx.x * kSB + r), g.seed,
+                                     g.counter);
+        }
         if (tid == 0) {
             s_go = wait_release(rel, ctl, base, t, timeout_ticks);
             if (st) st[1] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -2211,8 +2263,7 @@ __global__ __launch_bounds__(kNT, 1) void ppo_rollout_persistent_kernel(const Ac
         }
         __syncthreads();
         if (!s_go) return;
-        const ActArgs g = s_args;
-        act_body<C>(g, sm, t > 0 && pl.param_end > 0, st ? st + 2 : nullptr);
+        act_body<C, true>(g, sm, t > 0 && pl.param_end > 0, noise, st ? st + 2 : nullptr);
         step_stores_acked();
         if (st && tid == 0) st[5] = (long long)__builtin_amdgcn_s_memrealtime();
         if (stamps && tid == 0 && t == 5 && blk < 64) stamps[320 + blk] = (long long)__builtin_amdgcn_s_memrealtime();

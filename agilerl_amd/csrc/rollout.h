@@ -160,14 +160,20 @@ __device__ __forceinline__ unsigned long long stream_env(long long env_off, cons
 // of (env, counter ^ (a >> 2) << 56) -> u in (0, 1) -> lg - log(-log u).
 // The callers call it under their own `a < A ? .. : -3e38`: hoisted out of that
 // test it costs ppo_rollout_persistent_kernel a wave of occupancy.
-__device__ __forceinline__ float gumbel_score(float lg, int a, unsigned long long env, unsigned long long seed,
+// gumbel_noise is the part that does not depend on the logit, log(-log u): a
+// persistent step computes it while it waits for the host's release.
+__device__ __forceinline__ float gumbel_noise(int a, unsigned long long env, unsigned long long seed,
                                               unsigned long long counter) {
     const uint4 rnd = philox(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)counter,
                                         (unsigned)(counter >> 32) ^ ((unsigned)(a >> 2) << 24)),
                              make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
     const unsigned w = (a & 3) == 0 ? rnd.x : (a & 3) == 1 ? rnd.y : (a & 3) == 2 ? rnd.z : rnd.w;
     const float u = ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    return lg - logf(-logf(u));
+    return logf(-logf(u));
+}
+__device__ __forceinline__ float gumbel_score(float lg, int a, unsigned long long env, unsigned long long seed,
+                                              unsigned long long counter) {
+    return lg - gumbel_noise(a, env, seed, counter);
 }
 
 // ---------------------------------------------------------------------------

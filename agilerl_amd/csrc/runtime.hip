@@ -188,6 +188,15 @@ extern "C" int agx_host_signal_wait_range(agx_rollout_ctl *ctl, int64_t s0, int6
     return rc != AGX_OK ? rc : agx_host_wait_range(ctl, w0, w1, target, timeout_s);
 }
 
+// release every workgroup to seq, then wait until the first nwg reach target:
+// one call for a pacing loop whose release is always followed by its own wait
+extern "C" int agx_host_signal_wait(agx_rollout_ctl *ctl, uint32_t seq, int64_t nwg, uint32_t target,
+                                    double timeout_s) {
+    AGX_REQUIRE(ctl, "agx_host_signal_wait: null ctl");
+    const int rc = agx_host_signal(ctl, seq);
+    return rc != AGX_OK ? rc : agx_host_wait(ctl, nwg, target, timeout_s);
+}
+
 extern "C" int agx_host_wait(const agx_rollout_ctl *ctl, int64_t nwg, uint32_t target, double timeout_s) {
     AGX_REQUIRE(ctl && nwg > 0, "agx_host_wait: bad arguments");
     const uint32_t *done = agx::rollout_done_words(const_cast<agx_rollout_ctl *>(ctl));

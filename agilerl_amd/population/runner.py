@@ -21,8 +21,8 @@ never): the whole
 rollout is ONE launch (agx_ppo_rollout_persistent) whose workgroups keep the
 parameters in LDS and are paced step by step through a control block in
 coherent host memory — the host releases step t after the env step
-(agx_host_signal) and spins on the workgroups' done words (agx_host_wait),
-so a vector step costs no launch and no event wait.  Staging, actions and
+and spins on the workgroups' done words (agx_host_signal_wait: both in one
+native call), so a vector step costs no launch and no event wait.  Staging, actions and
 the control block then live in coherent (fine-grained) host memory, which
 the device re-reads within one launch.
 
@@ -455,9 +455,9 @@ class PopulationRunner:
     def _pace_persistent(self, lib, ctl, base) -> None:
         T = self.pop.T
         try:
-            for t in range(T):
-                lib.agx_host_signal(ctl, base + t + 1)
-                _lib.check(lib.agx_host_wait(ctl, self.n_wg, base + t + 1, self.timeout_s), "agx_host_wait")
+            for t in range(T):  # release step t and wait for its actions: one native call
+                _lib.check(lib.agx_host_signal_wait(ctl, base + t + 1, self.n_wg, base + t + 1, self.timeout_s),
+                           "agx_host_wait")
                 self._env_step()
             lib.agx_host_signal(ctl, base + T + 1)  # reward/done of step T-1, final obs, bootstrap value
         except BaseException:
@@ -600,8 +600,7 @@ class PopulationRunner:
         c = self.begin_iteration()
         try:
             while c.t < self.pop.T:
-                self.pace_release(c)
-                self.pace_wait_step(c)
+                self.pace_step(c)
         except BaseException:
             self.abort_iteration(c)
             raise
@@ -651,6 +650,17 @@ class PopulationRunner:
         """Wait for released step c.t, step the env; after the last step the
         release of the final obs / bootstrap value."""
         _lib.check(c.lib.agx_host_wait(c.ctl, self.n_wg, c.base + c.t + 1, self.timeout_s), "agx_host_wait")
+        self._step_released(c)
+
+    def pace_step(self, c: "_IterCtx") -> None:
+        """pace_release + pace_wait_step in one native call: for a host that
+        paces this runner alone, where a release is always followed by its
+        own wait."""
+        seq = c.base + c.t + 1
+        _lib.check(c.lib.agx_host_signal_wait(c.ctl, seq, self.n_wg, seq, self.timeout_s), "agx_host_wait")
+        self._step_released(c)
+
+    def _step_released(self, c: "_IterCtx") -> None:
         self._env_step()
         c.t += 1
         if c.t == self.pop.T:

@@ -333,6 +333,10 @@ int agx_host_signal(agx_rollout_ctl *ctl, uint32_t seq);
 /* spin until every done word >= target; AGX_EHIP on ctl->timeout or after
  * timeout_s */
 int agx_host_wait(const agx_rollout_ctl *ctl, int64_t nwg, uint32_t target, double timeout_s);
+/* agx_host_signal(ctl, seq) then agx_host_wait(ctl, nwg, target, timeout_s):
+ * one call per vector step for a pacing loop whose release is always followed
+ * by its own wait */
+int agx_host_signal_wait(agx_rollout_ctl *ctl, uint32_t seq, int64_t nwg, uint32_t target, double timeout_s);
 /* the same for workgroups [w0, w1) only (ctl->seq untouched): a host that
  * paces two halves of a launch, stepping one half's envs while the other
  * half's workgroups run */

@@ -27,21 +27,14 @@ lib = _lib.load()
 T = pop.T
 dev_t, env_t, launch_t = [], [], []
 orig_env = run._env_step
-orig_sig, orig_wait = lib.agx_host_signal, lib.agx_host_wait
-marks = {}
+orig_sigwait = lib.agx_host_signal_wait
 
 
-class Sig:
-    def __call__(self, ctl, seq):
-        marks["s"] = time.perf_counter()
-        return orig_sig(ctl, seq)
-
-
-class Wait:
-    def __call__(self, *a):
-        rc = orig_wait(*a)
-        dev_t.append(time.perf_counter() - marks["s"])
-        return rc
+def sigwait(*a):  # the pacing loop's one call per vector step: release, then wait for every done word
+    t0 = time.perf_counter()
+    rc = orig_sigwait(*a)
+    dev_t.append(time.perf_counter() - t0)
+    return rc
 
 
 def env_step():
@@ -50,7 +43,7 @@ def env_step():
     env_t.append(time.perf_counter() - t0)
 
 
-lib.agx_host_signal, lib.agx_host_wait = Sig(), Wait()
+lib.agx_host_signal_wait = sigwait
 run._env_step = env_step
 for _ in range(20):
     torch.cuda.synchronize()
@@ -60,7 +53,7 @@ for _ in range(20):
     pop.finish_rollout(run.last_obs, run.last_done, run.last_value)
     pop.learn()
 torch.cuda.synchronize()
-lib.agx_host_signal, lib.agx_host_wait = orig_sig, orig_wait
+lib.agx_host_signal_wait = orig_sigwait
 dev_t = sorted(dev_t)
 print(f"device step (signal -> all done): median {1e6 * dev_t[len(dev_t) // 2]:.1f} us, "
       f"p10 {1e6 * dev_t[len(dev_t) // 10]:.1f}, p90 {1e6 * dev_t[9 * len(dev_t) // 10]:.1f}; "
@@ -68,20 +61,25 @@ print(f"device step (signal -> all done): median {1e6 * dev_t[len(dev_t) // 2]:.
 print(f"env step {1e6 * sum(env_t) / len(env_t):.1f} us; collect {1e3 * sum(launch_t) / len(launch_t):.3f} ms "
       f"({1e6 * sum(launch_t) / len(launch_t) / T:.1f} us/step)")
 
-# in-kernel phases of workgroup 0 (s_memrealtime, 100 MHz)
+# in-kernel phases of workgroup 0 (s_memrealtime, 100 MHz), pooled over 8 stamped rollouts
 buf = torch.zeros(384, dtype=torch.int64, device="cuda")
-lib.agx_debug_rollout_stamps(ctypes.c_void_p(buf.data_ptr()))
-run.collect()
-lib.agx_debug_rollout_stamps(None)
-pop.finish_rollout(run.last_obs, run.last_done, run.last_value)
-torch.cuda.synchronize()
-st = buf[:256].view(32, 8).cpu().numpy()[:T + 1].astype(float) * 10.0  # ns
 names = ["wait for host", "host reads", "scatter+zero+forward", "sample+stores", "store acks"]
-ph = [st[1:T, k + 1] - st[1:T, k] for k in range(5)]
-print("in-kernel phases (us, median over steps 1..T-1): " +
-      ", ".join(f"{n} {float(sorted(x)[len(x) // 2]) / 1e3:.2f}" for n, x in zip(names, ph)))
-gap = st[2:T, 1] - st[1:T - 1, 5]
-print(f"done -> next release seen: {float(sorted(gap)[len(gap) // 2]) / 1e3:.2f} us (host detect + env step + signal)")
+ph, gap, step = [[] for _ in names], [], []
+for _ in range(8):
+    lib.agx_debug_rollout_stamps(ctypes.c_void_p(buf.data_ptr()))
+    run.collect()
+    lib.agx_debug_rollout_stamps(None)
+    pop.finish_rollout(run.last_obs, run.last_done, run.last_value)
+    torch.cuda.synchronize()
+    st = buf[:256].view(32, 8).cpu().numpy()[:T + 1].astype(float) * 10.0  # ns
+    for k in range(5):
+        ph[k] += list(st[1:T, k + 1] - st[1:T, k])
+    step += list(st[1:T, 5] - st[1:T, 1])
+    gap += list(st[2:T, 1] - st[1:T - 1, 5])
+med = lambda x: float(np.median(x)) / 1e3  # noqa: E731
+print("in-kernel phases (us, median over steps 1..T-1): " + ", ".join(f"{n} {med(x):.2f}" for n, x in zip(names, ph)))
+print(f"workgroup 0, release seen -> stores acknowledged: median {med(step):.2f} us")
+print(f"done -> next release seen: {med(gap):.2f} us (host detect + env step + signal)")
 nwg = run.n_wg
 b = buf.cpu().numpy().astype(float) * 10.0
 go, dn = b[256:256 + nwg], b[320:320 + nwg]
