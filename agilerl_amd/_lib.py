@@ -140,11 +140,13 @@ SIGNATURES = {
     "agx_td3_smooth_actions": (_INT, [_P] * 4 + [_I, _I, _D, _P, _P]),
     "agx_td3_workspace_bytes": (_SZ, [_I]),
     "agx_td3_critic_target": (_INT, [_P] * 6 + [_I, _D] + [_P] * 6),
+    "agx_matd3_critic_target": (_INT, [_P] * 6 + [_I, _D] + [_P] * 6),
     "agx_c51_project_loss": (_INT, [_P] * 7 + [_I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_c51_project_loss_rows": (_INT, [_P] * 5 + [_I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_adam_workspace_bytes": (_SZ, [_I, _I]),
     "agx_clip_adam": (_INT, [_P, _P, _P, _P, _I, _I, _P, _INT, _F, _P, _F, _F, _F, _P, _P, _P, _P]),
     "agx_polyak": (_INT, [_P, _P, _I, _F, _P]),
+    "agx_polyak_segments": (_INT, [_P, _INT, _F, _P]),
     "agx_noisy_reset": (_INT, [_P, _INT, _P]),
     "agx_noisy_streams_forward": (_INT, [_P, _INT, _INT, _P, _I, _F, _P]),
     "agx_noisy_streams_forward_each": (_INT, [_P, _INT, _INT, _P, _I, _F, _P]),

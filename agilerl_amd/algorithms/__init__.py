@@ -3,7 +3,8 @@
 from .ddpg import DDPG
 from .dqn import DQN, RainbowDQN
 from .maddpg import MADDPG
+from .matd3 import MATD3
 from .ppo import PPO
 from .td3 import TD3
 
-__all__ = ["PPO", "DQN", "RainbowDQN", "MADDPG", "DDPG", "TD3"]
+__all__ = ["PPO", "DQN", "RainbowDQN", "MADDPG", "MATD3", "DDPG", "TD3"]

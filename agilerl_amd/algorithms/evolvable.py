@@ -1,6 +1,6 @@
 """The EvolvableAlgorithm hooks the reference's Mutations call
 (agilerl/algorithms/core/base.py:744-775, hpo/mutation.py:413-453, 515-570)
-for the object-level agents (DQN, RainbowDQN, DDPG, TD3, MADDPG):
+for the object-level agents (DQN, RainbowDQN, DDPG, TD3, MADDPG, MATD3):
 
 * ``registry``            the agent's HyperparameterConfig (hpo/registry.py);
 * ``get_lr_names``        the attributes that are learning rates;
@@ -28,7 +28,7 @@ from .flat_state import flat_state
 
 class NetGroup(NamedTuple):
     """Attribute names of one eval network, its target copy, its optimizer and
-    the learning rate that drives it (each a dict keyed by agent id in MADDPG)."""
+    the learning rate that drives it (each a dict keyed by agent id in MADDPG / MATD3)."""
     net: str
     target: str
     opt: str
@@ -94,12 +94,14 @@ class EvolvableAgentMixin:
                 adam = lambda m: torch.optim.Adam(m.parameters(), lr=lr)  # noqa: E731
                 setattr(self, g.opt, {a: adam(m) for a, m in net.items()} if hasattr(net, "items") else adam(net))
 
-    def _step(self, group, max_norm: float = 0.0) -> None:
+    def _step(self, group, max_norm: float = 0.0, key=None) -> None:
         """Where the reference calls ``optimizer.step()``: one launch over the
-        group's flat buffers (flat_state.py), else the torch optimizer."""
-        fs = flat_state(self, group)
+        group's flat buffers (flat_state.py), else the torch optimizer.
+        ``key``: the agent id, for a group of dicts."""
+        fs = flat_state(self, group) if key is None else flat_state(self, group, key)
         if fs is None or not fs.step(max_norm):
-            getattr(self, group[2]).step()
+            opt = getattr(self, group[2])
+            (opt if key is None else opt[key]).step()
 
     @torch.no_grad()
     def soft_update(self, group=None) -> None:

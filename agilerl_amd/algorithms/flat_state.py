@@ -168,27 +168,32 @@ class FlatLearnState:
         _lib.call("agx_polyak", self.tgt.data_ptr(), self.prm.data_ptr(), self.n, float(tau), _lib.stream())
 
 
-def flat_state(agent, group=None) -> FlatLearnState | None:
+def flat_state(agent, group=None, key=None) -> FlatLearnState | None:
     """The valid flat state of one of the agent's network groups (names of
     net, target, optimizer; default: the first, the policy group), adopting
     its current tensors when a mutation, clone or checkpoint load replaced
     them, or None where it does not apply (CPU, an optimizer other than
-    plain single-group Adam).  Cached per agent under the net's name."""
+    plain single-group Adam).  Cached per agent under the net's name.  For a
+    group whose attributes are dicts keyed by agent id (MATD3), ``key`` picks
+    the member: one flat state per (group, key), cached under that pair."""
     first = agent._groups[0]
     name = (group or first)[0]
     actor, target, opt = (getattr(agent, n) for n in (group or first)[:3])
+    if key is not None:
+        actor, target, opt = actor[key], target[key], opt[key]
     if agent.device.type != "cuda" or not _plain_adam(opt):
         return None
     # rows of a live RainbowPopulationLearner: it owns the tensors (a learner
     # that was released, or tensors the agent has since replaced, do not count)
-    owned = agent.__dict__.get("_pop_rows") if name == first[0] else None
+    owned = agent.__dict__.get("_pop_rows") if name == first[0] and key is None else None
     if owned is not None:
         learner, ptrs = owned[0](), owned[1]
         if learner is not None and tuple(p.data_ptr() for p in actor.parameters()) == ptrs:
             return None
         agent.__dict__.pop("_pop_rows", None)
     cache = agent.__dict__.setdefault("_flat", {})
-    fs = cache.get(name)
+    slot = name if key is None else (name, key)
+    fs = cache.get(slot)
     if fs is None or not fs.valid(actor, target, opt):
-        fs = cache[name] = FlatLearnState(actor, target, opt)
+        fs = cache[slot] = FlatLearnState(actor, target, opt)
     return fs

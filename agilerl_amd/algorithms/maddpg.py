@@ -11,6 +11,11 @@ gamma Q'(s', a'), MSE and its gradient — is one libagx launch
 (``agx_maddpg_critic_target``); soft updates are ``agx_polyak``.  Grouped
 (shared-policy) agents, action masks and env-defined actions are outside the
 hot path.
+
+Everything but the update itself — construction, exploration noise,
+``get_action``, ``test``, the architecture mutation over the network groups —
+lives in ``_MultiAgentPolicyGradient``, which ``MATD3`` (algorithms/matd3.py)
+shares.
 """
 
 from __future__ import annotations
@@ -40,21 +45,19 @@ def _action_dim(space) -> int:
     return int(space.n) if hasattr(space, "n") else int(np.prod(space.shape))
 
 
-class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
-    algo = "MADDPG"
-    # maddpg.py:424-444: the actors are the policy group (targets shared); one
-    # optimizer set per learning rate, every attribute a dict keyed by agent id
-    _groups = (NetGroup("actors", "actor_targets", "actor_optimizers", "lr_actor"),
-               NetGroup("critics", "critic_targets", "critic_optimizers", "lr_critic"))
+_ACTORS = NetGroup("actors", "actor_targets", "actor_optimizers", "lr_actor")
+
+
+class _MultiAgentPolicyGradient(EvolvableAgentMixin, C.TorchCheckpointMixin):
+    """MADDPG / MATD3: the actors group (the policy group, targets shared),
+    then one group per set of centralised critics; one optimizer set per
+    group, every attribute a dict keyed by agent id."""
+
     _ckpt_spaces = False
 
-    def __init__(self, observation_spaces, action_spaces, agent_ids: list[str] | None = None,
-                 O_U_noise: bool = True, expl_noise: float = 0.1, vect_noise_dim: int = 1, mean_noise: float = 0.0,
-                 theta: float = 0.15, dt: float = 1e-2, index: int = 0, hp_config=None,
-                 net_config: dict[str, Any] | None = None, batch_size: int = 64, lr_actor: float = 0.001,
-                 lr_critic: float = 0.01, learn_step: int = 5, gamma: float = 0.95, tau: float = 0.01, mut=None,
-                 normalize_images: bool = True, actor_networks=None, critic_networks=None, device="cuda",
-                 accelerator=None, torch_compiler=None, wrap: bool = True) -> None:
+    def _setup(self, observation_spaces, action_spaces, agent_ids, O_U_noise, expl_noise, vect_noise_dim, mean_noise,
+               theta, dt, index, hp_config, net_config, batch_size, lr_actor, lr_critic, learn_step, gamma, tau, mut,
+               custom_networks, device, policy_freq=None) -> None:
         assert learn_step >= 1, "Learn step must be greater than or equal to one."
         assert isinstance(learn_step, int), "Learn step rate must be an integer."
         assert isinstance(batch_size, int), "Batch size must be an integer."
@@ -66,7 +69,10 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
         assert isinstance(gamma, float), "Gamma must be a float."
         assert isinstance(tau, float), "Tau must be a float."
         assert tau > 0, "Tau must be greater than zero."
-        if actor_networks is not None or critic_networks is not None:
+        if policy_freq is not None:
+            assert isinstance(policy_freq, int), "Policy frequency must be an integer."
+            assert policy_freq > 0, "Policy frequency must be greater than zero."
+        if any(n is not None for n in custom_networks):
             raise NotImplementedError("custom actor/critic modules: use net_config (MLP) networks")
         if agent_ids is None:
             agent_ids = list(observation_spaces.keys()) if hasattr(observation_spaces, "keys") else \
@@ -98,18 +104,24 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
 
         agent_cfgs = self._agent_configs(net_config)
         critic_cfg = self._critic_config(agent_cfgs)
-        self.actors = torch.nn.ModuleDict({a: self._actor(a, agent_cfgs[a]) for a in self.agent_ids})
-        self.actor_targets = torch.nn.ModuleDict({a: self._actor(a, agent_cfgs[a]) for a in self.agent_ids})
-        self.critics = torch.nn.ModuleDict({a: self._critic(critic_cfg) for a in self.agent_ids})
-        self.critic_targets = torch.nn.ModuleDict({a: self._critic(critic_cfg) for a in self.agent_ids})
+        made = {}
+        for name in self._construction_order():
+            policy = name in _ACTORS[:2]
+            made[name] = torch.nn.ModuleDict({a: self._actor(a, agent_cfgs[a]) if policy else self._critic(critic_cfg)
+                                              for a in self.agent_ids})
+        for net, target, _ in self._triples():
+            setattr(self, net, made[net])
+            setattr(self, target, made[target])
         for a in self.agent_ids:
-            self.actor_targets[a].load_state_dict(self.actors[a].state_dict())
-            self.critic_targets[a].load_state_dict(self.critics[a].state_dict())
+            for net, target, _ in self._triples():
+                getattr(self, target)[a].load_state_dict(getattr(self, net)[a].state_dict())
         # the networks' own generators (EvolvableModule.rng, shared with their
-        # modules; seeded from the agent's initial index so a run is reproducible)
+        # modules; seeded from the agent's initial index so a run is reproducible;
+        # a second set of critics draws from a stream of its own)
         for i, a in enumerate(self.agent_ids):
             self.actors[a].rng = np.random.default_rng((0x5EED, int(index), i))
-            self.critics[a].rng = np.random.default_rng((0x5EEE, int(index), i))
+            for k, g in enumerate(self._groups[1:]):
+                getattr(self, g.net)[a].rng = np.random.default_rng((0x5EEE, int(index), i) + ((k,) if k else ()))
             # maddpg.py:346-347: the actors' encoders do not mutate (the critic's
             # encoder is of another type)
             self.actors[a].encoder.disable_mutations()
@@ -118,6 +130,12 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
         self._init_registry(hp_config)
 
     # ---- network construction (maddpg.py:296-380) ---------------------------
+    def _construction_order(self) -> list[str]:
+        """The network dicts in the order they are constructed, which is the
+        order their initialisation draws from torch's generator: each
+        group's networks, then its targets."""
+        return [name for g in self._groups for name in g[:2]]
+
     def _agent_configs(self, net_config) -> dict[str, dict]:
         net_config = copy.deepcopy(as_config(net_config) or {})
         per_agent = all(a in net_config for a in self.agent_ids) if net_config else False
@@ -188,8 +206,9 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
         """_architecture_mutate_multi (hpo/mutation.py:887-1011): a method
         sampled from the actors' table with ``rng`` (Mutations.rng), applied to
         the sampled agent's actor; the method it applied (with its mutation
-        dict) to every other actor that has it; then, per critic and once per
-        mutated agent (the reference's repeat guard), the analogous method.
+        dict) to every other actor that has it; then, per critic of every
+        non-policy group in registration order and once per mutated agent
+        (the reference's repeat guard), the analogous method.
         The targets are re-made from the mutated networks
         (reinit_shared_networks, :104-160).  -> the mutation label (the
         applied method without its agent id) or None."""
@@ -213,21 +232,22 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
                 if done is not None:
                     mutated.append(a)
         self.critic_mutations = []
+        for g in self._groups[1:]:
+            for a in self.agent_ids:
+                critic = getattr(self, g.net)[a]
+                analogous, last = False, None
+                for m_agent in mutated:
+                    if analogous and last == analogous:
+                        continue
+                    analogous = self._find_analogous_mutation(sampled, critic.mutation_methods, m_agent)
+                    if analogous is None:
+                        raise RuntimeError(f"{self.algo} architecture mutation: no analogous method for {sampled!r} "
+                                           f"in {g.net}[{a!r}] ({critic.mutation_methods})")
+                    last, _ = critic.apply_mutation_dict(analogous, mut_dict)
+                    self.critic_mutations.append((a, analogous, str(last)))
         for a in self.agent_ids:
-            critic = self.critics[a]
-            analogous, last = False, None
-            for m_agent in mutated:
-                if analogous and last == analogous:
-                    continue
-                analogous = self._find_analogous_mutation(sampled, critic.mutation_methods, m_agent)
-                if analogous is None:
-                    raise RuntimeError(f"MADDPG architecture mutation: no analogous method for {sampled!r} in "
-                                       f"critic {a!r} ({critic.mutation_methods})")
-                last, _ = critic.apply_mutation_dict(analogous, mut_dict)
-                self.critic_mutations.append((a, analogous, str(last)))
-        for a in self.agent_ids:
-            self.actor_targets[a] = copy.deepcopy(self.actors[a])
-            self.critic_targets[a] = copy.deepcopy(self.critics[a])
+            for net, target, _ in self._triples():
+                getattr(self, target)[a] = copy.deepcopy(getattr(self, net)[a])
         return sampled
 
     # ---- acting (maddpg.py:456-625) ---------------------------------------
@@ -278,8 +298,11 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
             raw[a] = act.numpy()
         return processed, raw
 
-    # ---- learning (maddpg.py:629-838) ---------------------------------------
-    def learn(self, experiences) -> dict[str, tuple[float, float]]:
+    # ---- learning: what maddpg.py:629-668 and matd3.py:713-743 share ------------
+    def _batch(self, experiences) -> tuple:
+        """The sampled batch on the device and the target actors' forwards,
+        run once: (stacked actions, stacked next actions, states, next
+        states, actions, rewards, dones), the stacks in agent order."""
         states, actions, rewards, next_states, dones = experiences
         dev = self.device
         actions = {a: t.to(dev) for a, t in actions.items()}
@@ -291,34 +314,7 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
             next_actions = [self.actor_targets[a](next_states[a]) for a in self.agent_ids]
         stacked_actions = torch.cat([actions[a] for a in self.agent_ids], dim=1)
         stacked_next_actions = torch.cat(next_actions, dim=1)
-        losses = {a: self._learn_individual(a, stacked_actions, stacked_next_actions, states, next_states, actions,
-                                            rewards, dones) for a in self.agent_ids}
-        for a in self.agent_ids:
-            self.soft_update(self.actors[a], self.actor_targets[a])
-            self.soft_update(self.critics[a], self.critic_targets[a])
-        return losses
-
-    def _learn_individual(self, agent_id, stacked_actions, stacked_next_actions, states, next_states, actions,
-                          rewards, dones) -> tuple[float, float]:
-        actor, critic = self.actors[agent_id], self.critics[agent_id]
-        q_value = critic(states, stacked_actions)
-        with torch.no_grad():
-            q_next = self.critic_targets[agent_id](next_states, stacked_next_actions)
-        # NaN handling, y_j and MSE fused in agx_maddpg_critic_target (maddpg.py:764-781)
-        critic_loss = MSECriticLoss.apply(q_value, None, q_next, None, rewards[agent_id].float().reshape(-1),
-                                          dones[agent_id].float().reshape(-1), float(self.gamma), True)
-        opt_c = self.critic_optimizers[agent_id]
-        opt_c.zero_grad()
-        critic_loss.backward()
-        opt_c.step()
-        action = actor(states[agent_id])
-        detached = {a: (action if a == agent_id else actions[a]) for a in self.agent_ids}
-        actor_loss = -critic(states, torch.cat([detached[a] for a in self.agent_ids], dim=1)).mean()
-        opt_a = self.actor_optimizers[agent_id]
-        opt_a.zero_grad()
-        actor_loss.backward()
-        opt_a.step()
-        return actor_loss.item(), critic_loss.item()
+        return stacked_actions, stacked_next_actions, states, next_states, actions, rewards, dones
 
     @torch.no_grad()
     def soft_update(self, net: torch.nn.Module, target: torch.nn.Module) -> None:
@@ -367,3 +363,51 @@ class MADDPG(EvolvableAgentMixin, C.TorchCheckpointMixin):
     # ---- checkpoints (core/base.py:939-1072 layout, see checkpoint.py) --------
     def _ckpt_extra(self, ck: dict) -> None:
         ck["lr_actor"], ck["lr_critic"], ck["agent_ids"] = self.lr_actor, self.lr_critic, self.agent_ids
+
+
+class MADDPG(_MultiAgentPolicyGradient):
+    algo = "MADDPG"
+    # maddpg.py:424-444
+    _groups = (_ACTORS, NetGroup("critics", "critic_targets", "critic_optimizers", "lr_critic"))
+
+    def __init__(self, observation_spaces, action_spaces, agent_ids: list[str] | None = None,
+                 O_U_noise: bool = True, expl_noise: float = 0.1, vect_noise_dim: int = 1, mean_noise: float = 0.0,
+                 theta: float = 0.15, dt: float = 1e-2, index: int = 0, hp_config=None,
+                 net_config: dict[str, Any] | None = None, batch_size: int = 64, lr_actor: float = 0.001,
+                 lr_critic: float = 0.01, learn_step: int = 5, gamma: float = 0.95, tau: float = 0.01, mut=None,
+                 normalize_images: bool = True, actor_networks=None, critic_networks=None, device="cuda",
+                 accelerator=None, torch_compiler=None, wrap: bool = True) -> None:
+        self._setup(observation_spaces, action_spaces, agent_ids, O_U_noise, expl_noise, vect_noise_dim, mean_noise,
+                    theta, dt, index, hp_config, net_config, batch_size, lr_actor, lr_critic, learn_step, gamma, tau,
+                    mut, (actor_networks, critic_networks), device)
+
+    # ---- learning (maddpg.py:629-838) ---------------------------------------
+    def learn(self, experiences) -> dict[str, tuple[float, float]]:
+        batch = self._batch(experiences)
+        losses = {a: self._learn_individual(a, *batch) for a in self.agent_ids}
+        for a in self.agent_ids:
+            self.soft_update(self.actors[a], self.actor_targets[a])
+            self.soft_update(self.critics[a], self.critic_targets[a])
+        return losses
+
+    def _learn_individual(self, agent_id, stacked_actions, stacked_next_actions, states, next_states, actions,
+                          rewards, dones) -> tuple[float, float]:
+        actor, critic = self.actors[agent_id], self.critics[agent_id]
+        q_value = critic(states, stacked_actions)
+        with torch.no_grad():
+            q_next = self.critic_targets[agent_id](next_states, stacked_next_actions)
+        # NaN handling, y_j and MSE fused in agx_maddpg_critic_target (maddpg.py:764-781)
+        critic_loss = MSECriticLoss.apply(q_value, None, q_next, None, rewards[agent_id].float().reshape(-1),
+                                          dones[agent_id].float().reshape(-1), float(self.gamma), True)
+        opt_c = self.critic_optimizers[agent_id]
+        opt_c.zero_grad()
+        critic_loss.backward()
+        opt_c.step()
+        action = actor(states[agent_id])
+        detached = {a: (action if a == agent_id else actions[a]) for a in self.agent_ids}
+        actor_loss = -critic(states, torch.cat([detached[a] for a in self.agent_ids], dim=1)).mean()
+        opt_a = self.actor_optimizers[agent_id]
+        opt_a.zero_grad()
+        actor_loss.backward()
+        opt_a.step()
+        return actor_loss.item(), critic_loss.item()

@@ -1,5 +1,5 @@
 """What the object-level off-policy agents (DQN, RainbowDQN, DDPG, TD3,
-MADDPG) share besides the network groups of evolvable.py: unpacking a
+MADDPG, MATD3) share besides the network groups of evolvable.py: unpacking a
 sampled batch, the fused critic loss, and the evaluation loop."""
 
 from __future__ import annotations
@@ -21,12 +21,16 @@ def batch(agent, experiences, *keys) -> list[torch.Tensor]:
 class MSECriticLoss(torch.autograd.Function):
     """MSE(Q1, y) [+ MSE(Q2, y)] with y = r + (1 - d) gamma min(Q1', Q2'):
     one launch computes y, the loss and dLoss/dQk.  ``sanitize``: MADDPG's
-    form (one critic; NaN rewards -> 0, NaN dones -> 1, dones as uint8)."""
+    rules for r and d (NaN rewards -> 0, NaN dones -> 1, dones as uint8),
+    with one critic (MADDPG) or two (MATD3)."""
 
     @staticmethod
     def forward(ctx, q1, q2, qn1, qn2, rewards, dones, gamma, sanitize):
         r, d, twin = rewards.contiguous(), dones.contiguous(), q2 is not None
-        if sanitize:
+        if sanitize and twin:
+            _, g1, g2, loss = K.matd3_critic_target(q1.contiguous(), q2.contiguous(), qn1.contiguous(),
+                                                    qn2.contiguous(), r, d, gamma)
+        elif sanitize:
             _, g1, loss = K.maddpg_critic_target(q1.contiguous(), qn1.contiguous(), r, d, gamma)
         else:
             _, g1, g2, loss = K.td3_critic_target(q1.contiguous(), qn1.contiguous(), r, d, gamma,

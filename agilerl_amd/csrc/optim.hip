@@ -246,6 +246,26 @@ __global__ void polyak_kernel(float *__restrict__ t, const float *__restrict__ o
         t[i] = tau * o[i] + (1.0f - tau) * t[i];
 }
 
+// polyak_kernel over up to kMaxPolyak independent (target, online, n)
+// segments, the table in the kernel arguments: blockIdx.y = segment,
+// grid-stride over its elements with polyak_kernel's expression.  Scalar
+// f32 accesses: a segment's base is 4-byte aligned only (the target row of a
+// [2, n] pair buffer starts at element n).
+constexpr int kMaxPolyak = AGX_POLYAK_MAX_SEGMENTS;
+struct PolyakSet {
+    agx_polyak_segment s[kMaxPolyak];
+};
+
+__global__ __launch_bounds__(256) void polyak_segments_kernel(PolyakSet set, float tau) {
+    const agx_polyak_segment &S = set.s[blockIdx.y];
+    float *__restrict__ t = S.target;
+    const float *__restrict__ o = S.online;
+    const int64_t n = S.n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        t[i] = tau * o[i] + (1.0f - tau) * t[i];
+}
+
 // NoisyLinear.reset_noise over up to kMaxNoisy layers (custom_components.py:
 // 116-131): from the layer's two N(0,1) draws, f(x) = sign(x) * sqrt(|x|)
 // (torch's sign: (0 < x) - (x < 0); correctly rounded sqrt, as torch's),
@@ -357,4 +377,23 @@ extern "C" int agx_polyak(float *target, const float *online, int64_t n, float t
     const int64_t blocks = ceil_div(n, 256);
     polyak_kernel<<<(unsigned)(blocks > 4096 ? 4096 : blocks), 256, 0, as_stream(stream)>>>(target, online, n, tau);
     return check_launch("agx_polyak");
+}
+
+extern "C" int agx_polyak_segments(const agx_polyak_segment *segments, int n_segments, float tau, void *stream) {
+    AGX_REQUIRE(n_segments >= 0 && n_segments <= kMaxPolyak && (segments || n_segments == 0),
+                "agx_polyak_segments: bad segment list (n=%d, max %d)", n_segments, kMaxPolyak);
+    PolyakSet set = {};
+    int64_t most = 0;
+    for (int k = 0; k < n_segments; ++k) {
+        const agx_polyak_segment &S = segments[k];
+        AGX_REQUIRE(S.n >= 0 && (S.n == 0 || (S.target && S.online)),
+                    "agx_polyak_segments: segment %d: null pointer or negative length", k);
+        set.s[k] = S;
+        most = S.n > most ? S.n : most;
+    }
+    if (most == 0) return AGX_OK;  // nothing to update (an empty tensor's data pointer is null)
+    const int64_t blocks = ceil_div(most, 256);
+    polyak_segments_kernel<<<dim3((unsigned)(blocks > 4096 ? 4096 : blocks), (unsigned)n_segments), 256, 0,
+                             as_stream(stream)>>>(set, tau);
+    return check_launch("agx_polyak_segments");
 }

@@ -11,7 +11,8 @@
 //   y    = r + ((1 - d) * gamma) * min(Q1'(s', a'), Q2'(s', a'))
 //   loss = MSE(Q1, y) + MSE(Q2, y);  dloss/dQk = 2 (Qk - y) / B
 // MADDPG first sets NaN rewards to 0 and NaN dones to 1, casts the dones to
-// uint8 (truncation) and forms 1 - d in uint8 arithmetic.
+// uint8 (truncation) and forms 1 - d in uint8 arithmetic; MATD3
+// (matd3.py:861-880) does the same in front of the twin form.
 // Smoothing — td3.py:493-501, ddpg.py:448-456:
 //   noise = clamp(N(0, policy_noise), -c, c)             (torch.clamp)
 //   a'    = max(min(mu'(s') + noise, high), low)         (multi_dim_clamp)
@@ -267,4 +268,15 @@ extern "C" int agx_td3_critic_target(const float *q1, const float *q2, const flo
     auto launch = q2 ? critic_target<true, false> : critic_target<false, false>;
     return launch("agx_td3_critic_target", "agx_td3_critic_target loss", q1, q2, q_next1, q_next2, rewards, dones, B,
                   gamma, y, g_q1, g_q2, loss, workspace, stream);
+}
+
+extern "C" int agx_matd3_critic_target(const float *q1, const float *q2, const float *q_next1, const float *q_next2,
+                                       const float *rewards, const float *dones, int64_t B, double gamma, float *y,
+                                       float *g_q1, float *g_q2, float *loss, void *workspace, void *stream) {
+    AGX_REQUIRE(q1 && q2 && q_next1 && q_next2 && rewards && dones && loss && workspace && B >= 0,
+                "agx_matd3_critic_target: bad arguments");
+    AGX_REQUIRE(B <= (int64_t)0x7fffffff * kTdBlock, "agx_matd3_critic_target: B exceeds the grid");
+    if (B == 0) return AGX_OK;
+    return critic_target<true, true>("agx_matd3_critic_target", "agx_matd3_critic_target loss", q1, q2, q_next1,
+                                     q_next2, rewards, dones, B, gamma, y, g_q1, g_q2, loss, workspace, stream);
 }

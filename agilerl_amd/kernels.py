@@ -360,27 +360,29 @@ def td_target(q_next_target, rewards, dones, gamma, q_next_online=None, double=F
 
 
 def _critic_target(maddpg, q1, qn1, rewards, dones, gamma, q2=None, qn2=None):
-    """Shape checks, outputs and the launch of agx_maddpg_critic_target or
+    """Shape checks, outputs and the launch of agx_maddpg_critic_target
+    (``maddpg``, one critic), agx_matd3_critic_target (``maddpg``, two) or
     agx_td3_critic_target -> (y, dloss/dq1, dloss/dq2 | None, loss)."""
     B = q1.shape[0]
     f1, fn1, r, d = q1.reshape(-1), qn1.reshape(-1), rewards.reshape(-1), dones.reshape(-1)
     f2, fn2 = (q2.reshape(-1), qn2.reshape(-1)) if q2 is not None else (None, None)
-    named = [(f1, "q" if maddpg else "q1"), (fn1, "q_next" if maddpg else "qn1"), (r, "rewards"), (d, "dones")]
+    one = maddpg and q2 is None
+    named = [(f1, "q" if one else "q1"), (fn1, "q_next" if one else "qn1"), (r, "rewards"), (d, "dones")]
     for t, name in named + ([(f2, "q2"), (fn2, "qn2")] if q2 is not None else []):
         _need(t, name, _f32, (B,))
     dev = r.device
     y, g1 = torch.empty(B, 1, dtype=_f32, device=dev), torch.empty(B, 1, dtype=_f32, device=dev)
     g2 = torch.empty(B, 1, dtype=_f32, device=dev) if q2 is not None else None
     loss = torch.empty(1, dtype=_f32, device=dev)
-    if maddpg:
+    if one:
         ws = _ws(_lib.load().agx_td_workspace_bytes(B), dev)
         _lib.call("agx_maddpg_critic_target", f1.data_ptr(), fn1.data_ptr(), r.data_ptr(), d.data_ptr(), B,
                   float(gamma), y.data_ptr(), g1.data_ptr(), loss.data_ptr(), ws.data_ptr(), _lib.stream())
     else:
         ws = _ws(_lib.load().agx_td3_workspace_bytes(B), dev)
-        _lib.call("agx_td3_critic_target", f1.data_ptr(), _lib.ptr(f2), fn1.data_ptr(), _lib.ptr(fn2), r.data_ptr(),
-                  d.data_ptr(), B, float(gamma), y.data_ptr(), g1.data_ptr(), _lib.ptr(g2), loss.data_ptr(),
-                  ws.data_ptr(), _lib.stream())
+        _lib.call("agx_matd3_critic_target" if maddpg else "agx_td3_critic_target", f1.data_ptr(), _lib.ptr(f2),
+                  fn1.data_ptr(), _lib.ptr(fn2), r.data_ptr(), d.data_ptr(), B, float(gamma), y.data_ptr(),
+                  g1.data_ptr(), _lib.ptr(g2), loss.data_ptr(), ws.data_ptr(), _lib.stream())
     return y, g1, g2, loss
 
 
@@ -389,6 +391,14 @@ def maddpg_critic_target(q, q_next, rewards, dones, gamma):
     critic step (maddpg.py:764-790) in one launch (+ the fixed-order loss sum)."""
     y, g_q, _, loss = _critic_target(True, q, q_next, rewards, dones, gamma)
     return y, g_q, loss
+
+
+def matd3_critic_target(q1, q2, qn1, qn2, rewards, dones, gamma):
+    """-> (y (B,1), dloss/dq1 (B,1), dloss/dq2 (B,1), loss (1,)) of
+    MATD3.learn_individual's critic step (matd3.py:861-880): MADDPG's NaN and
+    uint8 rules for r and d, y from the smaller target critic, the sum of the
+    two MSE losses, in one launch (+ the fixed-order loss sums)."""
+    return _critic_target(True, q1, qn1, rewards, dones, gamma, q2, qn2)
 
 
 def td3_smooth_actions(mu, noise, low, high, noise_clip, out=None):
@@ -524,3 +534,27 @@ def polyak_(target: torch.Tensor, online: torch.Tensor, tau: float) -> None:
     _need(online, "online", _f32, tuple(target.shape))
     _lib.call("agx_polyak", target.data_ptr(), online.data_ptr(), target.numel(), float(tau),
               _lib.stream())
+
+
+class _PolyakSegment(ctypes.Structure):
+    _fields_ = [("target", ctypes.c_void_p), ("online", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
+POLYAK_MAX_SEGMENTS = 64  # AGX_POLYAK_MAX_SEGMENTS (include/agx.h)
+
+
+def polyak_segments_(targets, onlines, tau: float) -> None:
+    """agx_polyak_segments: target <- tau * online + (1 - tau) * target for
+    every (target, online) pair of contiguous f32 tensors, one launch per 64
+    pairs.  The pairs must not overlap one another."""
+    if len(targets) != len(onlines):
+        raise ValueError(f"polyak_segments_: {len(targets)} targets for {len(onlines)} online tensors")
+    for t, o in zip(targets, onlines):
+        _need(t, "target", _f32)
+        _need(o, "online", _f32, tuple(t.shape))
+    for k in range(0, len(targets), POLYAK_MAX_SEGMENTS):
+        chunk = list(zip(targets[k:k + POLYAK_MAX_SEGMENTS], onlines[k:k + POLYAK_MAX_SEGMENTS]))
+        arr = (_PolyakSegment * len(chunk))()
+        for j, (t, o) in enumerate(chunk):
+            arr[j] = _PolyakSegment(t.data_ptr(), o.data_ptr(), t.numel())
+        _lib.call("agx_polyak_segments", ctypes.cast(arr, ctypes.c_void_p), len(chunk), float(tau), _lib.stream())

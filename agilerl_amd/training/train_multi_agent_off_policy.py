@@ -1,6 +1,6 @@
 """Drop-in ``train_multi_agent_off_policy``
-(agilerl/training/train_multi_agent_off_policy.py:33-560) for MADDPG
-populations on the HBM ``MultiAgentReplayBuffer``.
+(agilerl/training/train_multi_agent_off_policy.py:33-560) for MADDPG and
+MATD3 populations on the HBM ``MultiAgentReplayBuffer``.
 
 Per generation each agent in turn: ``evo_steps // num_envs`` vector steps of
 ``get_action`` (raw actor outputs saved), ``save_to_memory`` into the shared

@@ -10,7 +10,7 @@ Sharding.  Under an initialised torch.distributed group of G > 1 ranks
 GLOBAL population and each rank gets its slice: rank r holds global agents
 r*P .. r*P + P - 1 with P = population_size / G (their global indices, init
 seeds and sampling streams), so the same script trains the same population
-on 1 or G GPUs.  Object-level agents (DQN / Rainbow / MADDPG) are built for
+on 1 or G GPUs.  Object-level agents (DQN / Rainbow / MADDPG / MATD3) are built for
 the whole population in order and the slice is kept, which leaves the
 torch generators where the unsharded build leaves them.  ``shard=False``
 keeps ``population_size`` agents per rank.  DDPG / TD3 populations
@@ -79,17 +79,20 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         for a in agents:
             a.sharded = bool(shard and world > 1)
         return agents[lo:lo + P]
-    if algo == "MADDPG":  # utils/utils.py:590-618
-        from ..algorithms.maddpg import MADDPG
+    if algo in ("MADDPG", "MATD3"):  # utils/utils.py:590-618, 620-649
+        from ..algorithms import MADDPG, MATD3
 
+        cls = MADDPG if algo == "MADDPG" else MATD3
         hp = dict(batch_size=INIT_HP.get("BATCH_SIZE", 64), lr_actor=INIT_HP.get("LR_ACTOR", 0.0001),
                   lr_critic=INIT_HP.get("LR_CRITIC", 0.001), learn_step=INIT_HP.get("LEARN_STEP", 5),
                   gamma=INIT_HP.get("GAMMA", 0.95), tau=INIT_HP.get("TAU", 0.01),
                   O_U_noise=INIT_HP.get("O_U_NOISE", True), expl_noise=INIT_HP.get("EXPL_NOISE", 0.1),
                   vect_noise_dim=num_envs, mean_noise=INIT_HP.get("MEAN_NOISE", 0.0),
                   theta=INIT_HP.get("THETA", 0.15), dt=INIT_HP.get("DT", 0.01))
-        agents = [MADDPG(observation_space, action_space, agent_ids=INIT_HP["AGENT_IDS"], index=i,
-                         net_config=net_config, device=device, hp_config=hp_config, **hp, **algo_kwargs)
+        if algo == "MATD3":
+            hp["policy_freq"] = INIT_HP.get("POLICY_FREQ", 2)
+        agents = [cls(observation_space, action_space, agent_ids=INIT_HP["AGENT_IDS"], index=i,
+                      net_config=net_config, device=device, hp_config=hp_config, **hp, **algo_kwargs)
                   for i in range(population_size if shard else P)]
         for a in agents:
             a.sharded = bool(shard and world > 1)
@@ -106,7 +109,7 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         return [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, num_envs=num_envs,
                                  device=device, hp_config=hp_config, **algo_kwargs) for i in range(P)]
     raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, MADDPG, "
-                              "DDPG, TD3)")
+                              "MATD3, DDPG, TD3)")
 
 
 __all__ = ["create_population"]

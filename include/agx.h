@@ -465,6 +465,22 @@ int agx_clip_adam(float *params, float *grads, float *exp_avg, float *exp_avg_sq
 /* Polyak soft update target <- tau*online + (1-tau)*target
  * (dqn.py:349-358, dqn_rainbow.py:492-501). */
 int agx_polyak(float *target, const float *online, int64_t n, float tau, void *stream);
+/* A whole soft update in one launch: agx_polyak's update, bit for bit, over
+ * up to AGX_POLYAK_MAX_SEGMENTS independent segments (one per network of a
+ * multi-agent learner: matd3.py:770-782 walks 3 N networks tensor by tensor).
+ * segments: host array, copied into the kernel arguments; target and online
+ * need f32 (4-byte) alignment only.  A segment with n == 0 is skipped (its
+ * pointers may be NULL); a NULL pointer with n > 0, a negative n or more than
+ * AGX_POLYAK_MAX_SEGMENTS segments is an error and nothing is launched.
+ * The segments' target ranges must not overlap one another or any online
+ * range: segments are updated concurrently, in no order. */
+#define AGX_POLYAK_MAX_SEGMENTS 64
+typedef struct agx_polyak_segment {
+    float *target;
+    const float *online;
+    int64_t n;
+} agx_polyak_segment;
+int agx_polyak_segments(const agx_polyak_segment *segments, int n_segments, float tau, void *stream);
 /* NoisyLinear.reset_noise (agilerl/modules/custom_components.py:116-131) for
  * up to 16 noisy layers of a network in one launch.  eps_in [in_features] and
  * eps_out [out_features] are the layer's two torch.randn draws (the caller

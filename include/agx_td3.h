@@ -47,6 +47,19 @@ int agx_td3_critic_target(const float *q1, const float *q2, const float *q_next1
                           const float *rewards, const float *dones, int64_t B, double gamma, float *y, float *g_q1,
                           float *g_q2, float *loss, void *workspace, void *stream);
 
+/* MATD3's critic step: the twin form above behind MADDPG's input rules.
+ * Replaces agilerl/algorithms/matd3.py:861-880 (MATD3.learn_individual):
+ * NaN rewards -> 0, NaN dones -> 1, dones cast to uint8 and 1 - d formed in
+ * uint8 arithmetic (a done of 2 gives 255), then
+ *   y    = r + ((1 - d) * (float)gamma) * min(q_next1, q_next2)   (torch.min: a NaN wins)
+ *   loss = f32(mean((q1 - y)^2)) + f32(mean((q2 - y)^2))
+ *   g_qk = (qk - y) * (2 / B)
+ * Shapes as for agx_td3_critic_target; q2 and q_next2 are required; y, g_q1,
+ * g_q2 may each be NULL; workspace: agx_td3_workspace_bytes(B). */
+int agx_matd3_critic_target(const float *q1, const float *q2, const float *q_next1, const float *q_next2,
+                            const float *rewards, const float *dones, int64_t B, double gamma, float *y, float *g_q1,
+                            float *g_q2, float *loss, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
