@@ -30,7 +30,7 @@ class AgxMultiHead(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
-# agx_bernoulli.h) one-to-one
+# agx_bernoulli.h, agx_cqn.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -141,6 +141,9 @@ SIGNATURES = {
     "agx_td3_workspace_bytes": (_SZ, [_I]),
     "agx_td3_critic_target": (_INT, [_P] * 6 + [_I, _D] + [_P] * 6),
     "agx_matd3_critic_target": (_INT, [_P] * 6 + [_I, _D] + [_P] * 6),
+    # include/agx_cqn.h: the conservative Q-learning loss
+    "agx_cqn_workspace_bytes": (_SZ, [_I, _I]),
+    "agx_cqn_loss": (_INT, [_P] * 6 + [_I, _I, _D, _INT] + [_P] * 6),
     "agx_c51_project_loss": (_INT, [_P] * 7 + [_I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_c51_project_loss_rows": (_INT, [_P] * 5 + [_I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_adam_workspace_bytes": (_SZ, [_I, _I]),

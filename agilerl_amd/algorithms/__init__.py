@@ -1,5 +1,6 @@
 """Drop-in algorithm classes (agilerl.algorithms) on the agx hot path."""
 
+from .cqn import CQN
 from .ddpg import DDPG
 from .dqn import DQN, RainbowDQN
 from .maddpg import MADDPG
@@ -7,4 +8,4 @@ from .matd3 import MATD3
 from .ppo import PPO
 from .td3 import TD3
 
-__all__ = ["PPO", "DQN", "RainbowDQN", "MADDPG", "MATD3", "DDPG", "TD3"]
+__all__ = ["PPO", "DQN", "RainbowDQN", "MADDPG", "MATD3", "DDPG", "TD3", "CQN"]

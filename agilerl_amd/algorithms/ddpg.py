@@ -58,6 +58,20 @@ def _set_arch(net, arch: dict) -> None:
     net.recreate_network(old)
 
 
+def save_arch(agent, ck: dict) -> None:
+    """Into a checkpoint being saved: the architecture of every network of the
+    agent's groups (MLP encoders), so a mutated agent loads into a fresh one."""
+    ck["network_arch"] = {n: _arch(getattr(agent, n)) for g in agent._groups for n in g[:2]}
+
+
+def restore_arch(agent, ck: dict) -> None:
+    """Take it back, before the state dicts are loaded: networks rebuilt where
+    they differ, then fresh optimizers over the (possibly rebuilt) parameters."""
+    for n, arch in ck.get("network_arch", {}).items():
+        _set_arch(getattr(agent, n), arch)
+    agent.reinit_optimizers()
+
+
 _ACTOR = NetGroup("actor", "actor_target", "actor_optimizer", "lr_actor")
 
 
@@ -304,12 +318,10 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin, C.TorchCheckpointMixin):
             ck[k] = C._plain(getattr(self, k))
         for k in self._CKPT_ARRAYS:
             ck[k] = torch.from_numpy(np.array(getattr(self, k), dtype=np.float64))
-        ck["network_arch"] = {n: _arch(getattr(self, n)) for g in self._groups for n in g[:2]}
+        save_arch(self, ck)
 
     def _ckpt_restore(self, ck: dict) -> None:
-        for n, arch in ck.get("network_arch", {}).items():
-            _set_arch(getattr(self, n), arch)
-        self.reinit_optimizers()  # over the (possibly rebuilt) parameters
+        restore_arch(self, ck)
         for k in self._CKPT_EXTRA:
             if k in ck:
                 setattr(self, k, ck[k])

@@ -79,15 +79,14 @@ class _TDLoss(torch.autograd.Function):
         return (g_q * gl,) + (None,) * 7
 
 
-class DQN(EvolvableAgentMixin, C.TorchCheckpointMixin):
-    algo = "DQN"
+class _EpsilonGreedyQAgent(EvolvableAgentMixin, C.TorchCheckpointMixin):
+    """What DQN and CQN (cqn.py) share: the QNetwork pair with its Adam
+    optimizer, epsilon-greedy ``get_action`` and ``test``."""
 
-    def __init__(self, observation_space, action_space, index: int = 0, hp_config=None, net_config=None,
-                 batch_size: int = 64, lr: float = 1e-4, learn_step: int = 5, gamma: float = 0.99,
-                 tau: float = 1e-3, mut=None, normalize_images: bool = True, double: bool = False,
-                 actor_network=None, device="cuda", accelerator=None, cudagraphs: bool = False, wrap: bool = True):
+    def _setup(self, observation_space, action_space, index, hp_config, net_config, batch_size, lr, learn_step,
+               gamma, tau, mut, normalize_images, double, actor_network, device) -> None:
         if not hasattr(action_space, "n"):
-            raise NotImplementedError("agx DQN supports Discrete action spaces")
+            raise NotImplementedError(f"agx {self.algo} supports Discrete action spaces")
         if actor_network is not None:
             raise NotImplementedError("custom actor modules: use net_config (MLP) networks")
         assert isinstance(batch_size, int) and batch_size >= 1, "Batch size must be an integer greater than or equal to one."
@@ -138,6 +137,21 @@ class DQN(EvolvableAgentMixin, C.TorchCheckpointMixin):
             greedy = torch.where(rand, random_a, greedy)
         return greedy.cpu().numpy()
 
+    @torch.no_grad()
+    def test(self, env, swap_channels: bool = False, max_steps: int | None = None, loop: int = 3) -> float:
+        return _evaluate(self, env, lambda o: self.get_action(o, epsilon=0.0), max_steps, loop)
+
+
+class DQN(_EpsilonGreedyQAgent):
+    algo = "DQN"
+
+    def __init__(self, observation_space, action_space, index: int = 0, hp_config=None, net_config=None,
+                 batch_size: int = 64, lr: float = 1e-4, learn_step: int = 5, gamma: float = 0.99,
+                 tau: float = 1e-3, mut=None, normalize_images: bool = True, double: bool = False,
+                 actor_network=None, device="cuda", accelerator=None, cudagraphs: bool = False, wrap: bool = True):
+        self._setup(observation_space, action_space, index, hp_config, net_config, batch_size, lr, learn_step, gamma,
+                    tau, mut, normalize_images, double, actor_network, device)
+
     def update(self, obs, actions, rewards, next_obs, dones) -> torch.Tensor:
         with torch.no_grad():
             q_next_target = self.actor_target(next_obs)
@@ -156,10 +170,6 @@ class DQN(EvolvableAgentMixin, C.TorchCheckpointMixin):
         loss = self.update(*batch(self, experiences, "obs", "action", "reward", "next_obs", "done"))
         self.soft_update()
         return float(loss.item())
-
-    @torch.no_grad()
-    def test(self, env, swap_channels: bool = False, max_steps: int | None = None, loop: int = 3) -> float:
-        return _evaluate(self, env, lambda o: self.get_action(o, epsilon=0.0), max_steps, loop)
 
 
 class _C51Loss(torch.autograd.Function):

@@ -19,35 +19,11 @@
 // f32 throughout, one rounding per op (the reference's op order); every mean
 // is accumulated in f64 over fixed-order block partials and rounded to f32,
 // and TD3's two are added in f32, as the sum of two nn.MSELoss values.
-#include "agx_common.h"
+#include "td_rules.h"
 
 #include "../../include/agx_td3.h"
 
 namespace agx {
-
-constexpr int kTdBlock = 256;
-
-// The tail of every kernel here: s1 (and s2) summed over the block in f64, an
-// xor butterfly per wave, then the waves in ascending order by thread 0.
-// True in thread 0, whose s1 / s2 then hold the sums.
-template <int THREADS, bool TWO>
-__device__ __forceinline__ bool block_sum(double &s1, double &s2) {
-    __shared__ double red[TWO ? 2 : 1][THREADS / kWave];
-    s1 = wave_sum(s1);
-    if (TWO) s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x / 64] = s1;
-        if (TWO) red[1][threadIdx.x / 64] = s2;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return false;
-    s1 = s2 = 0.0;
-    for (int w = 0; w < THREADS / kWave; ++w) {
-        s1 += red[0][w];
-        if (TWO) s2 += red[1][w];
-    }
-    return true;
-}
 
 // the block's squared errors into part1 / part2 [blockIdx], for loss_finalize
 template <bool TWO>
@@ -75,18 +51,6 @@ __global__ __launch_bounds__(1024) void loss_finalize(const double *__restrict__
     }
 }
 
-// torch.min / torch.max (and clamp) propagate NaN; fminf / fmaxf do not
-__device__ __forceinline__ float nan_min(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return fminf(a, b);
-}
-__device__ __forceinline__ float nan_max(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return fmaxf(a, b);
-}
-
 // one row per lane.  A NaN among the next-state values is the row's maximum,
 // as for torch.max / torch.argmax (argmax: the first NaN's index)
 __global__ __launch_bounds__(kTdBlock) void td_target_kernel(
@@ -96,25 +60,8 @@ __global__ __launch_bounds__(kTdBlock) void td_target_kernel(
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double sq = 0.0;
     if (i < B) {
-        const float *tn = qnt + i * A;
-        float qt;
-        if (dbl) {
-            const float *on = qno + i * A;
-            int best = 0;
-            float bv = on[0];
-            for (int a = 1; a < A; ++a) {
-                const float v = on[a];
-                if (v > bv || (v != v && bv == bv)) {
-                    bv = v;
-                    best = a;
-                }
-            }
-            qt = tn[best];
-        } else {
-            qt = tn[0];
-            for (int a = 1; a < A; ++a) qt = nan_max(qt, tn[a]);
-        }
-        const float yi = r[i] + (g * qt) * (1.0f - d[i]);
+        const float qt = row_q_next(dbl ? qno + i * A : nullptr, qnt + i * A, A, dbl);
+        const float yi = td_y(r[i], g, qt, d[i]);
         y[i] = yi;
         if (qc) {
             const int64_t ai = act[i];

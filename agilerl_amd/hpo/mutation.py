@@ -29,7 +29,7 @@ What runs, with the reference's draws from the reference's generators:
   by the engine at the next generation (agents grouped by learn_step).
 
 * ``activation_mutation`` (:457-513, _permutate_activation :710-731) on DQN /
-  Rainbow agents: the new activation drawn with ``self.rng`` from
+  Rainbow / CQN agents: the new activation drawn with ``self.rng`` from
   ``activation_selection`` minus the current one, every evolvable module of
   the Q network recreated with it (the encoder's output activation too), the
   target network re-made from the mutated network (reinit_shared_networks,
@@ -41,7 +41,7 @@ What runs, with the reference's draws from the reference's generators:
   kernel methods; its LAYER methods disabled), bit-exact against the
   reference's own networks; the engine regroups them as the MLP agents.
 
-* ``architecture_mutate`` on DQN / Rainbow agents with MLP or CNN encoders:
+* ``architecture_mutate`` on DQN / Rainbow / CQN agents with MLP or CNN encoders:
   the method from the network's table (head layer / node, latent node, and
   the encoder's node methods: MLP nodes or CNN channels / kernels), applied
   to the Q network with the network's generator, the target network re-made

@@ -359,6 +359,41 @@ def td_target(q_next_target, rewards, dones, gamma, q_next_online=None, double=F
     return y, g_q, loss
 
 
+def cqn_loss(q_cur, q_next_target, actions, rewards, dones, gamma, q_next_online=None, double=False,
+             with_terms=False):
+    """-> (y (B,1), dloss/dq_cur (B,A), loss (1,)[, terms (3,)]) of CQN.learn's
+    loss (cqn.py:234-252): DQN's TD target and half its MSE plus
+    mean(logsumexp_a Q) - mean(Q), with the dense gradient, in one launch
+    (+ the fixed-order sums).  terms = (mean lse, mean Q, MSE).  y is
+    td_target's, bit for bit.  Precondition: 0 <= actions < A."""
+    _need(q_cur, "q_cur", _f32)
+    if q_cur.dim() != 2:
+        raise ValueError(f"q_cur: expected [B, A], got {tuple(q_cur.shape)}")
+    B, A = q_cur.shape
+    _need(q_next_target, "q_next_target", _f32, (B, A))
+    a, r, d = actions.reshape(-1), rewards.reshape(-1), dones.reshape(-1)
+    _need(a, "actions", _i64, (B,))
+    _need(r, "rewards", _f32, (B,))
+    _need(d, "dones", _f32, (B,))
+    if double:
+        _need(q_next_online, "q_next_online", _f32, (B, A))
+    dev = q_cur.device
+    y = torch.empty(B, 1, dtype=_f32, device=dev)
+    g_q = torch.empty(B, A, dtype=_f32, device=dev)
+    loss = torch.empty(1, dtype=_f32, device=dev)
+    terms = torch.empty(3, dtype=_f32, device=dev) if with_terms else None
+    if B == 0:  # no launch: the means of nothing, as torch's mean of an empty tensor
+        loss.fill_(float("nan"))
+        if terms is not None:
+            terms.fill_(float("nan"))
+        return (y, g_q, loss, terms) if with_terms else (y, g_q, loss)
+    ws = _ws(_lib.load().agx_cqn_workspace_bytes(B, A), dev)
+    _lib.call("agx_cqn_loss", _lib.ptr(q_next_online) if double else None, q_next_target.data_ptr(),
+              q_cur.data_ptr(), a.data_ptr(), r.data_ptr(), d.data_ptr(), B, A, float(gamma), int(bool(double)),
+              y.data_ptr(), g_q.data_ptr(), loss.data_ptr(), _lib.ptr(terms), ws.data_ptr(), _lib.stream())
+    return (y, g_q, loss, terms) if with_terms else (y, g_q, loss)
+
+
 def _critic_target(maddpg, q1, qn1, rewards, dones, gamma, q2=None, qn2=None):
     """Shape checks, outputs and the launch of agx_maddpg_critic_target
     (``maddpg``, one critic), agx_matd3_critic_target (``maddpg``, two) or

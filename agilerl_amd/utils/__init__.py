@@ -10,7 +10,7 @@ Sharding.  Under an initialised torch.distributed group of G > 1 ranks
 GLOBAL population and each rank gets its slice: rank r holds global agents
 r*P .. r*P + P - 1 with P = population_size / G (their global indices, init
 seeds and sampling streams), so the same script trains the same population
-on 1 or G GPUs.  Object-level agents (DQN / Rainbow / MADDPG / MATD3) are built for
+on 1 or G GPUs.  Object-level agents (DQN / Rainbow / CQN / MADDPG / MATD3) are built for
 the whole population in order and the slice is kept, which leaves the
 torch generators where the unsharded build leaves them.  ``shard=False``
 keeps ``population_size`` agents per rank.  DDPG / TD3 populations
@@ -69,10 +69,11 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         return [PPO(observation_space, action_space, index=lo + i, hp_config=hp_config, net_config=net_config,
                     num_envs=num_envs, device=device, _population=pop, _row=i, **hp, **algo_kwargs)
                 for i in range(P)]
-    if algo in ("DQN", "Rainbow DQN", "RainbowDQN"):
+    if algo in ("DQN", "Rainbow DQN", "RainbowDQN", "CQN"):  # CQN: utils/utils.py:539-558
+        from ..algorithms.cqn import CQN
         from ..algorithms.dqn import DQN, RainbowDQN
 
-        cls = DQN if algo == "DQN" else RainbowDQN
+        cls = {"DQN": DQN, "CQN": CQN}.get(algo, RainbowDQN)
         agents = [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, device=device,
                                    hp_config=hp_config, **algo_kwargs)
                   for i in range(population_size if shard else P)]
@@ -108,8 +109,8 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         cls = DDPG if algo == "DDPG" else TD3
         return [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, num_envs=num_envs,
                                  device=device, hp_config=hp_config, **algo_kwargs) for i in range(P)]
-    raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, MADDPG, "
-                              "MATD3, DDPG, TD3)")
+    raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, CQN, "
+                              "MADDPG, MATD3, DDPG, TD3)")
 
 
 __all__ = ["create_population"]
