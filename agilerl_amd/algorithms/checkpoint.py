@@ -122,7 +122,7 @@ def group_state_dicts(agent) -> tuple[dict, dict]:
     def sd(x):
         return {a: m.state_dict() for a, m in x.items()} if hasattr(x, "items") else x.state_dict()
 
-    return ({n: sd(getattr(agent, n)) for g in agent._groups for n in g[:2]},
+    return ({n: sd(getattr(agent, n)) for g in agent._groups for n in g[:2] if n},
             {g[2]: sd(getattr(agent, g[2])) for g in agent._groups})
 
 
@@ -138,7 +138,8 @@ def load_group_state_dicts(agent, info: dict) -> None:
 
     for g in agent._groups:
         for n in g[:2]:
-            load(getattr(agent, n), info["modules"].get(f"{n}_state_dict") or {}, True)
+            if n:  # a group without a target network names none
+                load(getattr(agent, n), info["modules"].get(f"{n}_state_dict") or {}, True)
         load(getattr(agent, g[2]), info["optimizers"][f"{g[2]}_state_dict"], False)
 
 

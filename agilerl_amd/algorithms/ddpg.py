@@ -61,7 +61,7 @@ def _set_arch(net, arch: dict) -> None:
 def save_arch(agent, ck: dict) -> None:
     """Into a checkpoint being saved: the architecture of every network of the
     agent's groups (MLP encoders), so a mutated agent loads into a fresh one."""
-    ck["network_arch"] = {n: _arch(getattr(agent, n)) for g in agent._groups for n in g[:2]}
+    ck["network_arch"] = {n: _arch(getattr(agent, n)) for g in agent._groups for n in g[:2] if n}
 
 
 def restore_arch(agent, ck: dict) -> None:

@@ -82,7 +82,8 @@ class EvolvableAgentMixin:
         from the mutated one (reinit_shared_networks, mutation.py:104-160)."""
         net = getattr(self, self._groups[0].net)
         applied = net.apply_mutation(net.sample_mutation_method(new_layer_prob, rng))
-        setattr(self, self._groups[0].target, copy.deepcopy(net))
+        if self._groups[0].target:  # the bandits have no target copy
+            setattr(self, self._groups[0].target, copy.deepcopy(net))
         return applied
 
     def reinit_optimizers(self, optimizer=None) -> None:
@@ -134,6 +135,8 @@ class EvolvableAgentMixin:
 
     @torch.no_grad()
     def sync_shared_networks(self) -> None:
+        if not self._groups[0].target:
+            return
         net, shared = (getattr(self, n) for n in self._groups[0][:2])
         if isinstance(net, torch.nn.ModuleDict):
             for k in net:

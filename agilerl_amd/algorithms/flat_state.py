@@ -40,14 +40,16 @@ def _plain_adam(opt) -> bool:
 
 
 class FlatLearnState:
-    """Flat online / target / gradient / Adam buffers of one agent."""
+    """Flat online / target / gradient / Adam buffers of one agent.
+    ``target`` None: a network without a target copy (the bandits): no target
+    row is allocated and ``polyak`` must not be called."""
 
     def __init__(self, actor, target, opt):
         self.actor, self.target, self.opt = actor, target, opt
         self.params = list(actor.parameters())
-        self.tparams = list(target.parameters())
-        if len(self.params) != len(self.tparams) or any(p.shape != q.shape for p, q in
-                                                        zip(self.params, self.tparams)):
+        self.tparams = list(target.parameters()) if target is not None else []
+        if target is not None and (len(self.params) != len(self.tparams) or
+                                   any(p.shape != q.shape for p, q in zip(self.params, self.tparams))):
             raise ValueError("flat learner state: online and target networks differ in shape")
         dev = self.params[0].device
         sizes = [p.numel() for p in self.params]
@@ -56,8 +58,8 @@ class FlatLearnState:
         # tensor's online and target copies sit n elements apart, so the
         # no-grad forwards on s' take both networks in one grouped launch
         # (pair_view, dqn.py)
-        self.pair = torch.empty(2, n, dtype=torch.float32, device=dev)
-        self.prm, self.tgt = self.pair[0], self.pair[1]
+        self.pair = torch.empty(2 if target is not None else 1, n, dtype=torch.float32, device=dev)
+        self.prm, self.tgt = self.pair[0], self.pair[1] if target is not None else None
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m = torch.zeros(n, dtype=torch.float32, device=dev)
         self.v = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -72,14 +74,15 @@ class FlatLearnState:
         self.steps = torch.full((1,), step, dtype=torch.int64, device=dev)
         off = 0
         with torch.no_grad():
-            for p, q, k, st_t in zip(self.params, self.tparams, sizes, self.step_ts):
+            for p, q, k, st_t in zip(self.params, self.tparams or self.params, sizes, self.step_ts):
                 shape = p.shape
                 v = self.prm[off:off + k].view(shape)
                 v.copy_(p.data)
                 p.data = v
-                tv = self.tgt[off:off + k].view(shape)
-                tv.copy_(q.data)
-                q.data = tv
+                if target is not None:
+                    tv = self.tgt[off:off + k].view(shape)
+                    tv.copy_(q.data)
+                    q.data = tv
                 st = opt.state.get(p) or {}
                 mv, vv = self.m[off:off + k].view(shape), self.v[off:off + k].view(shape)
                 if "exp_avg" in st:
@@ -93,7 +96,7 @@ class FlatLearnState:
             self.offs[id(p)] = (off, k)
             off += k
         self.ptrs = [p.data_ptr() for p in self.params]
-        self.tptrs = [q.data_ptr() for q in self.tparams]
+        self.tptrs = [q.data_ptr() for q in self.tparams] if target is not None else []
         self.mptrs = [opt.state[p]["exp_avg"].data_ptr() for p in self.params]
         self.lr = float(opt.param_groups[0]["lr"])
         self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
@@ -119,7 +122,7 @@ class FlatLearnState:
             st = state.get(p)
             if st is None or st.get("step") is not st_t or st["exp_avg"].data_ptr() != mptr:
                 return False
-        return all(q.data_ptr() == ptr for q, ptr in zip(target.parameters(), self.tptrs))
+        return target is None or all(q.data_ptr() == ptr for q, ptr in zip(target.parameters(), self.tptrs))
 
     def step(self, max_norm: float) -> bool:
         """Gather the gradients, clip (max_norm > 0) + Adam in one launch.
@@ -178,7 +181,7 @@ def flat_state(agent, group=None, key=None) -> FlatLearnState | None:
     the member: one flat state per (group, key), cached under that pair."""
     first = agent._groups[0]
     name = (group or first)[0]
-    actor, target, opt = (getattr(agent, n) for n in (group or first)[:3])
+    actor, target, opt = (getattr(agent, n) if n else None for n in (group or first)[:3])
     if key is not None:
         actor, target, opt = actor[key], target[key], opt[key]
     if agent.device.type != "cuda" or not _plain_adam(opt):

@@ -133,7 +133,8 @@ def run(fs, key: tuple, inputs: list, body, nets: tuple, max_norm: float, tau: f
     def device_work(xs):
         out = body(xs)
         fs.launch(max_norm)
-        fs.polyak(tau)
+        if fs.target is not None:  # a group without a target network (the bandits): no soft update
+            fs.polyak(tau)
         for n in nets:
             n.reset_noise()
         return out

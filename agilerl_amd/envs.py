@@ -459,3 +459,47 @@ class StackedVecEnv:
         for e in self.envs:
             if hasattr(e, "close"):
                 e.close()
+
+
+class SyntheticBanditEnv:
+    """A contextual bandit with ``BanditEnv``'s contract (wrappers/learning.py:
+    ``reset() -> context``, ``step(arm) -> (context, reward)``, context
+    ``[arms, arms * features]`` float32 with the drawn feature row in block k
+    of row k) and no dataset behind it: feature rows come from a seeded ring,
+    and the rewarded arm of a row x is ``argmax(W x)`` for a fixed seeded
+    ``W`` — a fixed function of the context, so it can be learned.  Its own
+    generator: nothing is drawn from the global ones."""
+
+    agx_device_free = True
+
+    def __init__(self, arms: int = 10, features: int = 8, seed: int = 0, ring: int = 509):
+        self.arms, self.features, self.seed = int(arms), int(features), int(seed)
+        self.context_dim = (self.arms * self.features,)
+        self.observation_space = Box(-np.inf, np.inf, self.context_dim)
+        self.action_space = Discrete(self.arms)
+        rng = np.random.default_rng(seed)
+        self._w = rng.standard_normal((self.arms, self.features))
+        self._rows = rng.standard_normal((ring, self.features)).astype(np.float32)
+        self._targets = np.argmax(self._rows.astype(np.float64) @ self._w.T, axis=1)
+        self._order = np.random.default_rng(seed + 1)
+        self.prev_reward = np.zeros(self.arms)
+
+    def _new_state_and_target_action(self):
+        r = int(self._order.integers(0, len(self._rows)))
+        next_state = np.zeros((self.arms, *self.context_dim), dtype=np.float32)
+        for k in range(self.arms):
+            next_state[k, k * self.features:(k + 1) * self.features] = self._rows[r]
+        return next_state, int(self._targets[r])
+
+    def reset(self):
+        next_state, target = self._new_state_and_target_action()
+        self.prev_reward = np.zeros(self.arms)
+        self.prev_reward[target] = 1
+        return next_state
+
+    def step(self, k: int):
+        reward = self.prev_reward[int(k)]
+        next_state, target = self._new_state_and_target_action()
+        self.prev_reward = np.zeros(self.arms)
+        self.prev_reward[target] = 1
+        return next_state, reward

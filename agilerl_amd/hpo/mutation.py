@@ -59,6 +59,13 @@ What runs, with the reference's draws from the reference's generators:
   applied method on every actor that has it, the analogous method on every
   critic, targets re-made; bit-exact against the reference's own networks.
 
+* NeuralUCB / NeuralTS agents take the ``lr`` / ``batch_size`` / ``learn_step``
+  mutations, parameter mutations and architecture mutations as DQN agents do
+  (their single network has no target copy).  After an architecture mutation
+  the inverse covariance follows ``reinit_bandit_grads`` below — the rule of
+  _reinit_bandit_grads (:1064-1160) — and theta_0 / numel are re-read
+  (algorithms/neural_ucb_bandit.py).
+
 Not applied: architecture / activation mutations of DQN / Rainbow / MADDPG
 agents in a population sharded over ranks (the modules' draws are not
 replayed on the other ranks; recorded as no mutation with a warning, on
@@ -85,6 +92,34 @@ def set_global_seed(seed: int | None) -> None:
     np.random.seed(seed)
     torch.manual_seed(seed)
     random.seed(seed)
+
+
+def reinit_bandit_grads(sigma_inv: np.ndarray, old_sizes: dict, new_sizes: dict, lamb: float) -> np.ndarray:
+    """The rule of ``Mutations._reinit_bandit_grads`` (mutation.py:1064-1160)
+    on a bandit's inverse covariance when the exploration layer's parameters
+    change size.  ``old_sizes`` / ``new_sizes``: parameter name -> element
+    count, in parameter order.  Rows and columns of elements that no longer
+    exist are dropped (a shrunk parameter loses its tail, a vanished one
+    everything); new elements are inserted as zero rows and columns with
+    ``lamb`` on the diagonal (a grown parameter gains a tail).  The reference
+    writes ``lamb`` only at the first inserted index of a run and takes the
+    old layer after the mutation; here every inserted index gets ``lamb`` and
+    the caller passes the sizes from before the mutation."""
+    keep, i = [], 0
+    for key, old in old_sizes.items():
+        keep += list(range(i, i + min(old, new_sizes.get(key, 0))))
+        i += old
+    kept = np.asarray(sigma_inv)[np.ix_(keep, keep)]
+    pos, fresh, i = [], [], 0  # where the kept elements land, and the new indices
+    for key, new in new_sizes.items():
+        n_old = min(old_sizes.get(key, 0), new)
+        pos += list(range(i, i + n_old))
+        fresh += list(range(i + n_old, i + new))
+        i += new
+    out = np.zeros((i, i), dtype=kept.dtype)
+    out[np.ix_(pos, pos)] = kept
+    out[fresh, fresh] = lamb
+    return out
 
 
 class Mutations:

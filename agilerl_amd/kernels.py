@@ -2,7 +2,10 @@
 
 Every function takes device tensors, validates shapes/dtypes/devices on the
 host (so a kernel never sees a mismatched grid), launches on the current HIP
-stream and returns without synchronising.  No CPU fallback exists.
+stream and returns without synchronising.  No CPU fallback exists.  (One
+function here is torch ops by design: ``bandit_select_torch``, the bandit
+agents' CPU arithmetic and ``bandit_select``'s stated path past the kernel's
+shape range.)
 """
 
 from __future__ import annotations
@@ -593,3 +596,108 @@ def polyak_segments_(targets, onlines, tau: float) -> None:
         for j, (t, o) in enumerate(chunk):
             arr[j] = _PolyakSegment(t.data_ptr(), o.data_ptr(), t.numel())
         _lib.call("agx_polyak_segments", ctypes.cast(arr, ctypes.c_void_p), len(chunk), float(tau), _lib.stream())
+
+
+# --------------------------------------------------------------------------- #
+# Neural contextual bandits (include/agx_bandit.h)                             #
+# --------------------------------------------------------------------------- #
+BANDIT_RESIDENT_MAX_D = 112  # AGX_BANDIT_RESIDENT_MAX_D
+BANDIT_MAX_D = 1025          # AGX_BANDIT_MAX_D
+BANDIT_MAX_ARMS = 1024       # AGX_BANDIT_MAX_ARMS
+
+
+def bandit_normals(A: int, seed: int, counter: int):
+    """float32 [A]: the Thompson draws of one agx_bandit_select call on the
+    host — words (x, y) of the Philox4x32-10 block of (arm, 0, counter) under
+    key ``seed``, Box-Muller (agx_bandit.h).  The device evaluates log / sqrt /
+    cospi in float32; these are float64 values rounded once."""
+    import numpy as np
+
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.arange(A, dtype=np.uint64), np.zeros(A, np.uint64), np.full(A, counter & 0xFFFFFFFF, np.uint64),
+         np.full(A, (counter >> 32) & 0xFFFFFFFF, np.uint64)]
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    u = [((w >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24) for w in c[:2]]
+    return (np.sqrt(-2.0 * np.log(u[0].astype(np.float64))) * np.cos(2.0 * np.pi * u[1].astype(np.float64))
+            ).astype(np.float32)
+
+
+@torch.no_grad()
+def bandit_select_torch(h, mu, sigma_inv, mask=None, *, bias_one=True, scale=1.0, gamma=1.0, thompson=False,
+                        seed=0, counter=None):
+    """agx_bandit_select's arithmetic in torch ops on the tensors' device
+    (f64 sums rounded to f32 once, the rank-1 form of the update): what the
+    agents run on the CPU, and what ``bandit_select`` runs for shapes past the
+    kernel's range.  Same arguments and results; ``sigma_inv`` and ``counter``
+    are updated in place."""
+    A = h.shape[0]
+    g = h.to(_f32) * scale
+    if bias_one:
+        g = torch.cat([g, torch.full((A, 1), float(scale), dtype=_f32, device=g.device)], dim=1)
+    g64, S = g.to(_f64), sigma_inv.to(_f64)
+    quad = ((g64 @ S) * g64).sum(dim=1)
+    width = gamma * torch.sqrt(quad)
+    if thompson:
+        z = torch.from_numpy(bandit_normals(A, int(seed), int(counter.item()))).to(width.device)
+        width = width * z.to(_f64)
+        counter += 1
+    scores, quad = (mu.to(_f64) + width).to(_f32), quad.to(_f32)
+    eff = scores if mask is None else torch.where(mask.reshape(-1).to(scores.device) == 1, scores,
+                                                  torch.full_like(scores, -float("inf")))
+    nan = torch.isnan(eff)  # np.argmax: the first NaN wins, else the first maximum
+    action = torch.where(nan.any(), nan.to(torch.int8).argmax(), torch.nan_to_num(eff, nan=-float("inf")).argmax())
+    v = g64.index_select(0, action.reshape(1))[0]
+    u, w = S @ v, S.t() @ v
+    r = 1.0 / (1.0 + torch.dot(v, u))
+    sigma_inv.copy_((S - torch.outer(u * r, w)).to(_f32))
+    return action.reshape(1).to(_i64), scores, quad
+
+
+def bandit_select(h, mu, sigma_inv, mask=None, *, bias_one=True, scale=1.0, gamma=1.0, thompson=False, seed=0,
+                  counter=None):
+    """-> (action int64 (1,), scores (A,), quad (A,)) of one NeuralUCB /
+    NeuralTS step (neural_ucb_bandit.py:237-257): quad_k = g_k sigma_inv
+    g_k^T with g_k = scale [h_k, 1] (``bias_one``) or scale h_k, score_k =
+    mu_k + gamma sqrt(quad_k) [* z_k], numpy's masked argmax, and the
+    Sherman-Morrison update of ``sigma_inv`` in place — one launch for D =
+    H + bias_one <= BANDIT_RESIDENT_MAX_D, four above (agx_bandit.h).  ``h``
+    [A, H] may have a row stride >= H; ``mask`` uint8 / bool [A], 1 = legal;
+    ``counter`` int64 (1,) on the device, advanced by one (required when
+    ``thompson``).  Nothing is read back.  Past the kernel's range (A >
+    BANDIT_MAX_ARMS or D > BANDIT_MAX_D) the same arithmetic runs as torch ops."""
+    _need(h, "h", _f32, contiguous=False)
+    if h.dim() != 2:
+        raise ValueError(f"h: expected [A, H], got {tuple(h.shape)}")
+    A, H = h.shape
+    D = H + int(bool(bias_one))
+    if A < 1 or D < 1:
+        raise ValueError(f"bandit_select: need A >= 1 and D >= 1, got A = {A}, D = {D}")
+    ldh = H if A == 1 or H == 0 else h.stride(0)
+    if H > 0 and (h.stride(1) != 1 or ldh < H):
+        raise ValueError("h: rows must be contiguous and must not overlap")
+    _need(mu, "mu", _f32, (A,))
+    _need(sigma_inv, "sigma_inv", _f32, (D, D))
+    if mask is not None:
+        mask = mask.reshape(-1)
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        _need(mask, "mask", _u8, (A,))
+    if thompson or counter is not None:
+        _need(counter, "counter", _i64, (1,))
+    if A > BANDIT_MAX_ARMS or D > BANDIT_MAX_D:
+        return bandit_select_torch(h, mu, sigma_inv, mask, bias_one=bias_one, scale=scale, gamma=gamma,
+                                   thompson=thompson, seed=seed, counter=counter)
+    dev = mu.device
+    action = torch.empty(1, dtype=_i64, device=dev)
+    scores = torch.empty(A, dtype=_f32, device=dev)
+    quad = torch.empty(A, dtype=_f32, device=dev)
+    ws = _ws(_lib.load().agx_bandit_workspace_bytes(A, D), dev)
+    _lib.call("agx_bandit_select", h.data_ptr() if H else None, ldh, mu.data_ptr(), sigma_inv.data_ptr(),
+              _lib.ptr(mask), A, H, int(bool(bias_one)), float(scale), float(gamma), int(bool(thompson)),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(counter), scores.data_ptr(), quad.data_ptr(),
+              action.data_ptr(), ws.data_ptr(), _lib.stream())
+    return action, scores, quad

@@ -109,8 +109,16 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         cls = DDPG if algo == "DDPG" else TD3
         return [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, num_envs=num_envs,
                                  device=device, hp_config=hp_config, **algo_kwargs) for i in range(P)]
+    if algo in ("NeuralUCB", "NeuralTS"):  # utils/utils.py:682-722
+        from ..algorithms import NeuralTS, NeuralUCB
+
+        if world > 1:
+            raise NotImplementedError(f"{algo} populations run in a single process (train_bandits is not sharded)")
+        cls = NeuralUCB if algo == "NeuralUCB" else NeuralTS
+        return [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, device=device,
+                                 hp_config=hp_config, actor_network=actor_network, **algo_kwargs) for i in range(P)]
     raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, CQN, "
-                              "MADDPG, MATD3, DDPG, TD3)")
+                              "MADDPG, MATD3, DDPG, TD3, NeuralUCB, NeuralTS)")
 
 
 __all__ = ["create_population"]
