@@ -30,7 +30,7 @@ class AgxMultiHead(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
-# agx_bernoulli.h, agx_cqn.h, agx_bandit.h) one-to-one
+# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -148,6 +148,8 @@ SIGNATURES = {
     "agx_bandit_workspace_bytes": (_SZ, [_I, _I]),
     "agx_bandit_select": (_INT, [_P, _I, _P, _P, _P, _I, _I, _INT, _F, _F, _INT, ctypes.c_uint64, _P, _P, _P, _P, _P,
                                  _P]),
+    # include/agx_ippo.h: IPPO's float32 GAE over up to 8 agent groups
+    "agx_ippo_gae": (_INT, [_P, _INT, _I, _D, _D, _P]),
     "agx_c51_project_loss": (_INT, [_P] * 7 + [_I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_c51_project_loss_rows": (_INT, [_P] * 5 + [_I, _I, _D, _D, _D, _P, _P, _P]),
     "agx_adam_workspace_bytes": (_SZ, [_I, _I]),

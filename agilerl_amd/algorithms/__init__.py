@@ -3,6 +3,7 @@
 from .cqn import CQN
 from .ddpg import DDPG
 from .dqn import DQN, RainbowDQN
+from .ippo import IPPO
 from .maddpg import MADDPG
 from .matd3 import MATD3
 from .neural_ts_bandit import NeuralTS
@@ -10,4 +11,5 @@ from .neural_ucb_bandit import NeuralUCB
 from .ppo import PPO
 from .td3 import TD3
 
-__all__ = ["PPO", "DQN", "RainbowDQN", "MADDPG", "MATD3", "DDPG", "TD3", "CQN", "NeuralUCB", "NeuralTS"]
+__all__ = ["PPO", "DQN", "RainbowDQN", "MADDPG", "MATD3", "DDPG", "TD3", "CQN", "NeuralUCB", "NeuralTS",
+           "IPPO"]

@@ -2238,6 +2238,7 @@ int learn_graph(const char *what, const agx_ppo_graph *net, const HeadArg &h, co
     AGX_REQUIRE(P > 0 && P <= 65535 && S > 0 && S < (1ll << 31) && epochs > 0 && batch > 0 && epochs * P <= 65535,
                 "%s: bad sizes P=%lld S=%lld epochs=%lld batch=%lld", what, (long long)P, (long long)S,
                 (long long)epochs, (long long)batch);
+    if (int rc = adv_norm_minibatch_check(what, x)) return rc;
     const int64_t bb = batch < S ? batch : S;
     const Split sp = graph_split<HEAD>(net, P, bb);
     const int K = sp.K, R = sp.R, Q = sp.Q;
@@ -2273,6 +2274,11 @@ int learn_graph(const char *what, const agx_ppo_graph *net, const HeadArg &h, co
         x->error_word);
     const int rc2 = check_launch(what);
     if (rc2) return rc2;
+    if (x->adv_norm_minibatch) {  // IPPO: the gathered advantages, minibatch by minibatch
+        ppo_adv_norm_minibatch_kernel<<<dim3((unsigned)ceil_div(S, bb), (unsigned)(epochs * P)), kNormThreads, 0, s>>>(
+            grow, S, bb, (int)P, x->epochs_per_agent);
+        if (int rc3 = check_launch(what)) return rc3;
+    }
     a.ws = reinterpret_cast<float *>(ws + (K > 1 ? pw.scratch : w.agents));
     a.params = x->params;
     a.m = x->exp_avg;

@@ -2512,6 +2512,11 @@ extern "C" int agx_debug_learn_stall(int on) {
 
 extern "C" int agx_ppo_learn(const agx_ppo_net *net, const agx_ppo_learn_args *x, void *workspace, void *stream) {
     AGX_REQUIRE(net && x && workspace, "agx_ppo_learn: null net / args / workspace");
+    if (x->adv_norm_minibatch) {
+        set_error("agx_ppo_learn: adv_norm_minibatch is not supported by the compiled shapes (agx_ppo_learn_graph "
+                  "takes it)");
+        return AGX_EUNSUPPORTED;
+    }
     AGX_REQUIRE(x->params && x->exp_avg && x->exp_avg_sq && x->adam_step && x->lr && x->obs && x->actions &&
                     x->old_logp && x->adv && x->ret && x->old_value && x->perms,
                 "agx_ppo_learn: null pointer");

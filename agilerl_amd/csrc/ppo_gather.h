@@ -123,5 +123,64 @@ __global__ void ppo_gather_kernel(const float *__restrict__ obs, const typename 
     gr[3 * S + j] = old_v[sp];
 }
 
+// agx_ppo_learn_args.adv_norm_minibatch: the gathered advantages normalised
+// minibatch by minibatch (ippo.py:780-783), in place, after ppo_gather_kernel.
+// Block (m, e * P + p): rows [m B, min((m + 1) B, S)) of agent p's epoch-e
+// order, the rows the learner's minibatch m reads.  Two passes, mean then
+// unbiased standard deviation, each an f64 sum in a fixed order (a thread's
+// rows ascending, the xor butterfly of its wave, the waves ascending), then
+// (a - mean) / (std + 1e-8) in f64, rounded to f32 once as ppo_gather_kernel's
+// adv_stats form is.  A minibatch of fewer than two rows has no unbiased std
+// (the host rejects the sizes that produce one) and is left as gathered.
+constexpr int kNormThreads = 256;
+__device__ __forceinline__ double norm_block_sum(double v, double *part) {
+    v = wave_sum(v);
+    __syncthreads();  // the previous sum's readers are done with part
+    if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = v;
+    __syncthreads();
+    double s = part[0];
+    for (int w = 1; w < kNormThreads / kWave; ++w) s += part[w];
+    return s;
+}
+
+__global__ __launch_bounds__(kNormThreads) void ppo_adv_norm_minibatch_kernel(float *__restrict__ grow, long long S,
+                                                                              long long B, int P,
+                                                                              const int *__restrict__ epochs_p) {
+    __shared__ double part[kNormThreads / kWave];
+    const int ep = blockIdx.y;  // e * P + p
+    if (epochs_p && ep / P >= epochs_p[ep % P]) return;  // rows the learner never reads (uniform over the block)
+    const long long lo = (long long)blockIdx.x * B;
+    const long long hi = lo + B < S ? lo + B : S;
+    const long long n = hi - lo;
+    if (n < 2) return;
+    float *a = grow + (size_t)ep * 4 * S + S + lo;
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < n; i += kNormThreads) s += (double)a[i];
+    const double mean = norm_block_sum(s, part) / (double)n;
+    double q = 0.0;
+    for (long long i = threadIdx.x; i < n; i += kNormThreads) {
+        const double c = (double)a[i] - mean;
+        q += c * c;
+    }
+    const double denom = sqrt(norm_block_sum(q, part) / (double)(n - 1)) + 1e-8;
+    for (long long i = threadIdx.x; i < n; i += kNormThreads) a[i] = (float)(((double)a[i] - mean) / denom);
+}
+
+// The host-side rules of the flag, before any launch (`what`: the entry point).
+inline int adv_norm_minibatch_check(const char *what, const agx_ppo_learn_args *x) {
+    if (!x->adv_norm_minibatch) return AGX_OK;
+    AGX_REQUIRE(!x->adv_stats, "%s: adv_norm_minibatch normalises the advantages itself: adv_stats must be NULL",
+                what);
+    if (x->batch_per_agent) {
+        set_error("%s: adv_norm_minibatch with batch_per_agent is not supported", what);
+        return AGX_EUNSUPPORTED;
+    }
+    const long long bb = x->batch < x->S ? x->batch : x->S;
+    AGX_REQUIRE(bb > 1 && x->S % bb != 1,
+                "%s: adv_norm_minibatch: S=%lld, batch=%lld leave a one-row minibatch, which has no unbiased std",
+                what, (long long)x->S, (long long)x->batch);
+    return AGX_OK;
+}
+
 }  // namespace
 }  // namespace agx

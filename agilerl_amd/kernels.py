@@ -599,6 +599,49 @@ def polyak_segments_(targets, onlines, tau: float) -> None:
 
 
 # --------------------------------------------------------------------------- #
+# IPPO (include/agx_ippo.h)                                                    #
+# --------------------------------------------------------------------------- #
+class IppoGaeSegment(ctypes.Structure):
+    """Mirror of ``agx_ippo_gae_segment`` (include/agx_ippo.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rewards", "dones", "values", "next_value", "next_done",
+                                                "advantages", "returns")] + [("M", ctypes.c_int64)]
+
+
+IPPO_MAX_SEGMENTS = 8  # AGX_IPPO_MAX_SEGMENTS
+
+
+def ippo_gae_table(segments):
+    """(table, T) of ``ippo_gae``'s launch for ``segments``: tuples (rewards,
+    dones, values [T, M], next_value, next_done [M], advantages, returns
+    [T, M]) of contiguous f32 device tensors, one per agent group.  The table
+    holds raw pointers: the caller keeps the tensors alive while it is used."""
+    if not 1 <= len(segments) <= IPPO_MAX_SEGMENTS:
+        raise ValueError(f"ippo_gae: 1..{IPPO_MAX_SEGMENTS} segments per launch (got {len(segments)})")
+    T = int(segments[0][0].shape[0])
+    arr = (IppoGaeSegment * len(segments))()
+    for k, (r, d, v, nv, nd, adv, ret) in enumerate(segments):
+        if r.dim() != 2 or r.shape[0] != T:
+            raise ValueError(f"ippo_gae: segment {k}: rewards {tuple(r.shape)}, expected [{T}, M]")
+        M = int(r.shape[1])
+        for t, name in ((r, "rewards"), (d, "dones"), (v, "values"), (adv, "advantages"), (ret, "returns")):
+            _need(t, name, _f32, (T, M))
+        _need(nv, "next_value", _f32, (M,))
+        _need(nd, "next_done", _f32, (M,))
+        arr[k] = IppoGaeSegment(*(t.data_ptr() if M else None for t in (r, d, v, nv, nd, adv, ret)), M)
+    return arr, T
+
+
+def ippo_gae(segments, gamma: float, gae_lambda: float) -> None:
+    """agx_ippo_gae: the float32 GAE of ippo.py:702-725 for every agent group
+    of ``segments`` (``ippo_gae_table``) in one launch; advantages and returns
+    are written in place, bit for bit the reference's torch loop."""
+    arr, T = ippo_gae_table(segments)
+    _lib.call("agx_ippo_gae", ctypes.cast(arr, ctypes.c_void_p), len(segments), T, float(gamma), float(gae_lambda),
+              _lib.stream())
+
+
+# --------------------------------------------------------------------------- #
 # Neural contextual bandits (include/agx_bandit.h)                             #
 # --------------------------------------------------------------------------- #
 BANDIT_RESIDENT_MAX_D = 112  # AGX_BANDIT_RESIDENT_MAX_D

@@ -141,6 +141,7 @@ class AgxPPOLearnArgs(ctypes.Structure):
         ("error_word", ctypes.c_void_p),
         ("batch_per_agent", ctypes.c_void_p), ("epochs_per_agent", ctypes.c_void_p),
         ("ent_coef_per_agent", ctypes.c_void_p), ("skip_if_set", ctypes.c_void_p),
+        ("adv_norm_minibatch", ctypes.c_int32),
     ]
 
 
@@ -171,22 +172,27 @@ class FusedLearner:
     def learn(self, pop, perms: torch.Tensor | None = None, skip_if_set: int | None = None) -> torch.Tensor:
         """All epochs x minibatches of every agent in two launches (gather +
         learner).  Advantages are normalised on the fly from pop.adv_stats
-        (ppo.py:829-834); pop.advantages itself is left untouched."""
+        (ppo.py:829-834); pop.advantages itself is left untouched.  A
+        population with ``adv_norm_minibatch`` set (IPPO's groups) passes no
+        statistics: the prologue normalises the gathered rows minibatch by
+        minibatch instead (one more launch, ippo.py:780-783)."""
         if perms is None:
             perms = pop.permutations()
         opt = pop.opt
         b1, b2 = opt.betas
         masks = pop.action_masks
+        per_mb = bool(getattr(pop, "adv_norm_minibatch", False))
         # the argument block is rebuilt only when a buffer or hyperparameter
         # changes; per call only the permutations and the stream change (host
         # time between the rollout and the learner is on the critical path)
         key = (pop.params.data.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), opt.lr.data_ptr(),
                opt.steps.data_ptr(), pop.obs.data_ptr(), pop.advantages.data_ptr(), pop.returns.data_ptr(),
-               pop.values.data_ptr(), pop.log_probs.data_ptr(), pop.actions.data_ptr(), pop.adv_stats.data_ptr(),
+               pop.values.data_ptr(), pop.log_probs.data_ptr(), pop.actions.data_ptr(),
+               None if per_mb else pop.adv_stats.data_ptr(),
                None if masks is None else masks.data_ptr(), float(b1), float(b2), float(opt.eps), pop.split_batch,
                pop.update_epochs, float(pop.clip_coef), float(pop.vf_coef), float(pop.ent_coef),
                float(pop.max_grad_norm), float(pop.target_kl or 0.0), pop.err_word.data_ptr(),
-               *((None, None, None) if pop._hp_dev is None else (t.data_ptr() for t in pop._hp_dev)))
+               *((None, None, None) if pop._hp_dev is None else (t.data_ptr() for t in pop._hp_dev)), per_mb)
         if self.key != key:
             a = self.args
             a.P, a.S, a.epochs, a.batch = pop.P, pop.S, pop.update_epochs, pop.split_batch
@@ -200,6 +206,7 @@ class FusedLearner:
             a.loss_out, a.kl_out = self.loss.data_ptr(), self.kl.data_ptr()
             a.epochs_out, a.error_word = self.epochs_run.data_ptr(), key[23]
             a.batch_per_agent, a.epochs_per_agent, a.ent_coef_per_agent = key[24], key[25], key[26]
+            a.adv_norm_minibatch = int(key[27])
             self.key = key
             self.aref = ctypes.byref(self.args)
             self.dref = ctypes.byref(self.desc)

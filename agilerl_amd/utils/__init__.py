@@ -98,6 +98,23 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         for a in agents:
             a.sharded = bool(shard and world > 1)
         return agents[lo:lo + P]
+    if algo == "IPPO":  # utils/utils.py:651-680
+        from ..algorithms import IPPO
+
+        if world > 1:
+            raise NotImplementedError("IPPO populations run in a single process (multi-rank populations are not "
+                                      "supported)")
+        return [IPPO(observation_space, action_space, agent_ids=INIT_HP["AGENT_IDS"], index=i, hp_config=hp_config,
+                     net_config=net_config, batch_size=INIT_HP.get("BATCH_SIZE", 64), lr=INIT_HP.get("LR", 0.0001),
+                     learn_step=INIT_HP.get("LEARN_STEP", 2048), gamma=INIT_HP.get("GAMMA", 0.99),
+                     gae_lambda=INIT_HP.get("GAE_LAMBDA", 0.95),
+                     action_std_init=INIT_HP.get("ACTION_STD_INIT", 0.0), clip_coef=INIT_HP.get("CLIP_COEF", 0.2),
+                     ent_coef=INIT_HP.get("ENT_COEF", 0.01), vf_coef=INIT_HP.get("VF_COEF", 0.5),
+                     max_grad_norm=INIT_HP.get("MAX_GRAD_NORM", 0.5), target_kl=INIT_HP.get("TARGET_KL"),
+                     update_epochs=INIT_HP.get("UPDATE_EPOCHS", 4), actor_networks=actor_network,
+                     critic_networks=critic_network, action_batch_size=INIT_HP.get("ACTION_BATCH_SIZE"),
+                     device=device, accelerator=accelerator, torch_compiler=torch_compiler, **algo_kwargs)
+                for i in range(P)]
     if algo in ("DDPG", "TD3"):  # utils/utils.py:466-493, 560-587
         from ..algorithms import DDPG, TD3
 
@@ -118,7 +135,7 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
         return [cls.from_init_hp(observation_space, action_space, net_config, INIT_HP, index=i, device=device,
                                  hp_config=hp_config, actor_network=actor_network, **algo_kwargs) for i in range(P)]
     raise NotImplementedError(f"algorithm {algo!r} is outside the agx hot path (PPO, DQN, Rainbow DQN, CQN, "
-                              "MADDPG, MATD3, DDPG, TD3, NeuralUCB, NeuralTS)")
+                              "MADDPG, MATD3, IPPO, DDPG, TD3, NeuralUCB, NeuralTS)")
 
 
 __all__ = ["create_population"]

@@ -173,6 +173,19 @@ typedef struct agx_ppo_learn_args {
      * rollout the host aborted (env exception) or that timed out never runs
      * on the partial rollout. */
     const uint32_t *skip_if_set;
+    /* nonzero (the runtime-shape learners, agx_ppo_learn_*graph, only): the
+     * advantages are normalised minibatch by minibatch instead of per rollout
+     * (IPPO, agilerl/algorithms/ippo.py:780-783).  One more launch after the
+     * gather prologue takes the rows of every (epoch, agent, minibatch) the
+     * learner reads, in minibatch order, to (a - mean) / (std + 1e-8): mean
+     * and unbiased std two-pass f64 sums in a fixed order, the quotient in
+     * f64, rounded to f32 once.  A short last minibatch uses its own rows.
+     * adv_stats must then be NULL and min(batch, S) > 1, S % batch != 1
+     * (a one-row minibatch has no unbiased std; the reference skips it):
+     * AGX_EINVAL; batch_per_agent must be NULL, and agx_ppo_learn does not
+     * take the flag: AGX_EUNSUPPORTED.  All before any launch.  0: every
+     * call launches exactly what it did without the field. */
+    int32_t adv_norm_minibatch;
 } agx_ppo_learn_args;
 int agx_ppo_learn(const agx_ppo_net *net, const agx_ppo_learn_args *args, void *workspace, void *stream);
 /* Rollout policy step (PPO.get_action / _get_action_and_values, ppo.py:
