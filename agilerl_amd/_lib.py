@@ -30,7 +30,7 @@ class AgxMultiHead(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
-# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h) one-to-one
+# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -161,6 +161,10 @@ SIGNATURES = {
     "agx_noisy_streams_forward_each": (_INT, [_P, _INT, _INT, _P, _I, _F, _P]),
     "agx_noisy_streams_workspace_bytes": (_SZ, [_P, _INT, _INT, _I]),
     "agx_noisy_streams_backward": (_INT, [_P, _INT, _INT, _P, _I, _F, _P, _P, _P, _P]),
+    # include/agx_simba.h: SimBa encoders (descriptor: modules/simba.py AgxSimbaDesc)
+    "agx_simba_forward": (_INT, [_P, _P, _I, _P]),
+    "agx_simba_workspace_bytes": (_SZ, [_P, _I]),
+    "agx_simba_backward": (_INT, [_P, _P, _I, _P, _P, _P, _P]),
     "agx_conv2d_forward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _INT, _P, _P]),
     "agx_conv2d_wgrad_workspace_bytes": (_SZ, [_P]),
     "agx_conv2d_backward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _P, _P, _P, _P, _INT, _P, _P]),

@@ -19,6 +19,7 @@ import torch
 
 from .. import kernels as K
 from ..modules.mlp import EvolvableMLP
+from ..modules.simba import EvolvableSimBa
 from . import learn_graph
 from .ddpg import restore_arch, save_arch
 from .dqn import _EpsilonGreedyQAgent
@@ -63,7 +64,7 @@ class CQN(_EpsilonGreedyQAgent):
     # (ddpg.py save_arch / restore_arch, plus the activation, which DDPG / TD3
     # never mutate), so that a mutated agent loads into a freshly built one.
     def _ckpt_extra(self, ck: dict) -> None:
-        if isinstance(getattr(self.actor, "encoder", None), EvolvableMLP):
+        if isinstance(getattr(self.actor, "encoder", None), (EvolvableMLP, EvolvableSimBa)):
             save_arch(self, ck)
             ck["network_activation"] = self.actor.activation
 

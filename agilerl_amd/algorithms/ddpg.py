@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from ..modules.simba import EvolvableSimBa
 from ..networks import ContinuousQNetwork, DeterministicActor
 from ..networks.base import as_config, mlp_net_config
 from . import checkpoint as C
@@ -43,8 +44,12 @@ from .offpolicy import MSECriticLoss, _evaluate, batch
 
 
 def _arch(net) -> dict:
-    """What architecture mutations change of an MLP-encoder network."""
-    return {"latent_dim": int(net.latent_dim), "encoder": [int(h) for h in net.encoder.hidden_size],
+    """What architecture mutations change of an MLP-encoder network (the
+    encoder's hidden sizes) or a SimBa-encoder one (its width and blocks)."""
+    enc = net.encoder
+    return {"latent_dim": int(net.latent_dim),
+            "encoder": {"hidden_size": int(enc.hidden_size), "num_blocks": int(enc.num_blocks)}
+            if isinstance(enc, EvolvableSimBa) else [int(h) for h in enc.hidden_size],
             "head": [int(h) for h in net.head_net.hidden_size]}
 
 
@@ -53,7 +58,11 @@ def _set_arch(net, arch: dict) -> None:
         return
     old = net.latent_dim
     net.latent_dim = int(arch["latent_dim"])
-    net.encoder.hidden_size = [int(h) for h in arch["encoder"]]
+    if isinstance(net.encoder, EvolvableSimBa):
+        net.encoder.hidden_size = int(arch["encoder"]["hidden_size"])
+        net.encoder.num_blocks = int(arch["encoder"]["num_blocks"])
+    else:
+        net.encoder.hidden_size = [int(h) for h in arch["encoder"]]
     net.head_net.hidden_size = [int(h) for h in arch["head"]]
     net.recreate_network(old)
 
@@ -142,7 +151,9 @@ class _DeterministicPolicyGradient(EvolvableAgentMixin, C.TorchCheckpointMixin):
         # network construction (td3.py:242-303, ddpg.py:228-287)
         net_config = copy.deepcopy(as_config(net_config) or {})
         encoder_config = as_config(net_config.get("encoder_config"))
-        if encoder_config is not None:
+        if net_config.get("simba"):
+            pass  # EvolvableSimBa encoders: their own config (None: hidden 128, two blocks)
+        elif encoder_config is not None:
             if "hidden_size" in encoder_config:
                 if encoder_config.get("layer_norm", False):
                     warnings.warn(f"Layer normalization is not supported for the encoder of {name} networks. "

@@ -145,6 +145,22 @@ class _EpsilonGreedyQAgent(EvolvableAgentMixin, C.TorchCheckpointMixin):
 class DQN(_EpsilonGreedyQAgent):
     algo = "DQN"
 
+    # With a SimBa encoder a checkpoint carries what architecture mutations
+    # change (ddpg.py save_arch / restore_arch), so a mutated agent loads into
+    # a freshly built one; MLP and CNN encoders keep the checkpoint they had.
+    def _ckpt_extra(self, ck: dict) -> None:
+        from ..modules.simba import EvolvableSimBa
+        from .ddpg import save_arch
+
+        if isinstance(getattr(self.actor, "encoder", None), EvolvableSimBa):
+            save_arch(self, ck)
+
+    def _ckpt_restore(self, ck: dict) -> None:
+        from .ddpg import restore_arch
+
+        if "network_arch" in ck:
+            restore_arch(self, ck)
+
     def __init__(self, observation_space, action_space, index: int = 0, hp_config=None, net_config=None,
                  batch_size: int = 64, lr: float = 1e-4, learn_step: int = 5, gamma: float = 0.99,
                  tau: float = 1e-3, mut=None, normalize_images: bool = True, double: bool = False,

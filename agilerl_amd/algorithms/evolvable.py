@@ -68,9 +68,10 @@ class EvolvableAgentMixin:
             # every multi-rank run as one population split over the ranks.
             return False
         from ..modules.cnn import EvolvableCNN
+        from ..modules.simba import EvolvableSimBa
 
         net = getattr(self, self._groups[0].net)
-        return isinstance(getattr(net, "encoder", None), (EvolvableMLP, EvolvableCNN)) and \
+        return isinstance(getattr(net, "encoder", None), (EvolvableMLP, EvolvableCNN, EvolvableSimBa)) and \
             isinstance(getattr(net, "head_net", None), EvolvableMLP)
 
     def architecture_mutation(self, new_layer_prob: float, rng) -> str:

@@ -97,17 +97,9 @@ def enabled() -> bool:
 def _hooked(*nets) -> bool:
     """Module hooks run Python during forward / backward: a replay would
     skip them."""
-    from torch.nn.modules import module as M
+    from ..modules._hooks import hooked
 
-    if (M._global_forward_hooks or M._global_forward_pre_hooks or M._global_backward_hooks or
-            getattr(M, "_global_backward_pre_hooks", None)):
-        return True
-    for net in nets:
-        for m in net.modules():
-            if (m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or
-                    getattr(m, "_backward_pre_hooks", None)):
-                return True
-    return False
+    return hooked(*nets)
 
 
 def _sig(t: torch.Tensor) -> tuple:

@@ -29,7 +29,7 @@ import torch
 
 from ..envs import Dict as DictSpace
 from ..networks import ContinuousQNetwork, DeterministicActor
-from ..networks.base import as_config, mlp_net_config
+from ..networks.base import as_config, mlp_net_config, reject_simba
 from . import checkpoint as C
 from .evolvable import EvolvableAgentMixin, NetGroup
 from .offpolicy import MSECriticLoss
@@ -138,6 +138,7 @@ class _MultiAgentPolicyGradient(EvolvableAgentMixin, C.TorchCheckpointMixin):
 
     def _agent_configs(self, net_config) -> dict[str, dict]:
         net_config = copy.deepcopy(as_config(net_config) or {})
+        reject_simba(net_config)
         per_agent = all(a in net_config for a in self.agent_ids) if net_config else False
         out = {}
         for a in self.agent_ids:

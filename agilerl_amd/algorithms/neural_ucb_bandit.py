@@ -47,7 +47,7 @@ from torch import nn
 
 from .. import kernels as K
 from ..modules.mlp import EvolvableMLP
-from ..networks.base import as_config, image_norm_bounds, is_image_space, mlp_net_config
+from ..networks.base import as_config, image_norm_bounds, is_image_space, mlp_net_config, reject_simba
 from ..networks.value_networks import ValueNetwork
 from . import checkpoint as C
 from . import learn_graph
@@ -104,8 +104,9 @@ class _NeuralBandit(EvolvableAgentMixin, C.TorchCheckpointMixin):
         self.action_dim = int(action_space.n)
         self.obs_dim = int(np.prod(observation_space.shape))
         cfg = _net_kwargs(net_config)
-        if cfg.get("simba") or cfg.get("recurrent"):
-            raise NotImplementedError("SimBa and recurrent encoders are outside the agx path")
+        reject_simba(cfg)
+        if cfg.get("recurrent"):
+            raise NotImplementedError("recurrent encoders are outside the agx path")
         self._image = is_image_space(observation_space)
         if not hasattr(observation_space, "spaces"):  # neural_ucb_bandit.py:141-146: no LayerNorm
             enc = as_config(cfg.get("encoder_config"))

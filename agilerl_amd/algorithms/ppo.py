@@ -118,7 +118,9 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
     if not hasattr(action_space, "n") and not box and not multi and not binary:
         raise NotImplementedError("agx PPO supports Discrete, MultiDiscrete, MultiBinary and Box action spaces")
     net_config = dict(net_config or {})
-    from ..networks.base import is_image_space
+    from ..networks.base import is_image_space, reject_simba
+
+    reject_simba(net_config)
 
     if binary:
         # StochasticActor over a MultiBinary space (networks/actors.py:268): n Bernoulli logits.

@@ -2,8 +2,10 @@
 
 Box observations get EvolvableMLP encoders, image Box spaces (3-D shape,
 utils/evolvable_networks.py:74-84) EvolvableCNN encoders on the HIP conv
-kernels (modules/cnn.py), Dict/Tuple spaces EvolvableMultiInput; recurrent
-and SimBa encoders are outside the hot path and raise NotImplementedError.
+kernels (modules/cnn.py), Dict/Tuple spaces EvolvableMultiInput; ``simba=True``
+swaps a vector observation's encoder for EvolvableSimBa on the fused
+residual-block kernels (modules/simba.py).  Recurrent encoders are outside
+the hot path and raise NotImplementedError.
 """
 
 from __future__ import annotations
@@ -16,6 +18,24 @@ from torch import nn
 
 from ..modules.cnn import EvolvableCNN
 from ..modules.mlp import EvolvableMLP, preserve_parameters
+from ..modules.simba import EvolvableSimBa
+
+SIMBA_ALGOS = "SimBa encoders are supported for DQN, CQN, DDPG and TD3"
+
+
+def reject_simba(net_config) -> None:
+    """The algorithms whose fused learners and group kernels are MLP-only."""
+    cfg = as_config(net_config) or {}
+    if cfg.get("simba") or any(isinstance(v, dict) and v.get("simba") for v in cfg.values()):
+        raise NotImplementedError(f"{SIMBA_ALGOS}; this algorithm's fused kernels take MLP encoders")
+
+
+def assert_correct_simba_net_config(net_config: dict[str, Any]) -> None:
+    """networks/base.py:50-65."""
+    assert "hidden_size" in net_config, "Net config must contain hidden_size: int."
+    assert isinstance(net_config["hidden_size"], (int, np.int64)), "Net config hidden_size must be an integer."
+    assert "num_blocks" in net_config, "Net config must contain num_blocks: int."
+    assert isinstance(net_config["num_blocks"], int), "Net config num_blocks must be an integer."
 
 
 def mlp_net_config(hidden_size, **overrides) -> dict[str, Any]:
@@ -79,7 +99,7 @@ def flatdim(space) -> int:
 def mutation_probs(table: list[str], new_layer_prob: float) -> list[float]:
     """EvolvableModule.get_mutation_probs (modules/base.py:661-685) over a
     table of method names."""
-    layer = [m for m in table if m.split(".")[-1] in ("add_layer", "remove_layer")]
+    layer = [m for m in table if EvolvableNetwork.is_layer_method(m)]
     nl, nn_ = len(layer), len(table) - len(layer)
     if nl == 0 or nn_ == 0:
         return [1 / len(table)] * len(table)
@@ -92,8 +112,8 @@ class EvolvableNetwork(nn.Module):
                  recurrent: bool = False, device="cpu", random_seed: int | None = None,
                  encoder_name: str = "encoder") -> None:
         super().__init__()
-        if encoder_cls is not None or simba or recurrent:
-            raise NotImplementedError("agx networks build EvolvableMLP encoders (Box observations)")
+        if encoder_cls is not None or recurrent:
+            raise NotImplementedError("agx networks build EvolvableMLP / EvolvableSimBa encoders (Box observations)")
         multi = hasattr(observation_space, "spaces")
         if not multi and (not hasattr(observation_space, "shape") or hasattr(observation_space, "n")):
             raise NotImplementedError("agx networks take Box or Dict-of-Box observation spaces")
@@ -105,8 +125,10 @@ class EvolvableNetwork(nn.Module):
         self.rng = np.random.default_rng(seed=random_seed)  # latent-node draws (EvolvableModule.rng)
         encoder_config = as_config(encoder_config)
         image = not multi and is_image_space(observation_space)
+        self.simba = bool(simba) and not multi and not image  # vector spaces only (base.py:541-547)
         if encoder_config is None:  # get_default_encoder_config (utils/evolvable_networks.py:168-216)
             encoder_config = {"output_activation": "ReLU"} if multi else cnn_net_config() if image else \
+                dict(hidden_size=128, num_blocks=2, output_activation="ReLU") if self.simba else \
                 mlp_net_config([64, 64], output_activation="ReLU", output_vanish=False)
         if encoder_config.get("output_activation") is None:  # base.py:226-230
             encoder_config["output_activation"] = encoder_config.get("activation", "ReLU")
@@ -127,12 +149,20 @@ class EvolvableNetwork(nn.Module):
             # the encoder's LAYER mutations are disabled (networks/base.py:266-268)
             self.encoder.disable_mutations("layer")
             return
+        self.flatten_obs = len(observation_space.shape) > 1
+        if self.simba:  # EvolvableSimBa encoder (base.py:541-562)
+            assert_correct_simba_net_config(encoder_config)
+            encoder_config.pop("num_outputs", None)
+            self.encoder_config = encoder_config
+            self.encoder = EvolvableSimBa(num_inputs=int(np.prod(observation_space.shape)), num_outputs=latent_dim,
+                                          device=device, name=encoder_name, **encoder_config)
+            self.encoder.disable_mutations("layer")
+            return
         # MLP encoders: output LayerNorm follows layer_norm, no output vanish (base.py:547-554)
         encoder_config["output_layernorm"] = encoder_config.get("layer_norm", True)
         encoder_config["output_vanish"] = False
         encoder_config.pop("num_outputs", None)
         self.encoder_config = encoder_config
-        self.flatten_obs = len(observation_space.shape) > 1
         self.encoder = EvolvableMLP(num_inputs=int(np.prod(observation_space.shape)), num_outputs=latent_dim,
                                     device=device, name=encoder_name, **encoder_config)
 
@@ -160,7 +190,7 @@ class EvolvableNetwork(nn.Module):
     def recreate_encoder(self) -> None:
         """networks/base.py:493-503: the encoder rebuilt for the current latent,
         parameters kept where the shapes overlap."""
-        if isinstance(self.encoder, EvolvableCNN):
+        if isinstance(self.encoder, (EvolvableCNN, EvolvableSimBa)):
             self.encoder.num_outputs = self.latent_dim
             self.encoder.recreate_network()
             return
@@ -232,7 +262,7 @@ class EvolvableNetwork(nn.Module):
 
     @staticmethod
     def is_layer_method(method: str) -> bool:
-        return method.split(".")[-1] in ("add_layer", "remove_layer")
+        return method.split(".")[-1] in ("add_layer", "remove_layer", "add_block", "remove_block")
 
     def sample_mutation_method(self, new_layer_prob: float, rng) -> str:
         """EvolvableModule.sample_mutation_method (modules/base.py:661-711):

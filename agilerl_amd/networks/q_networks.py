@@ -227,7 +227,7 @@ class ContinuousQNetwork(EvolvableNetwork):
                  min_latent_dim: int = 8, max_latent_dim: int = 128, latent_dim: int = 32, simba: bool = False,
                  recurrent: bool = False, device="cpu", random_seed: int | None = None) -> None:
         encoder_config = as_config(encoder_config)
-        if not hasattr(observation_space, "spaces"):
+        if not hasattr(observation_space, "spaces") and not simba:  # a SimBa encoder keeps its LayerNorms
             if encoder_config is None:
                 encoder_config = mlp_net_config([64, 64], output_activation="ReLU", output_vanish=False,
                                                 layer_norm=False)

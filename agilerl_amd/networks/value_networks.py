@@ -3,7 +3,7 @@ a "value" head with one output — the network of the neural bandits, whose
 output ``Linear(H, 1)`` is their exploration layer.  Same module tree and
 state-dict keys as the reference (``encoder.model.encoder_linear_layer_1.
 weight``, ``head_net.model.value_linear_layer_output.weight`` ...).  MLP and
-CNN encoders; SimBa and recurrent encoders raise, as for every network here.
+CNN encoders; ``simba=True`` builds an EvolvableSimBa encoder (networks/base.py), recurrent encoders raise.
 """
 
 from __future__ import annotations
