@@ -165,6 +165,10 @@ SIGNATURES = {
     "agx_simba_forward": (_INT, [_P, _P, _I, _P]),
     "agx_simba_workspace_bytes": (_SZ, [_P, _I]),
     "agx_simba_backward": (_INT, [_P, _P, _I, _P, _P, _P, _P]),
+    "agx_simba_choose_plan": (_INT, [_P, _I, _P]),
+    "agx_simba_split_workspace_bytes": (_SZ, [_P, _I, _P, _INT]),
+    "agx_simba_forward_split": (_INT, [_P, _P, _I, _P, _P, _P]),
+    "agx_simba_backward_split": (_INT, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "agx_conv2d_forward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _INT, _P, _P]),
     "agx_conv2d_wgrad_workspace_bytes": (_SZ, [_P]),
     "agx_conv2d_backward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _P, _P, _P, _P, _INT, _P, _P]),

@@ -10,18 +10,29 @@ Same constructor, module names (``{name}_linear_layer_input``,
 ``{name}_activation_output``) and initialisation calls in the reference's
 order, so a seeded build has the reference's weights bit for bit.
 
-``simba_encoder(module, x)`` runs the whole encoder in blocks + 2 launches
-forward and blocks + 2 backward; the parameters stay the modules' own
+``simba_encoder(module, x, plan=None)`` runs the whole encoder in blocks + 2
+launches forward and blocks + 2 backward; the parameters stay the modules' own
 tensors and gradients come back through autograd.  It applies to f32 CUDA
 tensors of 1..1024 rows, widths (inputs, hidden, outputs) up to 512, an
 inner width scale_factor * hidden up to 2048, 1..8 blocks and an output
 activation of None / Identity / ReLU, on modules without hooks; anything else
 keeps the torch modules.
 
-``EvolvableSimBa.forward`` takes it where it was measured faster than the
-torch modules (at most 256 rows and scale_factor * hidden^2 up to
-4 * 224^2; rows are the kernels' only split, so wider encoders and larger
-batches leave most of the device idle).  AGX_SIMBA=1 takes it wherever it
+A plan (S, R, Q) splits a block's launches beyond their 16-row tiles: S inner
+slices, R row tiles per workgroup, Q row ranges of the dW role, the partial
+tiles summed in a fixed order by the last workgroup to arrive
+(include/agx_simba.h).  ``plan=None`` takes agx_simba_choose_plan's: (1, 1, 1),
+the whole kernels, for at most 256 rows and scale_factor * hidden^2 up to
+4 * 224^2, and the fastest plan of the sweep in DESIGN 4.12 elsewhere.
+AGX_SIMBA_SPLIT=0 makes that choice (1, 1, 1) everywhere (A/B runs); a tuple
+forces a plan and an illegal one raises ValueError.
+
+``EvolvableSimBa.forward`` takes the fused path where it was measured faster
+than the torch modules: at most 256 rows and scale_factor *
+hidden^2 up to 4 * 224^2 on the whole kernels, and at most 64 rows up to
+4 * 256^2 on the split ones.  Elsewhere the split kernels are 2 to 3.4 times
+faster than the whole ones and still 1.2 to 4.9 times slower than torch, so
+those shapes stay with torch.  AGX_SIMBA=1 takes the fused path wherever it
 applies, AGX_SIMBA=0 never (the torch encoder, for A/B checks)."""
 
 from __future__ import annotations
@@ -44,6 +55,8 @@ from .mlp import get_activation, preserve_parameters
 
 _MAX_BLOCKS, _MAX_ROWS, _MAX_WIDTH, _MAX_INNER = 8, 1024, 512, 2048
 _AUTO_MAX_ROWS, _AUTO_MAX_WORK = 256, 4 * 224 * 224  # forward()'s own bounds: rows, scale_factor * hidden^2
+_AUTO_SPLIT_MAX_ROWS, _AUTO_SPLIT_MAX_WORK = 64, 4 * 256 * 256  # and where the split plans were measured faster
+_COUNTER_BYTES = 1024  # AGX_SIMBA_COUNTER_BYTES
 _ACTS = {"Identity": 0, "ReLU": 1}
 _BLOCK_IN = ("ln_g", "ln_b", "w1", "b1", "w2", "b2")
 _TOP_IN = ("w_in", "b_in", "ln_g", "ln_b", "w_out", "b_out")
@@ -53,6 +66,13 @@ class AgxSimbaBlock(ctypes.Structure):
     """Mirror of ``agx_simba_block`` (include/agx_simba.h)."""
 
     _fields_ = [(n, ctypes.c_void_p) for n in _BLOCK_IN] + [("g_" + n, ctypes.c_void_p) for n in _BLOCK_IN]
+
+
+class AgxSimbaPlan(ctypes.Structure):
+    """Mirror of ``agx_simba_plan`` (include/agx_simba.h): inner slices S, row tiles per workgroup R,
+    role-W row ranges Q."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("slices", "row_tiles", "w_parts")]
 
 
 class AgxSimbaDesc(ctypes.Structure):
@@ -212,7 +232,11 @@ def _faster(module: EvolvableSimBa, rows: int) -> bool:
     """The shapes at which the fused path was measured faster, unless AGX_SIMBA=1 asks for it everywhere."""
     if os.environ.get("AGX_SIMBA") == "1":
         return True
-    return rows <= _AUTO_MAX_ROWS and module.scale_factor * module.hidden_size ** 2 <= _AUTO_MAX_WORK
+    work = module.scale_factor * module.hidden_size ** 2
+    if rows <= _AUTO_MAX_ROWS and work <= _AUTO_MAX_WORK:
+        return True
+    return (rows <= _AUTO_SPLIT_MAX_ROWS and work <= _AUTO_SPLIT_MAX_WORK and
+            os.environ.get("AGX_SIMBA_SPLIT") != "0")
 
 
 def _plan(module: EvolvableSimBa):
@@ -260,18 +284,27 @@ def _desc(meta, ts, acts, stats, out, grads=None) -> AgxSimbaDesc:
 
 
 class SimbaFn(torch.autograd.Function):
-    """(x [B, in], the encoder's parameters...) -> [B, out]."""
+    """(x [B, in], the encoder's parameters...) -> [B, out].  ``plan``: None for agx_simba_forward /
+    _backward, an (S, R, Q) tuple for the split entry points; the backward runs under the forward's plan."""
 
     @staticmethod
-    def forward(ctx, meta, x, *ts):
+    def forward(ctx, meta, plan, x, *ts):
         x = x.contiguous()
         B, (_, H, _, blocks, nout, _, _) = x.shape[0], meta
         acts = torch.empty(blocks + 1, B, H, dtype=torch.float32, device=x.device)
         stats = torch.empty(blocks + 1, B, 2, dtype=torch.float32, device=x.device)
         out = torch.empty(B, nout, dtype=torch.float32, device=x.device)
         d = _desc(meta, ts, acts, stats, out)
-        _lib.call("agx_simba_forward", ctypes.byref(d), x.data_ptr(), B, _lib.stream())
-        ctx.meta = meta
+        ctx.ws = None
+        if plan is None:
+            _lib.call("agx_simba_forward", ctypes.byref(d), x.data_ptr(), B, _lib.stream())
+        else:
+            # one workspace for both passes when a backward will follow: the counters are zero again after each
+            ws = _split_workspace(d, B, plan, any(ctx.needs_input_grad), x.device)
+            _lib.call("agx_simba_forward_split", ctypes.byref(d), x.data_ptr(), B, ctypes.byref(AgxSimbaPlan(*plan)),
+                      ws.data_ptr(), _lib.stream())
+            ctx.ws = ws if any(ctx.needs_input_grad) else None
+        ctx.meta, ctx.plan = meta, plan
         ctx.save_for_backward(x, acts, stats, out, *ts)
         return out
 
@@ -282,22 +315,58 @@ class SimbaFn(torch.autograd.Function):
         B = x.shape[0]
         g = g.to(torch.float32).contiguous()
         grads = [torch.empty_like(t) for t in ts]
-        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        gx = torch.empty_like(x) if ctx.needs_input_grad[2] else None
         d = _desc(ctx.meta, ts, acts, stats, out, grads)
-        nws = _lib.load().agx_simba_workspace_bytes(ctypes.byref(d), B)
-        ws = torch.empty(max(16, nws), dtype=torch.uint8, device=x.device)
-        _lib.call("agx_simba_backward", ctypes.byref(d), x.data_ptr(), B, g.data_ptr(), _lib.ptr(gx), ws.data_ptr(),
-                  _lib.stream())
-        return (None, gx, *[gr if ctx.needs_input_grad[2 + i] else None for i, gr in enumerate(grads)])
+        if ctx.plan is None:
+            nws = _lib.load().agx_simba_workspace_bytes(ctypes.byref(d), B)
+            ws = torch.empty(max(16, nws), dtype=torch.uint8, device=x.device)
+            _lib.call("agx_simba_backward", ctypes.byref(d), x.data_ptr(), B, g.data_ptr(), _lib.ptr(gx),
+                      ws.data_ptr(), _lib.stream())
+        else:
+            ws = ctx.ws if ctx.ws is not None else _split_workspace(d, B, ctx.plan, True, x.device)
+            _lib.call("agx_simba_backward_split", ctypes.byref(d), x.data_ptr(), B, g.data_ptr(), _lib.ptr(gx),
+                      ctypes.byref(AgxSimbaPlan(*ctx.plan)), ws.data_ptr(), _lib.stream())
+        return (None, None, gx, *[gr if ctx.needs_input_grad[3 + i] else None for i, gr in enumerate(grads)])
 
 
-def simba_encoder(module: EvolvableSimBa, x: torch.Tensor):
-    """``module.model(x)`` on the fused kernels, or None where they do not apply."""
+def _split_workspace(d: AgxSimbaDesc, B: int, plan, backward: bool, device) -> torch.Tensor:
+    """The split entry points' workspace with its counter region zeroed (by a fill kernel, so that it can
+    be captured); an illegal plan raises with the library's reason."""
+    n = _lib.load().agx_simba_split_workspace_bytes(ctypes.byref(d), B, ctypes.byref(AgxSimbaPlan(*plan)),
+                                                    int(backward))
+    if n == 0:
+        raise ValueError(f"simba plan {tuple(plan)}: {_lib.load().agx_last_error().decode(errors='replace')}")
+    ws = torch.empty(n, dtype=torch.uint8, device=device)
+    ws[:_COUNTER_BYTES].zero_()
+    return ws
+
+
+def choose_plan(meta, B: int):
+    """The library's plan for this shape as (S, R, Q); (1, 1, 1) under AGX_SIMBA_SPLIT=0."""
+    if os.environ.get("AGX_SIMBA_SPLIT") == "0":
+        return (1, 1, 1)
+    d, p = AgxSimbaDesc(), AgxSimbaPlan()
+    d.in_, d.H, d.scale, d.blocks, d.out_dim, d.act, d.eps = meta
+    _lib.check(_lib.load().agx_simba_choose_plan(ctypes.byref(d), B, ctypes.byref(p)), "agx_simba_choose_plan")
+    return (p.slices, p.row_tiles, p.w_parts)
+
+
+def simba_encoder(module: EvolvableSimBa, x: torch.Tensor, plan=None):
+    """``module.model(x)`` on the fused kernels, or None where they do not apply.  ``plan``: None for the
+    library's choice, or (S, R, Q) to force the split kernels' plan (include/agx_simba.h); an illegal one
+    raises ValueError."""
     if (not enabled() or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or
             x.dim() != 2 or not 1 <= x.shape[0] <= _MAX_ROWS):
         return None
-    plan = _plan(module)
-    if plan is None or plan[0][0] != x.shape[1] or hooked(module):
+    found = _plan(module)
+    if found is None or found[0][0] != x.shape[1] or hooked(module):
         return None
-    meta, ts = plan
-    return SimbaFn.apply(meta, x, *ts)
+    meta, ts = found
+    if plan is None:
+        plan = choose_plan(meta, x.shape[0])
+        plan = None if plan == (1, 1, 1) else plan  # the whole kernels' own entry points
+    else:
+        plan = tuple(int(v) for v in plan)
+        if len(plan) != 3:
+            raise ValueError(f"simba plan {plan}: not (S, R, Q)")
+    return SimbaFn.apply(meta, plan, x, *ts)

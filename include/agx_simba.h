@@ -66,6 +66,53 @@ size_t agx_simba_workspace_bytes(const agx_simba_desc *desc, int64_t B);
 int agx_simba_backward(const agx_simba_desc *desc, const float *x, int64_t B, const float *grad_out, float *grad_x,
                        void *workspace, void *stream);
 
+/* ---- split plans: wide encoders and large batches --------------------------
+ * The kernels above split a block's work by 16-row tiles only.  A plan
+ * (slices S, row_tiles R, w_parts Q) splits it further; (1, 1, 1) is exactly
+ * the kernels above and their bits.
+ *   S, 1..16 and at most ceil(scale*H / 16): the 16-unit tiles of the inner
+ *      dimension are dealt to S slices in order, the extra tiles to the
+ *      first slices.  The block forward and the backward's dx role run on a
+ *      (row groups x S) grid, each workgroup walking its slice only.
+ *   R, 1, 2 or 4: row tiles a workgroup stages; every weight operand it loads
+ *      feeds R MFMA accumulators.  Bounded by LDS (160 KB): the forward
+ *      stages [16R][H+4] + [16R][132] floats, the backward two [16R][H+4].
+ *   Q, 1..4 and at most ceil(B / 16): the row tiles are dealt to Q workgroups
+ *      per 32 inner units in the backward's dW role.
+ * Partial tiles go to the workspace; the workgroup of a row group (of a unit
+ * range) that arrives last, by a ticket from an integer counter, sums them
+ * in slice (range) order and finishes the output, so the bits do not depend
+ * on the arrival order.  No workgroup waits for another and there are no
+ * floating-point atomics.  The counters are the first
+ * AGX_SIMBA_COUNTER_BYTES of the workspace: zero on entry, zero on return. */
+#define AGX_SIMBA_MAX_SLICES 16
+#define AGX_SIMBA_MAX_W_PARTS 4
+#define AGX_SIMBA_COUNTER_BYTES 1024
+
+typedef struct agx_simba_plan {
+    int32_t slices, row_tiles, w_parts;
+} agx_simba_plan;
+
+/* Host only: the plan the library would run at this shape (from the sweep of
+ * tools/simba_time.py; (1, 1, 1) for B <= 256 and scale*H*H <= 4*224*224).
+ * Reads desc->H and desc->scale only. */
+int agx_simba_choose_plan(const agx_simba_desc *desc, int64_t B, agx_simba_plan *plan);
+
+/* Bytes of workspace of the split entry points, I = scale*H, or 0 for a plan
+ * outside the limits (agx_last_error says why):
+ *   AGX_SIMBA_COUNTER_BYTES + 4 * ((S > 1 ? S*B*H : 0)
+ *     + (backward ? 2*B*H + 4*ceil(B/16)*H + (Q > 1 ? Q*(2*I*H + I) : 0) : 0))
+ * Reads desc->H and desc->scale only. */
+size_t agx_simba_split_workspace_bytes(const agx_simba_desc *desc, int64_t B, const agx_simba_plan *plan,
+                                       int backward);
+
+/* agx_simba_forward / agx_simba_backward under a plan.  The plan is checked
+ * before anything else and before any HIP call. */
+int agx_simba_forward_split(const agx_simba_desc *desc, const float *x, int64_t B, const agx_simba_plan *plan,
+                            void *workspace, void *stream);
+int agx_simba_backward_split(const agx_simba_desc *desc, const float *x, int64_t B, const float *grad_out,
+                             float *grad_x, const agx_simba_plan *plan, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
