@@ -29,7 +29,9 @@ CFLAGS = [
 # split kernels (forward 80 / 104 / 152 VGPRs for R = 1 / 2 / 4, backward 213, no scratch) and
 # tests/test_simba_gpu.py, tests/test_simba_split_gpu.py.  The flag is a cc1-level override; if a compiler drops the feature name the
 # build fails loudly here rather than changing code generation silently.
-EXTRA_CFLAGS = {"simba.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# lstm.hip: the same flag for the same reasons; its resource report is in DESIGN 4.13.
+EXTRA_CFLAGS = {"simba.hip": _NO_PACKED_FP32, "lstm.hip": _NO_PACKED_FP32}
 
 
 def _needs(obj: str, src: str, deps: list[str]) -> bool:

@@ -30,7 +30,7 @@ class AgxMultiHead(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
-# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h) one-to-one
+# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h, agx_lstm.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -169,6 +169,11 @@ SIGNATURES = {
     "agx_simba_split_workspace_bytes": (_SZ, [_P, _I, _P, _INT]),
     "agx_simba_forward_split": (_INT, [_P, _P, _I, _P, _P, _P]),
     "agx_simba_backward_split": (_INT, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    # include/agx_lstm.h: stacked LSTM sequences (descriptor: modules/lstm.py AgxLstmDesc)
+    "agx_lstm_saved_bytes": (_SZ, [_P, _I, _I]),
+    "agx_lstm_workspace_bytes": (_SZ, [_P, _I, _I]),
+    "agx_lstm_forward": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "agx_lstm_backward": (_INT, [_P, _P, _P, _P, _I, _I] + [_P] * 10),
     "agx_conv2d_forward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _INT, _P, _P]),
     "agx_conv2d_wgrad_workspace_bytes": (_SZ, [_P]),
     "agx_conv2d_backward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _P, _P, _P, _P, _INT, _P, _P]),

@@ -106,7 +106,7 @@ class _NeuralBandit(EvolvableAgentMixin, C.TorchCheckpointMixin):
         cfg = _net_kwargs(net_config)
         reject_simba(cfg)
         if cfg.get("recurrent"):
-            raise NotImplementedError("recurrent encoders are outside the agx path")
+            raise NotImplementedError("recurrent bandits are the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
         self._image = is_image_space(observation_space)
         if not hasattr(observation_space, "spaces"):  # neural_ucb_bandit.py:141-146: no LayerNorm
             enc = as_config(cfg.get("encoder_config"))

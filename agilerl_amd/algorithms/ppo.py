@@ -218,7 +218,7 @@ class PPO:
                  wrap: bool = True, bptt_sequence_type=None, max_seq_len=None, *, _population=None,
                  _row: int | None = None) -> None:
         if recurrent:
-            raise NotImplementedError("recurrent PPO is outside the agx hot path")
+            raise NotImplementedError("recurrent PPO is the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
         if actor_network is not None or critic_network is not None:
             raise NotImplementedError("custom actor/critic modules: use net_config (MLP) networks")
         self.share_encoders = bool(share_encoders)

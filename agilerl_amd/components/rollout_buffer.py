@@ -40,7 +40,7 @@ class RolloutBuffer:
                  hidden_state_architecture=None, use_gae: bool = True, wrap_at_capacity: bool = False,
                  max_seq_len: int | None = None, bptt_sequence_type=None) -> None:
         if recurrent:
-            raise NotImplementedError("recurrent (BPTT) rollout storage is not on the agx hot path")
+            raise NotImplementedError("recurrent (BPTT) rollout storage is the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
         self.capacity = int(capacity)
         self.observation_space = observation_space
         self.action_space = action_space

@@ -63,5 +63,8 @@ class DeterministicActor(EvolvableNetwork):
             return action
         return (low + (high - low) * ((action - lo) / (hi - lo))).to(low.dtype)
 
-    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+    def forward(self, obs: torch.Tensor, hidden_state=None):
+        if self.recurrent:  # -> (action, next hidden state)
+            latent, hidden_state = self.extract_features(obs, hidden_state=hidden_state)
+            return self.head_net(latent), hidden_state
         return self.head_net(self.extract_features(obs))

@@ -4,8 +4,9 @@ Box observations get EvolvableMLP encoders, image Box spaces (3-D shape,
 utils/evolvable_networks.py:74-84) EvolvableCNN encoders on the HIP conv
 kernels (modules/cnn.py), Dict/Tuple spaces EvolvableMultiInput; ``simba=True``
 swaps a vector observation's encoder for EvolvableSimBa on the fused
-residual-block kernels (modules/simba.py).  Recurrent encoders are outside
-the hot path and raise NotImplementedError.
+residual-block kernels (modules/simba.py), ``recurrent=True`` for
+EvolvableLSTM on the fused sequence kernels (modules/lstm.py); the network
+then takes and returns the hidden state ({encoder_name}_h / _c, [L, B, H]).
 """
 
 from __future__ import annotations
@@ -17,6 +18,7 @@ import torch
 from torch import nn
 
 from ..modules.cnn import EvolvableCNN
+from ..modules.lstm import EvolvableLSTM
 from ..modules.mlp import EvolvableMLP, preserve_parameters
 from ..modules.simba import EvolvableSimBa
 
@@ -36,6 +38,13 @@ def assert_correct_simba_net_config(net_config: dict[str, Any]) -> None:
     assert isinstance(net_config["hidden_size"], (int, np.int64)), "Net config hidden_size must be an integer."
     assert "num_blocks" in net_config, "Net config must contain num_blocks: int."
     assert isinstance(net_config["num_blocks"], int), "Net config num_blocks must be an integer."
+
+
+def assert_correct_lstm_net_config(net_config: dict[str, Any]) -> None:
+    """networks/base.py:92-105."""
+    assert "hidden_state_size" in net_config, "LSTM net config must contain hidden_state_size: int."
+    assert isinstance(net_config["hidden_state_size"], (int, np.int64)), \
+        f"LSTM net config hidden_state_size must be an integer but is {type(net_config['hidden_state_size'])}."
 
 
 def mlp_net_config(hidden_size, **overrides) -> dict[str, Any]:
@@ -112,9 +121,13 @@ class EvolvableNetwork(nn.Module):
                  recurrent: bool = False, device="cpu", random_seed: int | None = None,
                  encoder_name: str = "encoder") -> None:
         super().__init__()
-        if encoder_cls is not None or recurrent:
-            raise NotImplementedError("agx networks build EvolvableMLP / EvolvableSimBa encoders (Box observations)")
+        if encoder_cls is not None:
+            raise NotImplementedError("agx networks build EvolvableMLP / EvolvableSimBa / EvolvableLSTM encoders "
+                                      "(Box observations)")
         multi = hasattr(observation_space, "spaces")
+        if recurrent and (simba or multi or is_image_space(observation_space)):
+            raise NotImplementedError("recurrent agx networks take vector Box observations, without simba")
+        self.recurrent, self.cached_hidden_state = bool(recurrent), None
         if not multi and (not hasattr(observation_space, "shape") or hasattr(observation_space, "n")):
             raise NotImplementedError("agx networks take Box or Dict-of-Box observation spaces")
         assert latent_dim <= max_latent_dim, "Latent dimension must be less than or equal to max latent dimension."
@@ -129,6 +142,7 @@ class EvolvableNetwork(nn.Module):
         if encoder_config is None:  # get_default_encoder_config (utils/evolvable_networks.py:168-216)
             encoder_config = {"output_activation": "ReLU"} if multi else cnn_net_config() if image else \
                 dict(hidden_size=128, num_blocks=2, output_activation="ReLU") if self.simba else \
+                dict(hidden_state_size=128, num_layers=1, output_activation="ReLU") if self.recurrent else \
                 mlp_net_config([64, 64], output_activation="ReLU", output_vanish=False)
         if encoder_config.get("output_activation") is None:  # base.py:226-230
             encoder_config["output_activation"] = encoder_config.get("activation", "ReLU")
@@ -158,6 +172,14 @@ class EvolvableNetwork(nn.Module):
                                           device=device, name=encoder_name, **encoder_config)
             self.encoder.disable_mutations("layer")
             return
+        if self.recurrent:  # EvolvableLSTM encoder (base.py:531-540)
+            assert_correct_lstm_net_config(encoder_config)
+            encoder_config.pop("num_outputs", None)
+            self.encoder_config = encoder_config
+            self.encoder = EvolvableLSTM(input_size=int(np.prod(observation_space.shape)), num_outputs=latent_dim,
+                                         device=device, name=encoder_name, **encoder_config)
+            self.encoder.disable_mutations("layer")
+            return
         # MLP encoders: output LayerNorm follows layer_norm, no output vanish (base.py:547-554)
         encoder_config["output_layernorm"] = encoder_config.get("layer_norm", True)
         encoder_config["output_vanish"] = False
@@ -166,10 +188,26 @@ class EvolvableNetwork(nn.Module):
         self.encoder = EvolvableMLP(num_inputs=int(np.prod(observation_space.shape)), num_outputs=latent_dim,
                                     device=device, name=encoder_name, **encoder_config)
 
-    def extract_features(self, x: torch.Tensor, hidden_state=None) -> torch.Tensor:
+    def extract_features(self, x: torch.Tensor, hidden_state=None):
+        """The latent, or (latent, next hidden state) when a hidden state is given (base.py:311-328)."""
         if self.flatten_obs:
             x = x.flatten(1)
-        return self.encoder(x)
+        if hidden_state is None:
+            return self.encoder(x)
+        return self.encoder(x, hidden_state=hidden_state)
+
+    def initialize_hidden_state(self, batch_size: int = 1) -> dict[str, torch.Tensor]:
+        """Zero states {encoder_name}_h / _c of [L, batch_size, H], built once per batch size and handed out as
+        copies (base.py:414-443)."""
+        if not self.recurrent:
+            raise ValueError("Cannot initialize hidden state for non-recurrent networks.")
+        if not self.cached_hidden_state or self.cached_hidden_state_batch_size != batch_size:
+            self.cached_hidden_state_batch_size = batch_size
+            self.cached_hidden_state = {
+                f"{self.encoder.name}_{k}": torch.zeros(tuple(batch_size if d == -1 else d for d in shape),
+                                                        device=self.device)
+                for k, shape in self.encoder.hidden_state_architecture.items()}
+        return {k: v.clone() for k, v in self.cached_hidden_state.items()}
 
     def forward_head(self, latent: torch.Tensor, *args, **kwargs) -> torch.Tensor:
         return self.head_net(latent, *args, **kwargs)
@@ -190,7 +228,7 @@ class EvolvableNetwork(nn.Module):
     def recreate_encoder(self) -> None:
         """networks/base.py:493-503: the encoder rebuilt for the current latent,
         parameters kept where the shapes overlap."""
-        if isinstance(self.encoder, (EvolvableCNN, EvolvableSimBa)):
+        if isinstance(self.encoder, (EvolvableCNN, EvolvableSimBa, EvolvableLSTM)):
             self.encoder.num_outputs = self.latent_dim
             self.encoder.recreate_network()
             return

@@ -36,7 +36,10 @@ class QNetwork(EvolvableNetwork):
         self.num_actions = flatdim(action_space)
         self.head_net = self.create_mlp(self.latent_dim, self.num_actions, "value", head_config)
 
-    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+    def forward(self, obs: torch.Tensor, hidden_state=None):
+        if self.recurrent:  # -> (Q values, next hidden state)
+            latent, hidden_state = self.extract_features(obs, hidden_state=hidden_state)
+            return self.head_net(latent), hidden_state
         return self.head_net(self.extract_features(obs))
 
 

@@ -3,7 +3,8 @@ a "value" head with one output — the network of the neural bandits, whose
 output ``Linear(H, 1)`` is their exploration layer.  Same module tree and
 state-dict keys as the reference (``encoder.model.encoder_linear_layer_1.
 weight``, ``head_net.model.value_linear_layer_output.weight`` ...).  MLP and
-CNN encoders; ``simba=True`` builds an EvolvableSimBa encoder (networks/base.py), recurrent encoders raise.
+CNN encoders; ``simba=True`` builds an EvolvableSimBa encoder, ``recurrent=True`` an EvolvableLSTM one
+(networks/base.py): ``forward`` then takes the hidden state and returns (value, next hidden state).
 """
 
 from __future__ import annotations
@@ -29,7 +30,10 @@ class ValueNetwork(EvolvableNetwork):
             head_config = mlp_net_config([32], output_activation=None)
         self.head_net = self.create_mlp(self.latent_dim, 1, "value", head_config)
 
-    def forward(self, x: torch.Tensor, hidden_state=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, hidden_state=None):
+        if self.recurrent:
+            latent, hidden_state = self.extract_features(x, hidden_state=hidden_state)
+            return self.head_net(latent), hidden_state
         return self.head_net(self.extract_features(x))
 
     def get_output_dense(self) -> nn.Module:

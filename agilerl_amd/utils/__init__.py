@@ -56,7 +56,7 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
                   max_grad_norm=INIT_HP.get("MAX_GRAD_NORM", 0.5), target_kl=INIT_HP.get("TARGET_KL"),
                   update_epochs=INIT_HP.get("UPDATE_EPOCHS", 4))
         if INIT_HP.get("RECURRENT", False):
-            raise NotImplementedError("recurrent PPO is outside the agx hot path")
+            raise NotImplementedError("recurrent PPO is the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
         # a Box action space: the Gaussian policy's initial log_std (ppo.py:121, 168)
         algo_kwargs.setdefault("action_std_init", float(INIT_HP.get("ACTION_STD_INIT", 0.0)))
         assert algo_kwargs["action_std_init"] >= 0, "Action standard deviation must be greater than or equal to zero."

@@ -1,0 +1,75 @@
+/* Stacked LSTM sequences (torch.nn.LSTM, batch_first, unidirectional, no
+ * projection; agilerl/modules/lstm.py EvolvableLSTM's `{name}_lstm`):
+ *
+ *   (i, f, g, o) = (sigm, sigm, tanh, sigm)(W_ih x_t + b_ih + W_hh h_{t-1} + b_hh)
+ *   c_t = f * c_{t-1} + i * g,   h_t = o * tanh(c_t)
+ *
+ * fp32 on v_mfma_f32_16x16x4_f32.  One workgroup carries a 16-row tile of the
+ * batch through every layer and every step: c_t stays in registers, h_t in a
+ * double-buffered LDS tile, W_hh in registers for H <= AGX_LSTM_RESIDENT_H.
+ * A row's result does not depend on B, on T or on the row's place in its
+ * tile, so a sequence run in chunks (the state carried through h_n / c_n)
+ * has the bits of the sequence run whole.  The backward is a reverse scan per
+ * layer on the same tiles, then everything without a serial dependency over
+ * all B * T rows at once; no floating-point atomics, every sum in a fixed
+ * order.
+ *
+ * Replaces nn.LSTM's forward and autograd's backward through it; binding:
+ * agilerl_amd/modules/lstm.py. */
+#ifndef AGX_LSTM_H
+#define AGX_LSTM_H
+
+#include "agx.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AGX_LSTM_MAX_LAYERS 4
+#define AGX_LSTM_MAX_HIDDEN 512    /* H: a multiple of 16 in [16, 512] */
+#define AGX_LSTM_MAX_INPUT 512     /* layer 0's input size, any value in [1, 512] */
+#define AGX_LSTM_RESIDENT_H 64     /* W_hh operands live in registers up to here */
+
+/* One layer, nn.LSTM layouts, gate order i, f, g, o along 4H: w_ih [4H][in_k]
+ * (in_0 = in, in_k = H above), w_hh [4H][H], b_ih / b_hh [4H]; g_*: the
+ * backward's outputs of the same shapes (forward: unused). */
+typedef struct agx_lstm_layer {
+    const float *w_ih, *w_hh, *b_ih, *b_hh;
+    float *g_w_ih, *g_w_hh, *g_b_ih, *g_b_hh;
+} agx_lstm_layer;
+
+typedef struct agx_lstm_desc {
+    agx_lstm_layer layer[AGX_LSTM_MAX_LAYERS];
+    int32_t in, H, L;
+} agx_lstm_desc;
+
+/* Bytes of `saved` for B sequences of T steps, N = B * T: per layer the
+ * post-activation gates [N][4H] and c_t [N][H], and below the top layer its
+ * output h_t [N][H]: 4 * N * H * (6 L - 1).  0 for a descriptor outside the
+ * limits (agx_last_error says why). */
+size_t agx_lstm_saved_bytes(const agx_lstm_desc *desc, int64_t B, int64_t T);
+
+/* x [B][T][in], h0 / c0 [L][B][H] -> y [B][T][H] (the top layer's h_t), h_n /
+ * c_n [L][B][H].  One launch for the whole stack.  saved == NULL: the no-grad
+ * form, which writes y, h_n and c_n only (the layers below the top pass their
+ * outputs through y in place). */
+int agx_lstm_forward(const agx_lstm_desc *desc, const float *x, const float *h0, const float *c0, int64_t B, int64_t T,
+                     float *y, float *h_n, float *c_n, void *saved, void *stream);
+
+/* Bytes of the backward's workspace: the gate gradients [N][4H] of the layer
+ * at hand and, with L > 1, the gradient [N][H] handed to the layer below. */
+size_t agx_lstm_workspace_bytes(const agx_lstm_desc *desc, int64_t B, int64_t T);
+
+/* gy [B][T][H]; gh_n / gc_n [L][B][H] (NULL: zero); gx [B][T][in], gh0 / gc0
+ * [L][B][H] (NULL: not needed).  `saved` and y are the forward's.  Writes
+ * every g_* of the descriptor, each element once (g_b_ih and g_b_hh get the
+ * same sums).  Three launches per layer. */
+int agx_lstm_backward(const agx_lstm_desc *desc, const float *x, const float *h0, const float *c0, int64_t B, int64_t T,
+                      const float *y, const void *saved, const float *gy, const float *gh_n, const float *gc_n,
+                      float *gx, float *gh0, float *gc0, void *workspace, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* AGX_LSTM_H */
