@@ -30,7 +30,7 @@ class AgxMultiHead(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
-# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h, agx_lstm.h) one-to-one
+# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h, agx_lstm.h, agx_bptt.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -174,6 +174,13 @@ SIGNATURES = {
     "agx_lstm_workspace_bytes": (_SZ, [_P, _I, _I]),
     "agx_lstm_forward": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "agx_lstm_backward": (_INT, [_P, _P, _P, _P, _I, _I] + [_P] * 10),
+    # include/agx_bptt.h: truncated BPTT for recurrent PPO (gather arguments: kernels.py BpttGatherArgs)
+    "agx_bptt_capacity": (_I, [_I, _I]),
+    "agx_bptt_plan_workspace_bytes": (_SZ, [_I]),
+    "agx_bptt_plan": (_INT, [_P, _I, _I, _I, _INT, _P, _P, _P, _P, _P]),
+    "agx_bptt_gather": (_INT, [_P, _P]),
+    "agx_ppo_seq_loss_workspace_bytes": (_SZ, [_I]),
+    "agx_ppo_seq_loss_fwd_bwd": (_INT, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     "agx_conv2d_forward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _INT, _P, _P]),
     "agx_conv2d_wgrad_workspace_bytes": (_SZ, [_P]),
     "agx_conv2d_backward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _P, _P, _P, _P, _INT, _P, _P]),

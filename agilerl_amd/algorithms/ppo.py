@@ -23,9 +23,10 @@ Box observations, ``net_config`` with
 actor head [32], critic head [16] unless ``head_config`` is given,
 ppo.py:286-320 via networks/base.py and networks/actors.py),
 LayerNorm on, shared encoder.  ``get_action`` / ``learn`` / ``test`` keep the
-reference's signatures and return types; recurrent policies,
-squashed Box outputs and custom ``actor_network`` objects raise
-NotImplementedError (outside the hot path).  ``get_action(obs, action_mask)``
+reference's signatures and return types; squashed Box outputs and custom
+``actor_network`` objects raise NotImplementedError (outside the hot path);
+``recurrent=True`` builds the per-agent BPTT agent of
+algorithms/ppo_recurrent.py.  ``get_action(obs, action_mask)``
 applies the reference's legal-action masks (logits of illegal actions ->
 -1e8, ppo.py:529-565); ``target_kl`` stops an agent's epochs early exactly
 as ppo.py:917-918 does, inside the fused learner.
@@ -207,6 +208,15 @@ def spec_from_net_config(observation_space, action_space, net_config: dict | Non
 class PPO:
     algo = "PPO"
 
+    def __new__(cls, *args, recurrent: bool = False, **kwargs):
+        """``recurrent=True`` builds the per-agent BPTT agent (algorithms/ppo_recurrent.py), a PPO beside
+        the population engine."""
+        if recurrent and cls is PPO:
+            from .ppo_recurrent import RecurrentPPO
+
+            cls = RecurrentPPO
+        return super().__new__(cls)
+
     def __init__(self, observation_space, action_space, index: int = 0, hp_config=None,
                  net_config: dict[str, Any] | None = None, batch_size: int = 64, lr: float = 1e-4,
                  learn_step: int = 2048, gamma: float = 0.99, gae_lambda: float = 0.95, mut=None,
@@ -217,8 +227,8 @@ class PPO:
                  rollout_buffer_config=None, recurrent: bool = False, device="cuda", accelerator=None,
                  wrap: bool = True, bptt_sequence_type=None, max_seq_len=None, *, _population=None,
                  _row: int | None = None) -> None:
-        if recurrent:
-            raise NotImplementedError("recurrent PPO is the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
+        if recurrent:  # positional: __new__ dispatches on the keyword
+            raise TypeError("PPO: pass recurrent=True by keyword")
         if actor_network is not None or critic_network is not None:
             raise NotImplementedError("custom actor/critic modules: use net_config (MLP) networks")
         self.share_encoders = bool(share_encoders)

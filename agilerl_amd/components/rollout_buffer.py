@@ -8,8 +8,12 @@ launch, bit-identical to the reference's NumPy loop (f64 carry, NumPy-2
 dtype flow) for f32 ``last_value``.  Fields are plain tensors in a dict
 (``tensordict`` is not a dependency); ``get_tensor_batch`` returns a dict.
 
-Recurrent / BPTT sequence storage (``recurrent=True``) is outside the hot
-path and raises NotImplementedError.
+``recurrent=True`` stores the hidden state each step was taken from, one HBM
+tensor [capacity, num_envs, layers, hidden] per key, and serves truncated
+BPTT (:676-922) from the device: ``prepare_sequence_tensors`` is one
+agx_bptt_plan call (the sequence table; S, L and the sequences' lengths are
+read back once), ``get_minibatch_sequences`` one agx_bptt_gather launch per
+minibatch (include/agx_bptt.h).  Vector Box observations only.
 """
 
 from __future__ import annotations
@@ -39,8 +43,10 @@ class RolloutBuffer:
                  gae_lambda: float = 0.95, gamma: float = 0.99, recurrent: bool = False,
                  hidden_state_architecture=None, use_gae: bool = True, wrap_at_capacity: bool = False,
                  max_seq_len: int | None = None, bptt_sequence_type=None) -> None:
-        if recurrent:
-            raise NotImplementedError("recurrent (BPTT) rollout storage is the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
+        if recurrent and hidden_state_architecture is None:
+            raise ValueError("hidden_state_architecture must be provided if recurrent=True")
+        if recurrent and len(_obs_shape(observation_space)) != 1:
+            raise NotImplementedError("recurrent agx rollout storage takes vector Box observations")
         self.capacity = int(capacity)
         self.observation_space = observation_space
         self.action_space = action_space
@@ -56,6 +62,8 @@ class RolloutBuffer:
         self.bptt_sequence_type = bptt_sequence_type
         self.pos = 0
         self.full = False
+        self.num_sequences = self.max_sequence_length = None
+        self._plan = self._unpadded_slices = None
         self._initialize_buffers()
 
     def _initialize_buffers(self) -> None:
@@ -74,6 +82,10 @@ class RolloutBuffer:
             "returns": torch.zeros((C, N), **f32),
             "episode_starts": torch.zeros((C, N), dtype=torch.bool, device=dev),
         }
+        if self.recurrent:
+            # {key: (layers, num_envs, hidden)} -> [capacity, num_envs, layers, hidden] per key (:203-223)
+            self.buffer["hidden_states"] = {k: torch.zeros((C, N, int(sh[0]), int(sh[2])), **f32)
+                                            for k, sh in self.hidden_state_architecture.items()}
         self._gae_ws = None
 
     # ------------------------------------------------------------------ #
@@ -115,6 +127,10 @@ class RolloutBuffer:
                 self.buffer["action_masks"] = torch.ones((self.capacity, N, m.shape[-1]), dtype=torch.bool,
                                                          device=self.device)
             self.buffer["action_masks"][self.pos].copy_(m)
+        if self.recurrent and hidden_state is not None:  # (layers, num_envs, hidden) -> (num_envs, layers, hidden)
+            for k, h in hidden_state.items():
+                self.buffer["hidden_states"][k][self.pos].copy_(torch.as_tensor(h).permute(1, 0, 2))
+        self._plan = self._unpadded_slices = None
         self.pos += 1
         if self.pos == self.capacity:
             self.full = True
@@ -132,8 +148,25 @@ class RolloutBuffer:
         rew = b["rewards"][:T].reshape(1, T, N)
         done = b["dones"][:T].view(torch.uint8).reshape(1, T, N)
         val = b["values"][:T].reshape(1, T, N)
-        K.gae(rew, done, val, lv, ld, self.gamma, self.gae_lambda, self.use_gae,
-              advantages=b["advantages"][:T].reshape(1, T, N), returns=b["returns"][:T].reshape(1, T, N))
+        out = K.gae(rew, done, val, lv, ld, self.gamma, self.gae_lambda, self.use_gae,
+                    advantages=b["advantages"][:T].reshape(1, T, N), returns=b["returns"][:T].reshape(1, T, N),
+                    with_stats=self.recurrent)
+        # recurrent: the launch's mean / unbiased std of the advantages, for normalize_advantages
+        self._adv_stats = (T, out[2]) if self.recurrent else None
+
+    def normalize_advantages(self) -> None:
+        """(a - mean) / (std + 1e-8) over the filled prefix in place (ppo.py:935-944), from the statistics the
+        GAE launch took: one agx_adv_normalize launch.  Applies once per compute_returns_and_advantages."""
+        stats = getattr(self, "_adv_stats", None)
+        if stats is None:
+            raise ValueError("normalize_advantages() follows compute_returns_and_advantages() on a recurrent buffer")
+        T, st = stats
+        K.adv_normalize_(self.buffer["advantages"][:T], st)
+        self._adv_stats = None
+
+    def _flat_items(self):
+        """The per-step tensors (the nested hidden states are served by get_minibatch_sequences)."""
+        return [(k, v) for k, v in self.buffer.items() if k != "hidden_states"]
 
     def get_tensor_batch(self, batch_size: int | None = None, device=None) -> dict[str, torch.Tensor]:
         target = torch.device(device) if device is not None else self.device
@@ -141,7 +174,7 @@ class RolloutBuffer:
         total = T * self.num_envs
         if total == 0:
             return {}
-        flat = {k: v[:T].reshape(total, *v.shape[2:]) for k, v in self.buffer.items()}
+        flat = {k: v[:T].reshape(total, *v.shape[2:]) for k, v in self._flat_items()}
         if batch_size is not None:
             if batch_size > total:
                 warnings.warn(f"Batch size {batch_size} is larger than buffer_size {total}. Returning all data.",
@@ -156,7 +189,7 @@ class RolloutBuffer:
         total = T * self.num_envs
         if total == 0:
             return {}
-        flat = {k: v[:T].reshape(total, *v.shape[2:]) for k, v in self.buffer.items()}
+        flat = {k: v[:T].reshape(total, *v.shape[2:]) for k, v in self._flat_items()}
         if batch_size is not None and batch_size <= total:
             idx = torch.as_tensor(np.random.choice(total, size=batch_size, replace=False)).to(self.device)
             flat = {k: v.index_select(0, idx) for k, v in flat.items()}
@@ -164,3 +197,59 @@ class RolloutBuffer:
             warnings.warn(f"Batch size {batch_size} is larger than buffer size {total}. Returning all data.",
                           stacklevel=2)
         return {k: v.cpu().numpy() for k, v in flat.items()}
+
+    # ---- truncated BPTT (rollout_buffer.py:676-922) ---------------------------
+    def prepare_sequence_tensors(self, device=None) -> None:
+        """The sequence table of the filled prefix: ``num_sequences``, ``max_sequence_length`` (the longest
+        sequence, as the reference pads to) and ``unpadded_slices``; the padded tensors themselves are built
+        per minibatch.  The caller normalises the advantages first (ppo.py:935-944)."""
+        if not self.recurrent:
+            raise ValueError("prepare_sequence_tensors() is only supported when recurrent=True.")
+        if self.size() == 0:
+            raise ValueError("Attempting to prepare sequences with empty buffer.")
+        T = self.capacity if self.full else self.pos
+        seq, row_offset, meta = K.bptt_plan(self.buffer["dones"][:T], self.max_seq_len, self.bptt_sequence_type)
+        S, L, _rows, _ = (int(x) for x in meta.cpu())  # the one read-back of a learn()
+        self.num_sequences, self.max_sequence_length = S, L
+        self._plan = (T, seq, row_offset, seq[:S, 2].cpu().to(torch.int64))
+        self._unpadded_slices = None
+
+    @property
+    def unpadded_slices(self):
+        """The flat step indices t * num_envs + env of every sequence (:765-775), built on first use."""
+        if self._plan is None:
+            return None
+        if self._unpadded_slices is None:
+            N = self.num_envs
+            self._unpadded_slices = [torch.arange(n) * N + (s * N + e)
+                                     for e, s, n in self._plan[1][:self.num_sequences].cpu().tolist()]
+        return self._unpadded_slices
+
+    def get_minibatch_sequences(self, batch_size: int):
+        """Yields (padded, unpadded) dicts of minibatches of whole sequences (:845-922): padded holds
+        observations / actions / pad_mask (/ action_masks) over [sequences * max_sequence_length] rows and
+        initial_hidden_states {key: [layers, sequences, hidden]} (already in the LSTM's order); unpadded holds
+        log_probs / advantages / values / returns of the valid rows, and their padded rows as valid_row."""
+        if self._plan is None:
+            raise ValueError("Attempting to fetch minibatches before preparing sequences. "
+                             "Call prepare_sequence_tensors() first.")
+        S, L = self.num_sequences, self.max_sequence_length
+        if batch_size > S:
+            warnings.warn(f"Batch size {batch_size} is larger than the number of sequences ({S}), using "
+                          f"batch_size = {S}.", stacklevel=2)
+            batch_size = S
+        T, seq, _row_offset, lens = self._plan
+        order = torch.randperm(S)  # the CPU generator, as the reference draws it
+        ids_dev = order.to(self.device)
+        b = self.buffer
+        for start in range(0, S, batch_size):
+            ids = order[start:start + batch_size]
+            n = lens[ids]
+            local = (torch.cumsum(n, 0) - n).to(torch.int32).to(self.device)
+            out = K.bptt_gather(seq, S, ids_dev[start:start + batch_size], local, int(n.sum()), L,
+                                b["observations"][:T], b["actions"][:T], b["log_probs"][:T], b["advantages"][:T],
+                                b["returns"][:T], b["values"][:T],
+                                mask=b["action_masks"][:T] if "action_masks" in b else None,
+                                hidden={k: v[:T] for k, v in b["hidden_states"].items()})
+            unpadded = {k: out.pop(k) for k in ("log_probs", "advantages", "values", "returns", "valid_row")}
+            yield out, unpadded

@@ -744,3 +744,157 @@ def bandit_select(h, mu, sigma_inv, mask=None, *, bias_one=True, scale=1.0, gamm
               int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(counter), scores.data_ptr(), quad.data_ptr(),
               action.data_ptr(), ws.data_ptr(), _lib.stream())
     return action, scores, quad
+
+
+# --------------------------------------------------------------------------- #
+# Truncated BPTT for recurrent PPO (include/agx_bptt.h)                         #
+# --------------------------------------------------------------------------- #
+BPTT_TYPES = {"chunked": 0, "maximum": 1, "fifty_percent_overlap": 2}  # BPTTSequenceType values -> AGX_BPTT_*
+BPTT_MAX_HIDDEN_KEYS = 4  # AGX_BPTT_MAX_HIDDEN_KEYS
+
+
+def _ptr_fields(*names):
+    return [(n, ctypes.c_void_p) for n in names]
+
+
+class BpttGatherArgs(ctypes.Structure):
+    """Mirror of ``agx_bptt_gather_args`` (include/agx_bptt.h)."""
+
+    _fields_ = (_ptr_fields("seq", "ids", "local_off") +
+                [(n, ctypes.c_int64) for n in ("S", "Bs", "L", "T", "N", "D", "A", "M", "n_valid")] +
+                _ptr_fields("obs", "actions", "mask", "log_probs", "advantages", "returns", "values") +
+                [("hidden", ctypes.c_void_p * BPTT_MAX_HIDDEN_KEYS), ("layers", ctypes.c_int32 * BPTT_MAX_HIDDEN_KEYS),
+                 ("H", ctypes.c_int32 * BPTT_MAX_HIDDEN_KEYS), ("n_hidden", ctypes.c_int32),
+                 ("pad_", ctypes.c_int32)] +
+                _ptr_fields("obs_out", "act_out", "mask_out", "pad_mask") +
+                [("hidden_out", ctypes.c_void_p * BPTT_MAX_HIDDEN_KEYS)] +
+                _ptr_fields("old_logp", "adv", "ret", "old_value", "valid_row"))
+
+
+def bptt_sequence_type(sequence_type) -> int:
+    """AGX_BPTT_* of a BPTTSequenceType member, its value or its name (None: CHUNKED, the reference's default)."""
+    if sequence_type is None:
+        return 0
+    key = getattr(sequence_type, "value", sequence_type)
+    if isinstance(key, str) and key.lower() in BPTT_TYPES:
+        return BPTT_TYPES[key.lower()]
+    if isinstance(key, int) and not isinstance(key, bool) and key in BPTT_TYPES.values():
+        return key
+    raise NotImplementedError(f"Received unrecognized sequence type: {sequence_type}")
+
+
+def bptt_plan(dones, max_seq_len=None, sequence_type=None):
+    """agx_bptt_plan on ``dones`` uint8 / bool [T, N] -> (seq int32 [T * N, 3] = (env, first step, length),
+    row_offset int32 [T * N + 1], meta int32 [4] = S, L, rows, 0); the first S table rows are written.  Nothing
+    is read back."""
+    if dones.dtype == torch.bool:
+        dones = dones.view(torch.uint8)
+    _need(dones, "dones", _u8)
+    if dones.dim() != 2 or dones.numel() == 0:
+        raise ValueError(f"dones: expected a non-empty [T, N], got {tuple(dones.shape)}")
+    T, N = dones.shape
+    dev = dones.device
+    cap = _lib.load().agx_bptt_capacity(T, N)
+    seq = torch.empty(cap, 3, dtype=_i32, device=dev)
+    row_offset = torch.empty(cap + 1, dtype=_i32, device=dev)
+    meta = torch.empty(4, dtype=_i32, device=dev)
+    ws = _ws(_lib.load().agx_bptt_plan_workspace_bytes(N), dev)
+    _lib.call("agx_bptt_plan", dones.data_ptr(), T, N, int(max_seq_len or 0), bptt_sequence_type(sequence_type),
+              seq.data_ptr(), row_offset.data_ptr(), meta.data_ptr(), ws.data_ptr(), _lib.stream())
+    return seq, row_offset, meta
+
+
+def bptt_gather(seq, S, ids, local_off, n_valid, L, obs, actions, log_probs, advantages, returns, values, mask=None,
+                hidden=None):
+    """agx_bptt_gather: the minibatch of sequences ``ids`` (int64 [Bs], rows of the table ``seq`` with S entries)
+    padded to L steps.  ``local_off`` int32 [Bs]: the exclusive prefix of the sequences' lengths, ``n_valid``
+    their sum.  obs [T, N, D] / actions [T, N, A] f32, mask uint8 / bool [T, N, M] or None, log_probs /
+    advantages / returns / values [T, N] f32, hidden: {key: [T, N, layers, H]} or None.  -> dict with
+    observations [Bs * L, D], actions [Bs * L, A], action_masks bool [Bs * L, M] (with a mask), pad_mask bool
+    [Bs * L], initial_hidden_states {key: [layers, Bs, H]}, and log_probs / advantages / returns / values
+    [n_valid] with valid_row int64 [n_valid]."""
+    _need(seq, "seq", _i32)
+    _need(ids, "ids", _i64)
+    Bs = ids.numel()
+    _need(local_off, "local_off", _i32, (Bs,))
+    _need(obs, "obs", _f32)
+    _need(actions, "actions", _f32)
+    if obs.dim() != 3 or actions.dim() != 3 or actions.shape[:2] != obs.shape[:2]:
+        raise ValueError("obs [T, N, D] and actions [T, N, A] must share T and N")
+    T, N, D = obs.shape
+    A = actions.shape[2]
+    S, L, n_valid = int(S), int(L), int(n_valid)
+    if not (0 < S <= seq.shape[0] and seq.dim() == 2 and seq.shape[1] == 3):
+        raise ValueError(f"seq: expected [>= {S}, 3], got {tuple(seq.shape)}")
+    if not (Bs >= 1 and 1 <= L <= T and 0 <= n_valid <= Bs * L):
+        raise ValueError(f"bptt_gather: Bs = {Bs}, L = {L} (T = {T}), n_valid = {n_valid}")
+    for t, n in ((log_probs, "log_probs"), (advantages, "advantages"), (returns, "returns"), (values, "values")):
+        _need(t, n, _f32, (T, N))
+    dev = obs.device
+    a = BpttGatherArgs()
+    a.seq, a.ids, a.local_off = seq.data_ptr(), ids.data_ptr(), local_off.data_ptr()
+    a.S, a.Bs, a.L, a.T, a.N, a.D, a.A, a.M, a.n_valid = S, Bs, L, T, N, D, A, 0, n_valid
+    a.obs, a.actions = obs.data_ptr(), actions.data_ptr()
+    a.log_probs, a.advantages = log_probs.data_ptr(), advantages.data_ptr()
+    a.returns, a.values = returns.data_ptr(), values.data_ptr()
+    out = {"observations": torch.empty(Bs * L, D, dtype=_f32, device=dev),
+           "actions": torch.empty(Bs * L, A, dtype=_f32, device=dev),
+           "pad_mask": torch.empty(Bs * L, dtype=torch.bool, device=dev)}
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        _need(mask, "mask", _u8)
+        if mask.dim() != 3 or mask.shape[:2] != (T, N):
+            raise ValueError(f"mask: expected [{T}, {N}, M], got {tuple(mask.shape)}")
+        a.M, a.mask = mask.shape[2], mask.data_ptr()
+        out["action_masks"] = torch.empty(Bs * L, a.M, dtype=torch.bool, device=dev)
+        a.mask_out = out["action_masks"].data_ptr()
+    hidden = hidden or {}
+    if len(hidden) > BPTT_MAX_HIDDEN_KEYS:
+        raise ValueError(f"bptt_gather: at most {BPTT_MAX_HIDDEN_KEYS} hidden-state keys (got {len(hidden)})")
+    out["initial_hidden_states"] = {}
+    for q, (key, h) in enumerate(hidden.items()):
+        _need(h, f"hidden[{key}]", _f32)
+        if h.dim() != 4 or h.shape[:2] != (T, N):
+            raise ValueError(f"hidden[{key}]: expected [{T}, {N}, layers, H], got {tuple(h.shape)}")
+        o = out["initial_hidden_states"][key] = torch.empty(h.shape[2], Bs, h.shape[3], dtype=_f32, device=dev)
+        a.hidden[q], a.layers[q], a.H[q], a.hidden_out[q] = h.data_ptr(), h.shape[2], h.shape[3], o.data_ptr()
+    a.n_hidden = len(hidden)
+    for k in ("log_probs", "advantages", "returns", "values"):
+        out[k] = torch.empty(n_valid, dtype=_f32, device=dev)
+    out["valid_row"] = torch.empty(n_valid, dtype=_i64, device=dev)
+    a.obs_out, a.act_out, a.pad_mask = out["observations"].data_ptr(), out["actions"].data_ptr(), \
+        out["pad_mask"].data_ptr()
+    a.old_logp, a.adv, a.ret, a.old_value = (out[k].data_ptr() for k in ("log_probs", "advantages", "returns",
+                                                                           "values"))
+    a.valid_row = out["valid_row"].data_ptr()
+    _lib.call("agx_bptt_gather", ctypes.byref(a), _lib.stream())
+    return out
+
+
+def ppo_seq_loss_fwd_bwd(logp, value, entropy, valid_row, old_logp, adv, ret, old_value, clip_coef=0.2, vf_coef=0.5,
+                         ent_coef=0.01):
+    """agx_ppo_seq_loss_fwd_bwd: logp / value / entropy f32 [rows] over every padded row; valid_row int64
+    [n_valid], strictly ascending, and old_logp / adv / ret / old_value f32 [n_valid] of those rows.
+    -> (g_logp, g_value, g_entropy [rows], zero on pad rows; stats f32 [8])."""
+    rows = logp.numel()
+    for t, n in ((logp, "logp"), (value, "value"), (entropy, "entropy")):
+        _need(t, n, _f32)
+        if t.numel() != rows:
+            raise ValueError(f"{n}: expected {rows} elements")
+    _need(valid_row, "valid_row", _i64)
+    n_valid = valid_row.numel()
+    if not 1 <= n_valid <= rows:
+        raise ValueError(f"valid_row: {n_valid} valid rows of {rows}")
+    for t, n in ((old_logp, "old_logp"), (adv, "adv"), (ret, "ret"), (old_value, "old_value")):
+        _need(t, n, _f32)
+        if t.numel() != n_valid:
+            raise ValueError(f"{n}: expected {n_valid} elements")
+    out = tuple(torch.empty_like(logp) for _ in range(3))
+    stats = torch.empty(8, dtype=_f32, device=logp.device)
+    ws = _ws(_lib.load().agx_ppo_seq_loss_workspace_bytes(rows), logp.device)
+    _lib.call("agx_ppo_seq_loss_fwd_bwd", logp.data_ptr(), value.data_ptr(), entropy.data_ptr(), rows,
+              valid_row.data_ptr(), n_valid, old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+              old_value.data_ptr(), float(clip_coef), float(vf_coef), float(ent_coef), out[0].data_ptr(),
+              out[1].data_ptr(), out[2].data_ptr(), stats.data_ptr(), ws.data_ptr(), _lib.stream())
+    return out[0], out[1], out[2], stats

@@ -1,7 +1,7 @@
-from .actors import DeterministicActor
+from .actors import DeterministicActor, StochasticActor
 from .base import EvolvableNetwork
 from .q_networks import ContinuousQNetwork, DuelingDistributionalMLP, QNetwork, RainbowQNetwork
 from .value_networks import ValueNetwork
 
 __all__ = ["EvolvableNetwork", "QNetwork", "RainbowQNetwork", "DuelingDistributionalMLP", "ContinuousQNetwork",
-           "DeterministicActor", "ValueNetwork"]
+           "DeterministicActor", "StochasticActor", "ValueNetwork"]

@@ -68,3 +68,91 @@ class DeterministicActor(EvolvableNetwork):
             latent, hidden_state = self.extract_features(obs, hidden_state=hidden_state)
             return self.head_net(latent), hidden_state
         return self.head_net(self.extract_features(obs))
+
+
+class EvolvableDistribution(torch.nn.Module):
+    """The head of a ``StochasticActor`` (agilerl/networks/distributions.py:110-342) for Discrete and Box
+    action spaces: the MLP as ``_wrapped`` and, for Box, the learned ``log_std`` [1, A] (the reference's
+    state-dict names).  ``forward`` keeps the masked logits for ``log_prob``; sampling is torch ops."""
+
+    def __init__(self, action_space, network, action_std_init: float = 0.0, device="cpu") -> None:
+        super().__init__()
+        self._wrapped, self.action_space, self.device = network, action_space, device
+        self.discrete = hasattr(action_space, "n")
+        self.logits = None
+        if not self.discrete:
+            self.log_std = torch.nn.Parameter(torch.ones(1, flatdim(action_space), device=device) * action_std_init)
+
+    @property
+    def net_config(self):
+        return self._wrapped.net_config
+
+    def __deepcopy__(self, memo):
+        """A copy without the last forward's logits (a graph tensor cannot be deep-copied)."""
+        import copy
+
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        new.__dict__.update(copy.deepcopy({**self.__dict__, "logits": None}, memo))
+        return new
+
+    def log_prob(self, action: torch.Tensor) -> torch.Tensor:
+        from ..population.nets import categorical, gaussian
+
+        if self.logits is None:
+            raise ValueError("Distribution not initialized. Call forward first.")
+        if self.discrete:
+            return categorical(self.logits)[0].gather(-1, action.long().reshape(-1, 1)).squeeze(-1)
+        return gaussian(self.logits, self.log_std, action)[0]
+
+    def forward(self, latent: torch.Tensor, action_mask=None, sample: bool = True):
+        """-> (action, log_prob, entropy); action and log_prob are None without ``sample``."""
+        from ..population.nets import categorical, gaussian
+
+        logits = self._wrapped(latent)
+        if action_mask is not None:  # distributions.py:16-28: illegal logits -> -1e8
+            mask = torch.as_tensor(action_mask, device=logits.device).bool().view(logits.shape)
+            logits = torch.where(mask, logits, torch.full_like(logits, -1e8))
+        self.logits = logits
+        if self.discrete:
+            entropy = categorical(logits)[1]
+            action = torch.multinomial(torch.softmax(logits, dim=-1), 1).squeeze(-1) if sample else None
+        else:
+            entropy = gaussian(logits, self.log_std, logits)[1]
+            action = logits + torch.exp(self.log_std) * torch.randn_like(logits) if sample else None
+        return action, (self.log_prob(action) if sample else None), entropy
+
+
+class StochasticActor(EvolvableNetwork):
+    """``StochasticActor`` (agilerl/networks/actors.py:214-425) over Discrete (categorical logits) and 1-D Box
+    (mean, learned log_std) action spaces, for recurrent PPO: an encoder, the MLP head "actor" and its
+    distribution.  ``squash_output`` is not supported."""
+
+    def __init__(self, observation_space, action_space, encoder_cls=None, encoder_config=None, head_config=None,
+                 action_std_init: float = 0.0, squash_output: bool = False, min_latent_dim: int = 8,
+                 max_latent_dim: int = 128, latent_dim: int = 32, simba: bool = False, recurrent: bool = False,
+                 device="cpu", random_seed: int | None = None, encoder_name: str = "encoder") -> None:
+        super().__init__(observation_space, encoder_cls=encoder_cls, encoder_config=encoder_config,
+                         action_space=action_space, min_latent_dim=min_latent_dim, max_latent_dim=max_latent_dim,
+                         latent_dim=latent_dim, simba=simba, recurrent=recurrent, device=device,
+                         random_seed=random_seed, encoder_name=encoder_name)
+        if squash_output:
+            raise NotImplementedError("agx StochasticActor: squash_output=True is not supported")
+        if not hasattr(action_space, "n") and (hasattr(action_space, "nvec") or not hasattr(action_space, "low")
+                                               or len(action_space.shape) != 1):
+            raise NotImplementedError("agx StochasticActor: Discrete and 1-D Box action spaces")
+        if type(action_space).__name__ == "MultiBinary":
+            raise NotImplementedError("agx StochasticActor: Discrete and 1-D Box action spaces")
+        head_config = as_config(head_config)
+        if head_config is None:
+            head_config = mlp_net_config([32], output_activation=None)
+        else:
+            head_config["output_activation"] = None
+        self.action_std_init, self.squash_output, self.output_activation = action_std_init, False, None
+        self.output_size = flatdim(action_space)
+        self.head_net = EvolvableDistribution(action_space,
+                                              self.create_mlp(self.latent_dim, self.output_size, "actor", head_config),
+                                              action_std_init=action_std_init, device=device)
+
+    def action_log_prob(self, action: torch.Tensor) -> torch.Tensor:
+        return self.head_net.log_prob(action)

@@ -28,3 +28,52 @@ def collect_rollouts(agent, env, n_steps: int | None = None, last_obs=None, last
     c = int(runner.episodes[agent.row].item())
     scores = [s / c] * c if c else []
     return scores, runner.last_obs, runner.last_done, None, None
+
+
+def collect_rollouts_recurrent(agent, env, n_steps: int | None = None, last_obs=None, last_done=None,
+                               last_scores=None, last_info=None, **_kwargs):
+    """``collect_rollouts_recurrent`` (on_policy.py:23-203, 227-245) for ``PPO(recurrent=True)``: each step's
+    hidden state is stored before the step is taken, and goes back to the initial state where the step ended an
+    episode.  -> (completed episode scores, obs, done, scores, info) for the caller's next call."""
+    import numpy as np
+    import torch
+
+    from .algorithms.ppo_recurrent import reset_hidden_state
+
+    if last_obs is None and last_done is None and last_scores is None and last_info is None:
+        obs, info = env.reset()
+        scores, done = np.zeros(agent.num_envs), np.zeros(agent.num_envs)
+        agent.hidden_state = agent.get_initial_hidden_state(agent.num_envs)
+    else:
+        obs, done, scores, info = last_obs, last_done, last_scores, last_info
+    info = info if isinstance(info, dict) else {}
+    n_steps = n_steps or -(agent.learn_step // -agent.num_envs)
+    buf = agent.rollout_buffer
+    buf.reset()
+    box = not hasattr(agent.action_space, "n")
+    completed = []
+    term = np.zeros(agent.num_envs, dtype=bool)
+    for _ in range(n_steps):
+        stored = agent.hidden_state
+        mask = info.get("action_mask")
+        action, log_prob, _, value, agent.hidden_state = agent.get_action(obs, action_mask=mask, hidden_state=stored)
+        env_action = np.clip(action, agent.action_space.low, agent.action_space.high) if box else action
+        next_obs, reward, term, trunc, next_info = env.step(env_action)
+        ended = np.atleast_1d(np.logical_or(term, trunc))
+        reward = np.atleast_1d(reward)
+        buf.add(obs=obs, action=action, reward=reward, done=ended, value=np.atleast_1d(value),
+                log_prob=np.atleast_1d(log_prob), next_obs=next_obs, hidden_state=stored, action_mask=mask)
+        scores += reward
+        done = ended
+        if np.any(ended):
+            reset_hidden_state(agent.hidden_state, agent.get_initial_hidden_state(agent.num_envs), ended)
+        obs, info = next_obs, next_info if isinstance(next_info, dict) else {}
+        for i in np.flatnonzero(ended):
+            completed.append(float(scores[i]))
+            agent.scores.append(float(scores[i]))
+            scores[i] = 0
+    with torch.no_grad():
+        _, _, _, last_value, _ = agent._get_action_and_values(agent.preprocess_observation(obs),
+                                                              hidden_state=agent.hidden_state, sample=False)
+    buf.compute_returns_and_advantages(last_value=last_value, last_done=np.atleast_1d(term))
+    return completed, obs, done, scores, info

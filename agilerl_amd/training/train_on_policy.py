@@ -179,12 +179,59 @@ def _train_with_collector(engine, pop, env, evo_steps: int, collect_fn) -> list:
     return losses
 
 
+def _train_recurrent(env, env_name, algo, pop, max_steps, evo_steps, eval_steps, eval_loop, target, tournament,
+                     mutation, verbose, collect_rollouts_fn):
+    """The reference's per-agent loop (train_on_policy.py:204-373) for ``PPO(recurrent=True)`` agents, which
+    live beside the population engine: agent after agent on the shared env, ``ceil(evo_steps / learn_step)``
+    times collect_rollouts_recurrent + learn, then ``agent.test``.  Single process, no tournament / mutation."""
+    from ..rollouts import collect_rollouts_recurrent
+
+    if not all(getattr(a, "recurrent", False) for a in pop):
+        raise ValueError("recurrent and non-recurrent PPO agents cannot share one population")
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("agx recurrent PPO populations run in a single process")
+    if tournament is not None and mutation is not None:
+        raise NotImplementedError("agx recurrent PPO: tournament selection and mutations are not applied yet "
+                                  "(pass tournament=None, mutation=None)")
+    collect = collect_rollouts_fn or collect_rollouts_recurrent
+    pop_fitnesses: list[list[float]] = []
+    t0 = time.time()
+    while all(agent.steps[-1] < max_steps for agent in pop):
+        losses = []
+        with _Phase("train"):
+            for agent in pop:
+                steps = 0
+                last = {}
+                for _ in range(-(evo_steps // -agent.learn_step)):
+                    out = collect(agent, env, **last)
+                    last = dict(zip(("last_obs", "last_done", "last_scores", "last_info"), out[1:]))
+                    losses.append(agent.learn())
+                    steps += agent.learn_step
+                agent.steps[-1] += steps
+        with _Phase("evaluate"):
+            fitness = [agent.test(env, max_steps=eval_steps, loop=eval_loop) for agent in pop]
+        for agent in pop:
+            agent.steps.append(agent.steps[-1])
+        pop_fitnesses.append(fitness)
+        if verbose:
+            fps = sum(a.steps[-1] for a in pop) / max(time.time() - t0, 1e-9)
+            print(f"--- {env_name} {algo}: steps {[a.steps[-1] for a in pop]}, fitness "
+                  f"{[round(f, 2) for f in fitness]}, mean loss {np.mean(losses):.4f}, {fps:.0f} env-steps/s")
+        if target is not None and np.all(np.greater([np.mean(a.fitness[-10:]) for a in pop], target)) \
+                and len(pop[0].steps) >= 100:
+            break
+    return pop, pop_fitnesses
+
+
 def train_on_policy(env, env_name: str, algo: str, pop, INIT_HP=None, MUT_P=None, swap_channels: bool = False,
                     max_steps: int = 1_000_000, evo_steps: int = 10_000, eval_steps=None, eval_loop: int = 1,
                     target: float | None = None, tournament=None, mutation=None, checkpoint=None,
                     checkpoint_path=None, overwrite_checkpoints: bool = False, save_elite: bool = False,
                     elite_path=None, wb: bool = False, verbose: bool = True, accelerator=None, wandb_api_key=None,
                     wandb_kwargs=None, collect_rollouts_fn=None):
+    if any(getattr(a, "recurrent", False) for a in pop):
+        return _train_recurrent(env, env_name, algo, pop, max_steps, evo_steps, eval_steps, eval_loop, target,
+                                tournament, mutation, verbose, collect_rollouts_fn)
     population = pop[0].population
     user_env = env
     if any(a.population is not population for a in pop):

@@ -55,8 +55,17 @@ def create_population(algo: str, net_config: dict[str, Any] | None, INIT_HP: dic
                   ent_coef=INIT_HP.get("ENT_COEF", 0.01), vf_coef=INIT_HP.get("VF_COEF", 0.5),
                   max_grad_norm=INIT_HP.get("MAX_GRAD_NORM", 0.5), target_kl=INIT_HP.get("TARGET_KL"),
                   update_epochs=INIT_HP.get("UPDATE_EPOCHS", 4))
-        if INIT_HP.get("RECURRENT", False):
-            raise NotImplementedError("recurrent PPO is the follow-up to the EvolvableLSTM encoders (modules/lstm.py)")
+        if INIT_HP.get("RECURRENT", False) or algo_kwargs.get("recurrent", False):
+            # per-agent BPTT agents beside the population engine (algorithms/ppo_recurrent.py)
+            if world > 1:
+                raise NotImplementedError("agx recurrent PPO populations run in a single process")
+            algo_kwargs.setdefault("action_std_init", float(INIT_HP.get("ACTION_STD_INIT", 0.0)))
+            algo_kwargs.setdefault("max_seq_len", INIT_HP.get("MAX_SEQ_LEN"))
+            algo_kwargs.setdefault("bptt_sequence_type", INIT_HP.get("BPTT_SEQUENCE_TYPE"))
+            algo_kwargs.setdefault("share_encoders", INIT_HP.get("SHARE_ENCODERS", True))
+            algo_kwargs["recurrent"] = True
+            return [PPO(observation_space, action_space, index=i, hp_config=hp_config, net_config=net_config,
+                        num_envs=num_envs, device=device, **hp, **algo_kwargs) for i in range(P)]
         # a Box action space: the Gaussian policy's initial log_std (ppo.py:121, 168)
         algo_kwargs.setdefault("action_std_init", float(INIT_HP.get("ACTION_STD_INIT", 0.0)))
         assert algo_kwargs["action_std_init"] >= 0, "Action standard deviation must be greater than or equal to zero."
