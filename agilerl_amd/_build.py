@@ -30,8 +30,9 @@ CFLAGS = [
 # tests/test_simba_gpu.py, tests/test_simba_split_gpu.py.  The flag is a cc1-level override; if a compiler drops the feature name the
 # build fails loudly here rather than changing code generation silently.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# lstm.hip: the same flag for the same reasons; its resource report is in DESIGN 4.13.
-EXTRA_CFLAGS = {"simba.hip": _NO_PACKED_FP32, "lstm.hip": _NO_PACKED_FP32}
+# lstm.hip: the same flag for the same reasons; its resource report is in DESIGN 4.13.  recurrent_policy.hip
+# shares lstm.hip's gate chains (csrc/lstm_gates.h) and must produce their bits: the same flag.
+EXTRA_CFLAGS = {"simba.hip": _NO_PACKED_FP32, "lstm.hip": _NO_PACKED_FP32, "recurrent_policy.hip": _NO_PACKED_FP32}
 
 
 def _needs(obj: str, src: str, deps: list[str]) -> bool:

@@ -12,14 +12,19 @@ minibatch one agx_bptt_gather, the networks over the padded rows, and
 agx_ppo_seq_loss_fwd_bwd (the masked loss with its three gradients, one
 ``autograd.Function``), then the two gradient clips and Adam.
 
-``get_action`` samples with torch ops on the logits: the Philox policy-step
-kernels take MLP layer lists.  ``share_encoders=True``, image / Dict
+``get_action`` samples with torch ops on the logits unless the fused step is
+switched on (``fused_step=True`` or AGX_RECURRENT_STEP=1; AGX_RECURRENT_STEP=0
+always wins): then a policy step, both LSTM encoders, both heads and the draw
+from the Philox streams, is one agx_ppo_act_recurrent launch
+(include/agx_recurrent.h) wherever its limits hold, and the torch modules run
+elsewhere.  The switch is off by default.  ``share_encoders=True``, image / Dict
 observations, MultiDiscrete / MultiBinary actions and ``squash_output`` raise.
 """
 
 from __future__ import annotations
 
 import copy
+import os
 import warnings
 
 import numpy as np
@@ -64,7 +69,8 @@ class RecurrentPPO(PPO):
                  target_kl: float | None = None, normalize_images: bool = True, update_epochs: int = 4,
                  actor_network=None, critic_network=None, share_encoders: bool = True, num_envs: int = 1,
                  use_rollout_buffer: bool = True, rollout_buffer_config=None, recurrent: bool = True, device="cuda",
-                 accelerator=None, wrap: bool = True, bptt_sequence_type=None, max_seq_len=None) -> None:
+                 accelerator=None, wrap: bool = True, bptt_sequence_type=None, max_seq_len=None,
+                 fused_step: bool = False) -> None:
         from ..hpo.registry import MutationRegistry
 
         if not use_rollout_buffer:
@@ -93,6 +99,8 @@ class RecurrentPPO(PPO):
         self.registry = MutationRegistry(hp_config)
         self.scores, self.fitness, self.steps = [], [], [0]
         self.hidden_state = None
+        self.fused_step = bool(fused_step)
+        self._act_seed, self._act_counter = None, 0  # the Philox key of the fused step: drawn on its first call
 
         cfg = dict(as_config(net_config) or {})
         critic_cfg = copy.deepcopy(cfg)
@@ -172,6 +180,26 @@ class RecurrentPPO(PPO):
         values, next_critic = self.critic(obs, hidden_state=critic_h)
         return action, log_prob, entropy, values.squeeze(-1), {**next_actor, **next_critic}
 
+    def fused_step_on(self) -> bool:
+        env = os.environ.get("AGX_RECURRENT_STEP")
+        return env != "0" and (self.fused_step or env == "1")
+
+    def fused_policy_step(self, obs, action_mask=None, hidden_state=None, *, sample: bool = True, reset=None,
+                          out=None, store_hidden=None, store_obs=None):
+        """One agx_ppo_act_recurrent launch over preprocessed ``obs`` (kernels.ppo_act_recurrent's dict), or None
+        with the switch off or where the kernel does not apply.  A sampled step advances the agent's counter."""
+        if not self.fused_step_on() or hidden_state is None or obs.device.type != "cuda":
+            return None
+        if self._act_seed is None:
+            self._act_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        res = K.ppo_act_recurrent(self.actor, self.critic, obs.reshape(obs.shape[0], -1), hidden_state,
+                                  sample=sample, seed=self._act_seed, counter=self._act_counter + 1,
+                                  mask=action_mask, reset=reset, out=out, store_hidden=store_hidden,
+                                  store_obs=store_obs)
+        if res is not None and sample:
+            self._act_counter += 1
+        return res
+
     def evaluate_actions(self, obs, actions, hidden_state=None, action_mask=None):
         """-> (log_prob, entropy, values) of ``actions`` (ppo.py:529-565); with [layers, B, H] states and
         B * L rows of observations the rows are B sequences of L steps."""
@@ -182,6 +210,16 @@ class RecurrentPPO(PPO):
     def get_action(self, obs, action_mask=None, hidden_state=None, *args, **kwargs):
         """-> (action, log_prob, entropy, value, next hidden state) (ppo.py:567-633)."""
         obs = self.preprocess_observation(obs)
+        res = self.fused_policy_step(obs, action_mask, hidden_state)
+        if res is not None:  # one launch, then one read of what it returned
+            host = torch.cat([res["actions"].reshape(-1), res["log_probs"], res["entropy"], res["values"]]).cpu()
+            n = obs.shape[0]
+            action = host[:-3 * n].reshape(n, -1).numpy()
+            action = action[:, 0].astype(np.int64) if self.discrete else action
+            if not self.training and not self.discrete:
+                action = np.clip(action, self.action_space.low, self.action_space.high)
+            log_prob, entropy, values = host[-3 * n:].reshape(3, n).numpy()
+            return action, log_prob, entropy, values, res["hidden"]
         with torch.no_grad():
             action, log_prob, entropy, values, next_hidden = self._get_action_and_values(obs, action_mask,
                                                                                          hidden_state, sample=True)
@@ -189,6 +227,15 @@ class RecurrentPPO(PPO):
         if not self.training and not self.discrete:
             action = np.clip(action, self.action_space.low, self.action_space.high)
         return action, log_prob.cpu().numpy(), entropy.cpu().numpy(), values.cpu().numpy(), next_hidden
+
+    def bootstrap_value(self, obs, hidden_state) -> torch.Tensor:
+        """The value [N] of ``obs`` under ``hidden_state`` without a draw: the rollout's last value."""
+        obs = self.preprocess_observation(obs)
+        res = self.fused_policy_step(obs, None, hidden_state, sample=False)
+        if res is not None:
+            return res["values"]
+        with torch.no_grad():
+            return self._get_action_and_values(obs, hidden_state=hidden_state, sample=False)[3]
 
     # ---- learning ---------------------------------------------------------------
     def bptt_loss(self, padded: dict, unpadded: dict):

@@ -135,6 +135,47 @@ class RolloutBuffer:
         if self.pos == self.capacity:
             self.full = True
 
+    def fused_step(self, agent, obs, action_mask, hidden_state, reset=None):
+        """One fused recurrent policy step (``agent.fused_policy_step``) that writes slot ``pos`` itself: the
+        observation, action, log-prob, value and the hidden state the step was taken from (zeros for the rows
+        flagged in ``reset``).  -> (action, log_prob, value as host arrays, next hidden state), with
+        ``finish_step`` to follow, or None where the kernel does not apply (nothing is written)."""
+        if self.pos == self.capacity:
+            if not self.wrap_at_capacity:
+                raise ValueError(f"Buffer has reached capacity ({self.capacity} transitions) but received more "
+                                 "transitions. Either increase capacity or set wrap_at_capacity=True.")
+            self.pos = 0
+        b, p, N = self.buffer, self.pos, self.num_envs
+        out = {k: b[k][p] for k in ("actions", "log_probs", "values")}
+        res = agent.fused_policy_step(agent.preprocess_observation(obs), action_mask, hidden_state, reset=reset,
+                                      out=out, store_hidden={k: v[p] for k, v in b["hidden_states"].items()},
+                                      store_obs=b["observations"][p])
+        if res is None:
+            return None
+        host = torch.cat([out["actions"].reshape(-1), out["log_probs"], out["values"]]).cpu().numpy()
+        action = host[:-2 * N].reshape(N, -1)
+        action = action[:, 0].astype(np.int64) if hasattr(self.action_space, "n") else action
+        return action, host[-2 * N:-N], host[-N:], res["hidden"]
+
+    def finish_step(self, reward, done, next_obs=None, action_mask=None) -> None:
+        """The host's half of a slot ``fused_step`` wrote: what the env returned, then the slot is taken."""
+        N = self.num_envs
+        self._put("rewards", reward, (N,), torch.float32)
+        self._put("dones", done, (N,), torch.bool)
+        if next_obs is not None:
+            self._put("next_observations", next_obs, (N, *self.buffer["observations"].shape[2:]), torch.float32)
+        self.buffer["episode_starts"][self.pos].zero_()
+        if action_mask is not None:
+            m = torch.as_tensor(action_mask, dtype=torch.bool).reshape(N, -1)
+            if "action_masks" not in self.buffer:
+                self.buffer["action_masks"] = torch.ones((self.capacity, N, m.shape[-1]), dtype=torch.bool,
+                                                         device=self.device)
+            self.buffer["action_masks"][self.pos].copy_(m)
+        self._plan = self._unpadded_slices = None
+        self.pos += 1
+        if self.pos == self.capacity:
+            self.full = True
+
     # ------------------------------------------------------------------ #
     def compute_returns_and_advantages(self, last_value, last_done) -> None:
         """GAE (or Monte-Carlo returns) over the filled prefix, rollout_buffer.py:413-481."""

@@ -1,11 +1,13 @@
 // The per-row math of the diagonal-Gaussian head (include/agx_gauss.h): one
-// dimension's log-prob term, the entropy, and the gradients of the mean and of
-// log_std.  Shared by the loss kernel (gauss_policy.hip) and the Gaussian head
-// of the runtime-shape learner (graph_learner.hip): the same float operations
-// in the same order in both.
+// dimension's log-prob term, the entropy, the gradients of the mean and of
+// log_std, and the step's Philox noise.  Shared by the loss kernel and policy
+// step (gauss_policy.hip), the Gaussian head of the runtime-shape learner
+// (graph_learner.hip) and the recurrent policy step (recurrent_policy.hip):
+// the same float operations in the same order in all of them.
 #pragma once
 
 #include "agx_common.h"
+#include "rollout.h"
 
 namespace agx {
 
@@ -24,6 +26,20 @@ __device__ __forceinline__ float gauss_inv_var(float ls) { return 1.f / expf(2.f
 // entropy of a row from the sum of its A log_std
 __device__ __forceinline__ float gauss_entropy(int A, float ls_sum) {
     return (float)(kGaussEntropy * (double)A) + ls_sum;
+}
+
+// eps of dimension d (agx_gauss.h): words (x, y) (d even) or (z, w) (d odd) of
+// the Philox block of (env, counter ^ (d >> 1) << 56) -> u1, u2 -> Box-Muller.
+// u = fl((w >> 8) + 0.5) 2^-24 as gumbel_score's: in (0, 1], so ln u1 is finite.
+__device__ __forceinline__ float gauss_noise(int d, unsigned long long env, unsigned long long seed,
+                                             unsigned long long counter) {
+    const uint4 rnd = philox(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)counter,
+                                        (unsigned)(counter >> 32) ^ ((unsigned)(d >> 1) << 24)),
+                             make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+    const unsigned w1 = (d & 1) ? rnd.z : rnd.x, w2 = (d & 1) ? rnd.w : rnd.y;
+    const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(w2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
 }
 
 // d log_prob / d mu_d = z / var, times the row's d loss / d log_prob

@@ -14,20 +14,6 @@
 namespace agx {
 namespace {
 
-// eps of dimension d (agx_gauss.h): words (x, y) (d even) or (z, w) (d odd) of
-// the Philox block of (env, counter ^ (d >> 1) << 56) -> u1, u2 -> Box-Muller.
-// u = fl((w >> 8) + 0.5) 2^-24 as gumbel_score's: in (0, 1], so ln u1 is finite.
-__device__ __forceinline__ float gauss_noise(int d, unsigned long long env, unsigned long long seed,
-                                             unsigned long long counter) {
-    const uint4 rnd = philox(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)counter,
-                                        (unsigned)(counter >> 32) ^ ((unsigned)(d >> 1) << 24)),
-                             make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-    const unsigned w1 = (d & 1) ? rnd.z : rnd.x, w2 = (d & 1) ? rnd.w : rnd.y;
-    const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(w2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
-}
-
 // what the Gaussian step writes besides the ActArgs' log_probs / values / entropy
 struct GaussHead {
     long long log_std_off;  // the A log_std floats in the parameter row

@@ -1,0 +1,378 @@
+// The fused policy step of recurrent PPO (include/agx_recurrent.h): LSTM
+// encoder at T = 1, output Linear, MLP head and the action distribution of
+// both networks of an agent in one launch.
+//
+// Grid (ceil(N / 16), 2), 8 waves: workgroup (x, y) takes env rows 16 x ..
+// 16 x + 15 through the actor (y = 0) or the critic (y = 1), so the two
+// encoders run side by side and neither waits on the other: the actor
+// workgroup writes action / log-prob / entropy, the critic workgroup the value.
+//
+// LDS: four slots of 16 rows, each wide enough for the widest tile of the
+// launch (row stride: the tile's 16-rounded width + 4, which spreads the
+// 16-byte A-operand reads of the 16 rows over the banks).
+//   slot 0  the observation tile, zero-padded to 16 columns
+//   slot 1  h_prev of the layer at hand (zeros for rows flagged in `reset`)
+//   slot 2/3  h' of layer l in slot 2 + (l & 1): the A operand of layer l + 1
+//             and, for the top layer, of the output Linear
+// After the LSTM slots 0 and 1 are free and carry the latent and the head
+// activations, ping-pong.
+//
+// LSTM layer: waves split by 16-unit tile as lstm.hip's fwd_kernel (wave w
+// owns tiles w, w + 8, ..).  A tile's four gate accumulators start at b_ih +
+// b_hh, take the input chain and then the h chain through lstm_gates.h with
+// the same A operand, so lane (r, q) ends with all four pre-activations of
+// rows 4q .. 4q + 3, unit 16 tile + r; c_prev comes from global memory into
+// that lane, c' = f c + i g and h' = o tanh(c') stay in registers, h' goes to
+// the LDS tile and both to the next-state outputs.  The accumulation order is
+// fwd_kernel's, so the states have agx_lstm_forward's bits at T = 1 (W_hh
+// register residency is a sequence optimisation: one step reads it once).
+//
+// Dense layers: one 16 x 16 output tile per wave and pass, one accumulator
+// from the bias over k ascending, four 16-deep steps' operands requested ahead
+// of their MFMAs; columns past the width are written as zeros, which is the
+// padding the next layer's A operand needs.  LayerNorm / activation are row
+// passes over the LDS tile, 16 lanes per row (waves 0 .. 3 hold the 16 rows).
+//
+// Epilogue, 16 lanes per row, entries a and a + 16 per lane, with the
+// operation order of the categorical step of graph_rollout.hip and of
+// gauss_policy.hip's gauss_step, on rollout.h's and gauss_head.h's streams.
+#include "../../include/agx_recurrent.h"
+
+#include "agx_common.h"
+#include "gauss_head.h"
+#include "lstm_gates.h"
+#include "rollout.h"
+
+namespace agx {
+namespace {
+
+using lstm::f32x4;
+
+constexpr int kRT = 512;  // threads
+constexpr int kRW = 8;    // waves
+constexpr int kLdsCap = 160 * 1024;
+
+// acc[row][unit] += sum_k arow[k] * wrow[k], k < K ascending.  arow: this lane's row of an LDS tile zero-padded
+// to K16 = the 16-rounded K; wrow: this lane's unit row of W [out][K].  VEC: 16-byte weight loads (K % 4 == 0,
+// W 16-byte aligned), else 4-byte loads; the same k order and bits either way.
+template <bool VEC>
+__device__ __forceinline__ f32x4 chain_row(int K, int q, f32x4 acc, const float *arow, const float *wrow) {
+    const int K16 = (K + 15) & ~15;
+#pragma unroll 1
+    for (int kc = 0; kc < K; kc += 64) {
+        f32x4 a[4], w[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = kc + 16 * s + 4 * q;
+            a[s] = *reinterpret_cast<const f32x4 *>(arow + min(k, K16 - 4));
+            if (VEC) {
+                w[s] = *reinterpret_cast<const f32x4 *>(wrow + min(k, K - 4));
+                if (k >= K) w[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float v = wrow[min(k + j, K - 1)];
+                    w[s][j] = k + j < K ? v : 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (kc + 16 * s < K) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = MFMA(a[s][j], w[s][j], acc);
+            }
+    }
+    return acc;
+}
+
+// Y [16][ldy] = X [16][ldx] W^T + b over the 16-rounded width of F, zeros in the columns past F
+__device__ __forceinline__ void dense(const float *X, int ldx, int K, const float *W, const float *b, int F, float *Y,
+                                      int ldy) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = lane & 15, q = lane >> 4;
+    const bool vec = (K & 3) == 0 && lstm::aligned16(W);
+    for (int tile = wave; tile < ((F + 15) >> 4); tile += kRW) {
+        const int unit = tile * 16 + r, uu = min(unit, F - 1);
+        const float bv = b[uu];
+        f32x4 acc = {bv, bv, bv, bv};
+        const float *wrow = W + (int64_t)uu * K;
+        acc = vec ? chain_row<true>(K, q, acc, X + r * ldx, wrow) : chain_row<false>(K, q, acc, X + r * ldx, wrow);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + unit] = unit < F ? acc[i] : 0.f;
+    }
+}
+
+// LayerNorm (affine lnw / lnb, eps 1e-5; null: none) and the activation over the F columns of every row of
+// Y [16][ld] in place: waves 0 .. 3, 16 lanes per row.  The loops run to the 16-rounded width, so the row
+// reductions see whole DPP rows.
+__device__ __forceinline__ void row_pass(float *Y, int ld, int F, const float *lnw, const float *lnb, int act) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave >= 4 || (!lnw && act == AGX_RECURRENT_ACT_NONE)) return;
+    const int sub = lane & 15, F16 = (F + 15) & ~15;
+    float *y = Y + (4 * wave + (lane >> 4)) * ld;
+    float mean = 0.f, rstd = 1.f;
+    if (lnw) {
+        float s = 0.f;
+        for (int j = sub; j < F16; j += 16) s = j < F ? s + y[j] : s;
+        mean = row_sum(s) * (1.f / (float)F);
+        float vs = 0.f;
+        for (int j = sub; j < F16; j += 16) {
+            const float d = y[j] - mean;
+            vs = j < F ? vs + d * d : vs;
+        }
+        rstd = 1.f / sqrtf(row_sum(vs) / (float)F + 1e-5f);
+    }
+    for (int j = sub; j < F; j += 16) {
+        float x = y[j];
+        if (lnw) x = (x - mean) * rstd * lnw[j] + lnb[j];
+        if (act == AGX_RECURRENT_ACT_RELU) x = relu(x);
+        if (act == AGX_RECURRENT_ACT_TANH) x = tanhf(x);
+        y[j] = x;
+    }
+}
+
+// The categorical step of the 16 rows of logits Y [16][ld]: graph_rollout.hip's graph_sample, the action as a float
+__device__ __forceinline__ void categorical_step(const agx_recurrent_step &s, const float *Y, int ld, int b0) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave >= 4) return;
+    const int sub = lane & 15, rl = 4 * wave + (lane >> 4);
+    const int A = s.A, N = (int)s.N, row = b0 + rl;
+    const bool live = row < N;
+    const int a0 = sub, a1 = sub + 16;
+    float lg0 = a0 < A ? Y[rl * ld + a0] : -3.0e38f;
+    float lg1 = a1 < A ? Y[rl * ld + a1] : -3.0e38f;
+    if (s.mask && live) {
+        const uint8_t *m = s.mask + (size_t)row * A;
+        if (a0 < A && !m[a0]) lg0 = -1.0e8f;
+        if (a1 < A && !m[a1]) lg1 = -1.0e8f;
+    }
+    const float mx = row_max(fmaxf(lg0, lg1));
+    const float lse = mx + logf(row_sum((a0 < A ? expf(lg0 - mx) : 0.f) + (a1 < A ? expf(lg1 - mx) : 0.f)));
+    const float p0 = a0 < A ? expf(lg0 - lse) : 0.f, p1 = a1 < A ? expf(lg1 - lse) : 0.f;
+    const float H = -row_sum((a0 < A ? p0 * logf(p0 + 1e-8f) : 0.f) + (a1 < A ? p1 * logf(p1 + 1e-8f) : 0.f));
+    if (live && sub == 0 && s.entropy) s.entropy[row] = H;
+    if (!s.sample) return;  // uniform
+    const unsigned long long env = stream_env(-1, nullptr, 0, N, live ? row : 0);
+    const float sc0 = a0 < A ? gumbel_score(lg0, a0, env, s.seed, s.counter) : -3.0e38f;
+    const float sc1 = a1 < A ? gumbel_score(lg1, a1, env, s.seed, s.counter) : -3.0e38f;
+    // first maximum over the actions: lane-local (a0 < a1), then the lowest index among the row's maxima
+    const float bl = fmaxf(sc0, sc1);
+    const int il = sc0 >= sc1 ? a0 : a1;
+    const float best = row_max(bl);
+    const int choice = (int)(-row_max(bl == best ? -(float)il : -1.0e9f));
+    const int srcl = (lane & ~15) + (choice & 15);
+    const float c0 = bperm(srcl, lg0), c1 = bperm(srcl, lg1);
+    if (live && sub == 0) {
+        if (s.actions) s.actions[row] = (float)choice;
+        if (s.log_probs) s.log_probs[row] = (choice < 16 ? c0 : c1) - lse;
+    }
+}
+
+// The Gaussian step of the 16 rows of means Y [16][ld]: gauss_policy.hip's gauss_step
+__device__ __forceinline__ void gauss_step(const agx_recurrent_step &s, const float *Y, int ld, int b0) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave >= 4) return;
+    const int sub = lane & 15, rl = 4 * wave + (lane >> 4);
+    const int A = s.A, N = (int)s.N, row = b0 + rl;
+    const bool live = row < N;
+    const int d0 = sub, d1 = sub + 16;
+    const bool on0 = d0 < A, on1 = d1 < A;
+    const float ls0 = on0 ? s.log_std[d0] : 0.f, ls1 = on1 ? s.log_std[d1] : 0.f;
+    const float H = gauss_entropy(A, row_sum(ls0 + ls1));
+    if (live && sub == 0 && s.entropy) s.entropy[row] = H;
+    if (!s.sample) return;  // uniform
+    const float mu0 = on0 ? Y[rl * ld + d0] : 0.f, mu1 = on1 ? Y[rl * ld + d1] : 0.f;
+    const unsigned long long env = stream_env(-1, nullptr, 0, N, live ? row : 0);
+    float a0 = mu0, a1 = mu1;
+    if (on0) a0 = fmaf(expf(ls0), gauss_noise(d0, env, s.seed, s.counter), mu0);
+    if (on1) a1 = fmaf(expf(ls1), gauss_noise(d1, env, s.seed, s.counter), mu1);
+    const float lp = row_sum((on0 ? gauss_logp_term(a0, mu0, ls0) : 0.f) + (on1 ? gauss_logp_term(a1, mu1, ls1) : 0.f));
+    if (!live) return;
+    if (s.actions) {
+        if (on0) s.actions[(size_t)row * A + d0] = a0;
+        if (on1) s.actions[(size_t)row * A + d1] = a1;
+    }
+    if (sub == 0 && s.log_probs) s.log_probs[row] = lp;
+}
+
+__global__ __launch_bounds__(kRT) void recurrent_step_kernel(const agx_recurrent_step s, const int slot) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const bool critic = blockIdx.y != 0;
+    const agx_recurrent_net &n = critic ? s.critic : s.actor;
+    const int N = (int)s.N, H = n.lstm.H, L = n.lstm.L, in = n.lstm.in;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = lane & 15, q = lane >> 4;
+    const int sr = threadIdx.x >> 5, sc = threadIdx.x & 31;  // staging: 32 threads per row
+    const int b0 = blockIdx.x * 16;
+    const int in16 = (in + 15) & ~15, ldx = in16 + 4, ldh = H + 4;
+    float *xs = lds, *hs = lds + slot;
+    const int srow = b0 + sr;
+    const bool slive = srow < N;
+    const bool skeep = slive && !(s.reset && s.reset[srow]);  // the row carries its state into the step
+
+    lstm::stage_step(xs, ldx, s.obs, N, 1, 0, in, in16, b0);
+    if (!critic && s.obs_store && slive)
+        for (int k = sc; k < in; k += 32) s.obs_store[(int64_t)srow * in + k] = s.obs[(int64_t)srow * in + k];
+
+    for (int l = 0; l < L; ++l) {
+        const agx_lstm_layer &p = n.lstm.layer[l];
+        const int K = l ? H : in;
+        const float *xin = l ? lds + (2 + ((l - 1) & 1)) * slot : xs;
+        const int ldin = l ? ldh : ldx;
+        float *hout = lds + (2 + (l & 1)) * slot;
+        {  // h_prev of this layer into LDS; the state the step is taken from into the rollout slot
+            const int64_t o = ((int64_t)l * N + min(srow, N - 1)) * H;
+            const int64_t so = ((int64_t)min(srow, N - 1) * L + l) * H;
+            for (int k = sc; k < H; k += 32) {
+                const float hv = skeep ? n.h[o + k] : 0.f;
+                hs[sr * ldh + k] = hv;
+                if (slive && n.h_store) n.h_store[so + k] = hv;
+                if (slive && n.c_store) n.c_store[so + k] = skeep ? n.c[o + k] : 0.f;
+            }
+        }
+        __syncthreads();
+        const float *xrow = xin + r * ldin, *hrow = hs + r * ldh;
+        const bool vec_ih = (K & 3) == 0 && lstm::aligned16(p.w_ih);
+        const bool vec_hh = lstm::aligned16(p.w_hh);
+        for (int tile = wave; tile < (H >> 4); tile += kRW) {
+            const int unit = tile * 16 + r;
+            f32x4 acc[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float b = p.b_ih[g * H + unit] + p.b_hh[g * H + unit];
+                acc[g] = f32x4{b, b, b, b};
+            }
+            const float *wi = p.w_ih + (int64_t)unit * K;
+            if (vec_ih)
+                lstm::gates_vec<2>(K, q, acc, xrow, wi, (int64_t)H * K);
+            else
+                lstm::gates_any(K, q, acc, xrow, wi, (int64_t)H * K);
+            const float *wh = p.w_hh + (int64_t)unit * H;
+            if (vec_hh)
+                lstm::gates_vec<2>(H, q, acc, hrow, wh, (int64_t)H * H);
+            else
+                lstm::gates_any(H, q, acc, hrow, wh, (int64_t)H * H);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = b0 + 4 * q + i;
+                const bool live = row < N;
+                const int64_t o = ((int64_t)l * N + min(row, N - 1)) * H + unit;
+                const float cp = (live && !(s.reset && s.reset[row])) ? n.c[o] : 0.f;
+                const float ig = lstm::sigm(acc[0][i]), fg = lstm::sigm(acc[1][i]), gg = tanhf(acc[2][i]),
+                            og = lstm::sigm(acc[3][i]);
+                const float cv = fg * cp + ig * gg;
+                const float hv = og * tanhf(cv);
+                hout[(4 * q + i) * ldh + unit] = hv;
+                if (live) {
+                    if (n.h_next) n.h_next[o] = hv;
+                    if (n.c_next) n.c_next[o] = cv;
+                }
+            }
+        }
+        __syncthreads();  // h' is whole, and hs is free for the next layer's h_prev
+    }
+
+    // the encoder's output Linear and activation, then the head: slots 0 and 1 in turn
+    const float *X = lds + (2 + ((L - 1) & 1)) * slot;
+    int ldX = ldh, F = n.latent, side = 0;
+    float *Y = lds;
+    int ldY = ((F + 15) & ~15) + 4;
+    dense(X, ldX, H, n.out_w, n.out_b, F, Y, ldY);
+    __syncthreads();
+    row_pass(Y, ldY, F, nullptr, nullptr, n.out_act);
+    __syncthreads();
+    for (int j = 0; j < n.n_head; ++j) {
+        const agx_recurrent_linear &hl = n.head[j];
+        X = Y;
+        ldX = ldY;
+        side ^= 1;
+        Y = lds + side * slot;
+        F = hl.out;
+        ldY = ((F + 15) & ~15) + 4;
+        dense(X, ldX, hl.in, hl.w, hl.b, F, Y, ldY);
+        __syncthreads();
+        row_pass(Y, ldY, F, hl.ln_w, hl.ln_b, hl.relu ? AGX_RECURRENT_ACT_RELU : AGX_RECURRENT_ACT_NONE);
+        __syncthreads();
+    }
+    if (critic) {
+        const int row = b0 + threadIdx.x;
+        if (threadIdx.x < 16 && row < N && s.values) s.values[row] = Y[threadIdx.x * ldY];
+    } else if (s.box) {
+        gauss_step(s, Y, ldY, b0);
+    } else {
+        categorical_step(s, Y, ldY, b0);
+    }
+}
+
+int check_net(const agx_recurrent_net &n, int out, const char *name, const char *who) {
+    const agx_lstm_desc &d = n.lstm;
+    AGX_REQUIRE(d.L >= 1 && d.L <= AGX_LSTM_MAX_LAYERS, "%s: %s: %d layers outside [1, %d]", who, name, d.L,
+                AGX_LSTM_MAX_LAYERS);
+    AGX_REQUIRE(d.H >= 16 && d.H <= AGX_LSTM_MAX_HIDDEN && d.H % 16 == 0,
+                "%s: %s: hidden size %d is not a multiple of 16 in [16, %d]", who, name, d.H, AGX_LSTM_MAX_HIDDEN);
+    AGX_REQUIRE(d.in >= 1 && d.in <= AGX_LSTM_MAX_INPUT, "%s: %s: input size %d outside [1, %d]", who, name, d.in,
+                AGX_LSTM_MAX_INPUT);
+    for (int l = 0; l < d.L; ++l) {
+        const agx_lstm_layer &p = d.layer[l];
+        AGX_REQUIRE(p.w_ih && p.w_hh && p.b_ih && p.b_hh, "%s: %s: LSTM layer %d: a parameter is NULL", who, name, l);
+    }
+    AGX_REQUIRE(n.out_w && n.out_b && n.h && n.c, "%s: %s: the output Linear or a state is NULL", who, name);
+    AGX_REQUIRE(n.latent >= 1 && n.latent <= AGX_PPO_GRAPH_MAX_WIDTH, "%s: %s: latent %d outside [1, %d]", who, name,
+                n.latent, AGX_PPO_GRAPH_MAX_WIDTH);
+    AGX_REQUIRE(n.out_act >= AGX_RECURRENT_ACT_NONE && n.out_act <= AGX_RECURRENT_ACT_TANH,
+                "%s: %s: output activation %d", who, name, n.out_act);
+    AGX_REQUIRE(n.n_head >= 2 && n.n_head <= AGX_RECURRENT_MAX_HEAD, "%s: %s: %d head layers outside [2, %d]", who,
+                name, n.n_head, AGX_RECURRENT_MAX_HEAD);
+    int width = n.latent;
+    for (int j = 0; j < n.n_head; ++j) {
+        const agx_recurrent_linear &h = n.head[j];
+        const bool last = j == n.n_head - 1;
+        AGX_REQUIRE(h.w && h.b && !h.ln_w == !h.ln_b, "%s: %s: head layer %d: NULL parameter", who, name, j);
+        AGX_REQUIRE(h.in == width && h.out >= 1 && h.out <= AGX_PPO_GRAPH_MAX_WIDTH,
+                    "%s: %s: head layer %d: %d -> %d after width %d", who, name, j, h.in, h.out, width);
+        AGX_REQUIRE(!last || (h.out == out && !h.ln_w && !h.relu), "%s: %s: the head must end in a plain Linear to %d",
+                    who, name, out);
+        width = h.out;
+    }
+    return AGX_OK;
+}
+
+int widest(const agx_recurrent_net &n) {
+    int w = n.lstm.in > n.lstm.H ? n.lstm.in : n.lstm.H;
+    w = n.latent > w ? n.latent : w;
+    for (int j = 0; j < n.n_head; ++j) w = n.head[j].out > w ? n.head[j].out : w;
+    return w;
+}
+
+}  // namespace
+}  // namespace agx
+
+using namespace agx;
+
+extern "C" int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *stream) {
+    const char *who = "agx_ppo_act_recurrent";
+    AGX_REQUIRE(step, "%s: step is NULL", who);
+    const agx_recurrent_step &s = *step;
+    AGX_REQUIRE(s.N >= 1 && s.N <= (1 << 24), "%s: N %lld outside [1, 2^24]", who, (long long)s.N);
+    AGX_REQUIRE(s.A >= 1 && s.A <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d actions (1..%d)", who, s.A,
+                AGX_PPO_GRAPH_MAX_ACTIONS);
+    AGX_REQUIRE(s.obs, "%s: obs is NULL", who);
+    AGX_REQUIRE(s.box ? (s.log_std && !s.mask) : !s.log_std, "%s: log_std goes with Box, a mask with Discrete", who);
+    if (int rc = check_net(s.actor, s.A, "actor", who)) return rc;
+    if (int rc = check_net(s.critic, 1, "critic", who)) return rc;
+    AGX_REQUIRE(s.actor.lstm.in == s.critic.lstm.in, "%s: the networks read observations of %d and %d floats", who,
+                s.actor.lstm.in, s.critic.lstm.in);
+    const int wa = widest(s.actor), wc = widest(s.critic);
+    const int slot = 16 * ((((wa > wc ? wa : wc) + 15) & ~15) + 4);
+    const size_t bytes = (size_t)4 * slot * sizeof(float);  // at most 4 * 16 * 516 * 4 = 129 KB
+    static const bool once = [] {
+        (void)hipFuncSetAttribute((const void *)recurrent_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kLdsCap);
+        return true;
+    }();
+    (void)once;
+    const dim3 grid((unsigned)ceil_div(s.N, 16), 2);
+    hipLaunchKernelGGL(recurrent_step_kernel, grid, dim3(kRT), bytes, as_stream(stream), s, slot);
+    return check_launch(who);
+}

@@ -898,3 +898,174 @@ def ppo_seq_loss_fwd_bwd(logp, value, entropy, valid_row, old_logp, adv, ret, ol
               old_value.data_ptr(), float(clip_coef), float(vf_coef), float(ent_coef), out[0].data_ptr(),
               out[1].data_ptr(), out[2].data_ptr(), stats.data_ptr(), ws.data_ptr(), _lib.stream())
     return out[0], out[1], out[2], stats
+
+
+# --------------------------------------------------------------------------- #
+# The fused recurrent policy step (include/agx_recurrent.h)                     #
+# --------------------------------------------------------------------------- #
+from .modules import lstm as _lstm  # noqa: E402  (the LSTM descriptor and its rules; imports nothing from here)
+
+RECURRENT_MAX_HEAD, RECURRENT_MAX_WIDTH, RECURRENT_MAX_ACTIONS = 4, 512, 32  # AGX_RECURRENT_MAX_HEAD, AGX_PPO_GRAPH_MAX_*
+_i32s = lambda *names: [(n, ctypes.c_int32) for n in names]  # noqa: E731
+
+
+class RecurrentLinear(ctypes.Structure):
+    """Mirror of ``agx_recurrent_linear``."""
+
+    _fields_ = _ptr_fields("w", "b", "ln_w", "ln_b") + _i32s("in_", "out", "relu", "pad_")
+
+
+class RecurrentNet(ctypes.Structure):
+    """Mirror of ``agx_recurrent_net``."""
+
+    _fields_ = ([("lstm", _lstm.AgxLstmDesc)] + _ptr_fields("out_w", "out_b") + _i32s("latent", "out_act") +
+                [("head", RecurrentLinear * RECURRENT_MAX_HEAD)] + _i32s("n_head", "pad_") +
+                _ptr_fields("h", "c", "h_next", "c_next", "h_store", "c_store"))
+
+
+class RecurrentStep(ctypes.Structure):
+    """Mirror of ``agx_recurrent_step``."""
+
+    _fields_ = ([("actor", RecurrentNet), ("critic", RecurrentNet)] + _ptr_fields("obs", "log_std", "reset", "mask") +
+                [("N", ctypes.c_int64)] + _i32s("A", "box", "sample", "pad_") +
+                [("seed", ctypes.c_uint64), ("counter", ctypes.c_uint64)] +
+                _ptr_fields("actions", "log_probs", "entropy", "values", "obs_store"))
+
+
+def _recurrent_net(net, head, n_out: int):
+    """(encoder, parameter tensors of the LSTM, output Linear, output activation code, head layers as
+    (Linear, LayerNorm or None, relu)) of a recurrent network the kernel takes, or None."""
+    from torch import nn
+
+    enc = getattr(net, "encoder", None)
+    if not isinstance(enc, _lstm.EvolvableLSTM) or getattr(net, "flatten_obs", False):
+        return None
+    found = _lstm._plan(enc.lstm)
+    out = enc.model[f"{enc.name}_lstm_output"]
+    act = enc.model[f"{enc.name}_output_activation"]
+    code = {nn.Identity: 0, nn.ReLU: 1, nn.Tanh: 2}.get(type(act))
+    if found is None or code is None or type(out) is not nn.Linear or out.bias is None or \
+            not 1 <= out.out_features <= RECURRENT_MAX_WIDTH:
+        return None
+    layers, width = [], out.out_features
+    for m in getattr(head, "model", ()):
+        if type(m) is nn.Linear and m.bias is not None and m.in_features == width:
+            if layers and not layers[-1][2]:  # a Linear after a layer without its ReLU
+                return None
+            layers.append([m, None, False])
+            width = m.out_features
+        elif type(m) is nn.LayerNorm and layers and m.elementwise_affine and layers[-1][1] is None \
+                and not layers[-1][2] and tuple(m.normalized_shape) == (width,) and m.eps == 1e-5:
+            layers[-1][1] = m
+        elif type(m) is nn.ReLU and layers and not layers[-1][2]:
+            layers[-1][2] = True
+        elif type(m) is not nn.Identity:
+            return None
+    if not 2 <= len(layers) <= RECURRENT_MAX_HEAD or layers[-1][1] is not None or layers[-1][2] or \
+            width != n_out or any(lay[0].out_features > RECURRENT_MAX_WIDTH for lay in layers):
+        return None
+    ts = [out.weight, out.bias] + [t for lin, ln, _ in layers for t in
+                                   ((lin.weight, lin.bias) + ((ln.weight, ln.bias) if ln is not None else ()))]
+    if any(t.dtype != _f32 or not t.is_cuda or not t.is_contiguous() for t in ts):
+        return None
+    return enc, found, out, code, layers
+
+
+def _fill_recurrent_net(d: RecurrentNet, plan, hidden, N: int, nxt, store):
+    """The descriptor of one network over its live parameters -> (h_next, c_next), or None on a state mismatch."""
+    enc, (meta, ts), out, code, layers = plan
+    (_, H, L), name = meta, enc.name
+    h, c = hidden.get(f"{name}_h"), hidden.get(f"{name}_c")
+    for t in (h, c):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (L, N, H) or t.dtype != _f32 or not t.is_cuda \
+                or not t.is_contiguous():
+            return None
+    d.lstm = _lstm._desc(meta, ts)
+    d.out_w, d.out_b, d.latent, d.out_act = out.weight.data_ptr(), out.bias.data_ptr(), out.out_features, code
+    for j, (lin, ln, relu) in enumerate(layers):
+        e = d.head[j]
+        e.w, e.b, e.in_, e.out, e.relu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, \
+            lin.out_features, int(relu)
+        if ln is not None:
+            e.ln_w, e.ln_b = ln.weight.data_ptr(), ln.bias.data_ptr()
+    d.n_head = len(layers)
+    h_next, c_next = nxt[0].view(L, N, H), nxt[1].view(L, N, H)
+    d.h, d.c, d.h_next, d.c_next = h.data_ptr(), c.data_ptr(), h_next.data_ptr(), c_next.data_ptr()
+    if store is not None:
+        hs, cs = store[f"{name}_h"], store[f"{name}_c"]
+        _need(hs, f"store[{name}_h]", _f32, (N, L, H))
+        _need(cs, f"store[{name}_c]", _f32, (N, L, H))
+        d.h_store, d.c_store = hs.data_ptr(), cs.data_ptr()
+    return {f"{name}_h": h_next, f"{name}_c": c_next}
+
+
+def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counter=0, mask=None, reset=None,
+                      out=None, store_hidden=None, store_obs=None):
+    """agx_ppo_act_recurrent: one policy step of a ``StochasticActor`` / ``ValueNetwork`` pair on EvolvableLSTM
+    encoders.  obs f32 [N, in]; hidden {``{encoder}_h`` / ``_c``: [L, N, H]} of both networks; mask uint8 / bool
+    [N, A] (Discrete, 1 = legal) and reset uint8 / bool [N] (1 = start from the zero state) or None.  ``out``:
+    {"actions" [N, 1] (Discrete) or [N, A] (Box), "log_probs", "values" [N]} f32 to write into (a rollout-buffer
+    slot) instead of new tensors; store_hidden {key: [N, L, H]} / store_obs [N, in]: the slot's copies of the
+    states the step was taken from and of obs.  -> {"actions", "log_probs" (None without ``sample``), "entropy",
+    "values", "hidden": the next states}, or None where the kernel does not apply (the caller runs the torch
+    modules): see include/agx_recurrent.h for the limits."""
+    from .modules._hooks import hooked
+
+    space = actor.action_space
+    box = not hasattr(space, "n")
+    A = int(space.shape[0]) if box else int(space.n)
+    head = getattr(actor, "head_net", None)
+    if not 1 <= A <= RECURRENT_MAX_ACTIONS or hooked(actor, critic) or (box and mask is not None):
+        return None
+    pa, pc = _recurrent_net(actor, getattr(head, "_wrapped", None), A), _recurrent_net(critic, critic.head_net, 1)
+    if pa is None or pc is None or not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.dtype != _f32 or \
+            not obs.is_cuda or not obs.is_contiguous() or obs.shape[1] != pa[1][0][0] or pa[1][0][0] != pc[1][0][0] \
+            or not 1 <= obs.shape[0] <= _lstm._MAX_ROWS:
+        return None
+    if box and (head.log_std.dtype != _f32 or not head.log_std.is_cuda or head.log_std.numel() != A):
+        return None
+    N, dev = obs.shape[0], obs.device
+    sizes = [p[1][0][2] * N * p[1][0][1] for p in (pa, pc)]  # L N H
+    nxt = torch.empty(2 * sum(sizes), dtype=_f32, device=dev)
+    s = RecurrentStep()
+    nh_a = _fill_recurrent_net(s.actor, pa, hidden, N, (nxt[:sizes[0]], nxt[sizes[0]:2 * sizes[0]]), store_hidden)
+    nh_c = _fill_recurrent_net(s.critic, pc, hidden, N, (nxt[2 * sizes[0]:2 * sizes[0] + sizes[1]],
+                                                          nxt[2 * sizes[0] + sizes[1]:]), store_hidden)
+    if nh_a is None or nh_c is None:
+        return None
+    out = out or {}
+    res = {"actions": out.get("actions"), "log_probs": out.get("log_probs"), "values": out.get("values")}
+    if sample and res["actions"] is None:
+        res["actions"] = torch.empty(N, A if box else 1, dtype=_f32, device=dev)
+    small = torch.empty(3, N, dtype=_f32, device=dev)
+    res["entropy"] = small[0]
+    if res["values"] is None:
+        res["values"] = small[1]
+    if sample and res["log_probs"] is None:
+        res["log_probs"] = small[2]
+    if sample:
+        _need(res["actions"], "actions", _f32, (N, A if box else 1))
+        _need(res["log_probs"], "log_probs", _f32, (N,))
+        s.actions, s.log_probs = res["actions"].data_ptr(), res["log_probs"].data_ptr()
+    else:
+        res["actions"] = res["log_probs"] = None
+    _need(res["values"], "values", _f32, (N,))
+    s.entropy, s.values = res["entropy"].data_ptr(), res["values"].data_ptr()
+    s.obs, s.N, s.A, s.box, s.sample = obs.data_ptr(), N, A, int(box), int(bool(sample))
+    s.seed, s.counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+    if box:
+        s.log_std = head.log_std.data_ptr()
+    keep = [nxt, small]
+    for name, t, shape in (("mask", mask, (N, A)), ("reset", reset, (N,))):
+        if t is None:
+            continue
+        t = torch.as_tensor(t)
+        t = (t.view(_u8) if t.dtype == torch.bool else t.to(_u8)).to(dev).reshape(shape).contiguous()
+        keep.append(t)
+        setattr(s, name, t.data_ptr())
+    if store_obs is not None:
+        _need(store_obs, "store_obs", _f32, tuple(obs.shape))
+        s.obs_store = store_obs.data_ptr()
+    _lib.call("agx_ppo_act_recurrent", ctypes.byref(s), _lib.stream())
+    res["hidden"] = {**nh_a, **nh_c}
+    return res

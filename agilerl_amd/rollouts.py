@@ -36,7 +36,6 @@ def collect_rollouts_recurrent(agent, env, n_steps: int | None = None, last_obs=
     hidden state is stored before the step is taken, and goes back to the initial state where the step ended an
     episode.  -> (completed episode scores, obs, done, scores, info) for the caller's next call."""
     import numpy as np
-    import torch
 
     from .algorithms.ppo_recurrent import reset_hidden_state
 
@@ -53,27 +52,43 @@ def collect_rollouts_recurrent(agent, env, n_steps: int | None = None, last_obs=
     box = not hasattr(agent.action_space, "n")
     completed = []
     term = np.zeros(agent.num_envs, dtype=bool)
+    fused = agent.fused_step_on()
+    reset = None  # the previous step's dones: the fused step starts those rows from the zero state itself
     for _ in range(n_steps):
         stored = agent.hidden_state
         mask = info.get("action_mask")
-        action, log_prob, _, value, agent.hidden_state = agent.get_action(obs, action_mask=mask, hidden_state=stored)
+        res = buf.fused_step(agent, obs, mask, stored, reset) if fused else None
+        if res is not None:  # slot `pos` holds obs / action / log-prob / value / the state taken; the host adds the rest
+            action, log_prob, value, agent.hidden_state = res
+        else:
+            if reset is not None:
+                reset_hidden_state(stored, agent.get_initial_hidden_state(agent.num_envs), reset)
+            action, log_prob, _, value, agent.hidden_state = agent.get_action(obs, action_mask=mask,
+                                                                              hidden_state=stored)
         env_action = np.clip(action, agent.action_space.low, agent.action_space.high) if box else action
         next_obs, reward, term, trunc, next_info = env.step(env_action)
         ended = np.atleast_1d(np.logical_or(term, trunc))
         reward = np.atleast_1d(reward)
-        buf.add(obs=obs, action=action, reward=reward, done=ended, value=np.atleast_1d(value),
-                log_prob=np.atleast_1d(log_prob), next_obs=next_obs, hidden_state=stored, action_mask=mask)
+        if res is not None:
+            buf.finish_step(reward=reward, done=ended, next_obs=next_obs, action_mask=mask)
+        else:
+            buf.add(obs=obs, action=action, reward=reward, done=ended, value=np.atleast_1d(value),
+                    log_prob=np.atleast_1d(log_prob), next_obs=next_obs, hidden_state=stored, action_mask=mask)
         scores += reward
         done = ended
+        reset = None
         if np.any(ended):
-            reset_hidden_state(agent.hidden_state, agent.get_initial_hidden_state(agent.num_envs), ended)
+            if fused:
+                reset = ended
+            else:
+                reset_hidden_state(agent.hidden_state, agent.get_initial_hidden_state(agent.num_envs), ended)
         obs, info = next_obs, next_info if isinstance(next_info, dict) else {}
         for i in np.flatnonzero(ended):
             completed.append(float(scores[i]))
             agent.scores.append(float(scores[i]))
             scores[i] = 0
-    with torch.no_grad():
-        _, _, _, last_value, _ = agent._get_action_and_values(agent.preprocess_observation(obs),
-                                                              hidden_state=agent.hidden_state, sample=False)
+    if reset is not None:  # the state handed to the next call is the reset one, as on the torch path
+        reset_hidden_state(agent.hidden_state, agent.get_initial_hidden_state(agent.num_envs), reset)
+    last_value = agent.bootstrap_value(obs, agent.hidden_state)
     buf.compute_returns_and_advantages(last_value=last_value, last_done=np.atleast_1d(term))
     return completed, obs, done, scores, info

@@ -1,0 +1,91 @@
+/* The fused policy step of recurrent PPO (agilerl/algorithms/ppo.py with
+ * `recurrent`, separate encoders): one launch takes a block of envs through
+ * both networks of the agent, the StochasticActor and the ValueNetwork, each
+ * an EvolvableLSTM encoder (nn.LSTM, output Linear, output activation) and an
+ * EvolvableMLP head, and through the distribution of the action space:
+ *
+ *   per network:  (h', c') = LSTM(obs, (h, c))  at T = 1, every layer
+ *                 latent   = act(W_out h'_top + b_out)
+ *                 head     = Linear [LayerNorm] ReLU ... Linear
+ *   Discrete:     masked logits, log-softmax, entropy, Gumbel-max sample
+ *   Box:          mean + exp(log_std) * eps, Gaussian log-prob and entropy
+ *
+ * Grid (ceil(N / 16), 2): a workgroup owns a 16-env row tile of one network
+ * (y = 0 the actor, y = 1 the critic).  The tiles of every layer stay in LDS,
+ * the cell update in registers; only the step's outputs reach global memory.
+ * The new states have the bits of agx_lstm_forward at T = 1 (the same gate
+ * chains, csrc/lstm_gates.h), so sequences the learner re-runs from stored
+ * states meet the states the rollout carried.  fp32 on
+ * v_mfma_f32_16x16x4_f32; no atomics; no workgroup waits on another.
+ *
+ * The samples are the Philox streams of agx_ppo_act (Discrete: Gumbel-max,
+ * word a & 3 of the block of (env, counter ^ (a >> 2) << 56)) and of
+ * agx_ppo_act_gauss_graph (Box: Box-Muller per dimension), keyed by the env's
+ * row index, `seed` and `counter`.
+ *
+ * Binding: agilerl_amd/kernels.py ppo_act_recurrent. */
+#ifndef AGX_RECURRENT_H
+#define AGX_RECURRENT_H
+
+#include "agx_graph.h"
+#include "agx_lstm.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AGX_RECURRENT_MAX_HEAD 4 /* head Linear layers: up to 3 hidden and the output */
+
+#define AGX_RECURRENT_ACT_NONE 0
+#define AGX_RECURRENT_ACT_RELU 1
+#define AGX_RECURRENT_ACT_TANH 2
+
+/* y = x W^T + b, W [out][in]; ln_w / ln_b: the affine of a LayerNorm over
+ * `out` after it (eps 1e-5), or both NULL; relu: ReLU last. */
+typedef struct agx_recurrent_linear {
+    const float *w, *b, *ln_w, *ln_b;
+    int32_t in, out, relu, pad_;
+} agx_recurrent_linear;
+
+/* One network.  The pointers are the live module parameters.  Limits: the
+ * LSTM's (agx_lstm.h); latent and every hidden head width in [1,
+ * AGX_PPO_GRAPH_MAX_WIDTH]; 2 <= n_head <= AGX_RECURRENT_MAX_HEAD, the last
+ * head layer plain (no LayerNorm, no ReLU). */
+typedef struct agx_recurrent_net {
+    agx_lstm_desc lstm;      /* g_* unused */
+    const float *out_w, *out_b; /* the encoder's output Linear [latent][H], [latent] */
+    int32_t latent, out_act; /* AGX_RECURRENT_ACT_* after it */
+    agx_recurrent_linear head[AGX_RECURRENT_MAX_HEAD];
+    int32_t n_head, pad_;
+    const float *h, *c;      /* [L][N][H]: the states the step starts from */
+    float *h_next, *c_next;  /* [L][N][H]: the states after it (may be h, c themselves) */
+    float *h_store, *c_store; /* [N][L][H] or NULL: the states the step was taken from, rollout-buffer order */
+} agx_recurrent_net;
+
+/* One policy step of N envs.  Every output pointer may be NULL. */
+typedef struct agx_recurrent_step {
+    agx_recurrent_net actor, critic; /* actor.head ends in A outputs, critic.head in 1 */
+    const float *obs;        /* [N][in] */
+    const float *log_std;    /* [A], Box only */
+    const uint8_t *reset;    /* [N] or NULL: 1 = the row starts from the zero state (and stores it) */
+    const uint8_t *mask;     /* [N][A] or NULL, Discrete only: 1 = legal; illegal logits become -1e8 */
+    int64_t N;
+    int32_t A;               /* Discrete: actions; Box: dimensions; 1 .. AGX_PPO_GRAPH_MAX_ACTIONS */
+    int32_t box;             /* 0: Discrete, 1: Box */
+    int32_t sample;          /* 0: no draw, `actions` and `log_probs` are not written */
+    int32_t pad_;
+    uint64_t seed, counter;
+    float *actions;          /* Discrete [N] (the index as a float), Box [N][A] */
+    float *log_probs, *entropy, *values; /* [N] */
+    float *obs_store;        /* [N][in] or NULL: a copy of obs (the rollout slot) */
+} agx_recurrent_step;
+
+/* One launch on `stream`; nothing is synchronised.  AGX_EINVAL (agx_last_error
+ * says why) for shapes outside the limits. */
+int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* AGX_RECURRENT_H */
