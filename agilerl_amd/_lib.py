@@ -30,8 +30,8 @@ class AgxMultiHead(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/agx.h (and agx_graph.h, agx_td3.h, agx_gauss.h, agx_multi.h,
-# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h, agx_lstm.h, agx_bptt.h, agx_recurrent.h)
-# one-to-one
+# agx_bernoulli.h, agx_cqn.h, agx_bandit.h, agx_ippo.h, agx_simba.h, agx_lstm.h, agx_bptt.h, agx_recurrent.h,
+# agx_recurrent_heads.h) one-to-one
 SIGNATURES = {
     "agx_last_error": (ctypes.c_char_p, []),
     "agx_version": (_INT, []),
@@ -184,6 +184,11 @@ SIGNATURES = {
     "agx_ppo_seq_loss_fwd_bwd": (_INT, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     # include/agx_recurrent.h: the fused recurrent policy step (descriptor: kernels.py RecurrentStep)
     "agx_ppo_act_recurrent": (_INT, [_P, _P]),
+    # include/agx_recurrent_heads.h: the BPTT learner's heads (descriptors: kernels.py RecurrentHeads / ...Grads)
+    "agx_recurrent_heads_saved_bytes": (_SZ, [_P]),
+    "agx_recurrent_heads_workspace_bytes": (_SZ, [_P]),
+    "agx_recurrent_heads_forward": (_INT, [_P, _P, _P, _P, _P, _P]),
+    "agx_recurrent_heads_backward": (_INT, [_P, _P, _P, _P, _P]),
     "agx_conv2d_forward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _INT, _P, _P]),
     "agx_conv2d_wgrad_workspace_bytes": (_SZ, [_P]),
     "agx_conv2d_backward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _P, _P, _P, _P, _INT, _P, _P]),

@@ -17,8 +17,18 @@ switched on (``fused_step=True`` or AGX_RECURRENT_STEP=1; AGX_RECURRENT_STEP=0
 always wins): then a policy step, both LSTM encoders, both heads and the draw
 from the Philox streams, is one agx_ppo_act_recurrent launch
 (include/agx_recurrent.h) wherever its limits hold, and the torch modules run
-elsewhere.  The switch is off by default.  ``share_encoders=True``, image / Dict
-observations, MultiDiscrete / MultiBinary actions and ``squash_output`` raise.
+elsewhere.  The switch is off by default.
+
+``learn()`` runs everything after the LSTMs as torch modules unless the fused
+heads are switched on (``fused_learn=True`` or AGX_RECURRENT_LEARN=1;
+AGX_RECURRENT_LEARN=0 always wins): then, per minibatch, each encoder's
+``nn.LSTM`` runs as ``EvolvableLSTM.forward`` runs it, and the output Linears,
+the heads, the log-prob and the entropy of both networks are one
+agx_recurrent_heads_forward launch with a two-launch backward
+(include/agx_recurrent_heads.h) wherever the limits hold.  Off by default.
+
+``share_encoders=True``, image / Dict observations, MultiDiscrete /
+MultiBinary actions and ``squash_output`` raise.
 """
 
 from __future__ import annotations
@@ -29,6 +39,7 @@ import warnings
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 from torch.nn.utils import clip_grad_norm_
 
 from .. import kernels as K
@@ -57,6 +68,29 @@ class SeqLossFn(torch.autograd.Function):
         return (g_loss * g_logp, g_loss * g_value, g_loss * g_entropy) + (None,) * 8
 
 
+class HeadsFn(torch.autograd.Function):
+    """(actor, critic, actions, mask; both networks' top-layer LSTM outputs [rows, H]; the parameters of
+    kernels.recurrent_heads_params) -> (log_prob, entropy, value [rows])."""
+
+    @staticmethod
+    def forward(ctx, actor, critic, actions, mask, h_actor, h_critic, *params):
+        h_top = (h_actor.detach().contiguous(), h_critic.detach().contiguous())
+        logp, entropy, value, saved = K.recurrent_heads_forward(actor, critic, h_top, actions, mask)
+        ctx.nets, ctx.mask = (actor, critic), mask
+        ctx.save_for_backward(*h_top, actions, saved)
+        return logp, entropy, value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_logp, g_entropy, g_value):
+        h_actor, h_critic, actions, saved = ctx.saved_tensors
+        ups = [torch.zeros(h_actor.shape[0], device=h_actor.device) if g is None else g.float().contiguous()
+               for g in (g_logp, g_entropy, g_value)]
+        dh_actor, dh_critic, grads = K.recurrent_heads_backward(*ctx.nets, (h_actor, h_critic), actions, ctx.mask,
+                                                                saved, *ups)
+        return (None, None, None, None, dh_actor, dh_critic, *grads)
+
+
 class RecurrentPPO(PPO):
     # the population view's descriptors give way to plain attributes
     lr = batch_size = update_epochs = ent_coef = learn_step = rollout_buffer = None
@@ -70,7 +104,7 @@ class RecurrentPPO(PPO):
                  actor_network=None, critic_network=None, share_encoders: bool = True, num_envs: int = 1,
                  use_rollout_buffer: bool = True, rollout_buffer_config=None, recurrent: bool = True, device="cuda",
                  accelerator=None, wrap: bool = True, bptt_sequence_type=None, max_seq_len=None,
-                 fused_step: bool = False) -> None:
+                 fused_step: bool = False, fused_learn: bool = False) -> None:
         from ..hpo.registry import MutationRegistry
 
         if not use_rollout_buffer:
@@ -99,7 +133,7 @@ class RecurrentPPO(PPO):
         self.registry = MutationRegistry(hp_config)
         self.scores, self.fitness, self.steps = [], [], [0]
         self.hidden_state = None
-        self.fused_step = bool(fused_step)
+        self.fused_step, self.fused_learn = bool(fused_step), bool(fused_learn)
         self._act_seed, self._act_counter = None, 0  # the Philox key of the fused step: drawn on its first call
 
         cfg = dict(as_config(net_config) or {})
@@ -238,13 +272,36 @@ class RecurrentPPO(PPO):
             return self._get_action_and_values(obs, hidden_state=hidden_state, sample=False)[3]
 
     # ---- learning ---------------------------------------------------------------
+    def fused_learn_on(self) -> bool:
+        env = os.environ.get("AGX_RECURRENT_LEARN")
+        return env != "0" and (self.fused_learn or env == "1")
+
+    def fused_heads(self, obs, actions, hidden_state, action_mask=None):
+        """(log_prob, entropy, values) of ``evaluate_actions`` with everything after the LSTMs on the head kernels
+        (HeadsFn), or None with the switch off or where they do not apply."""
+        if not self.fused_learn_on() or not isinstance(actions, torch.Tensor) or actions.device.type != "cuda":
+            return None
+        params = K.recurrent_heads_params(self.actor, self.critic)
+        if params is None or (action_mask is not None and not self.discrete):
+            return None
+        obs = self.preprocess_observation(obs)
+        h_top = [net.encoder.lstm_output(obs, hidden_state)[0] for net in (self.actor, self.critic)]
+        if any(h.dim() != 2 or h.dtype != torch.float32 for h in h_top):
+            return None
+        actions = actions.to(torch.float32).contiguous()
+        if actions.shape != ((h_top[0].shape[0],) if self.discrete else (h_top[0].shape[0], params[-1].numel())):
+            return None
+        return HeadsFn.apply(self.actor, self.critic, actions, action_mask, *h_top, *params)
+
     def bptt_loss(self, padded: dict, unpadded: dict):
         """One minibatch of get_minibatch_sequences -> (loss, stats [8]) (ppo.py:964-1050): the networks over
         every padded row, the masked loss in one kernel."""
         actions = padded["actions"].squeeze(-1) if self.discrete else padded["actions"]
-        logp, entropy, values = self.evaluate_actions(padded["observations"], actions,
-                                                      hidden_state=padded["initial_hidden_states"],
-                                                      action_mask=padded.get("action_masks"))
+        fused = self.fused_heads(padded["observations"], actions, padded["initial_hidden_states"],
+                                 padded.get("action_masks"))
+        logp, entropy, values = fused if fused is not None else self.evaluate_actions(
+            padded["observations"], actions, hidden_state=padded["initial_hidden_states"],
+            action_mask=padded.get("action_masks"))
         return SeqLossFn.apply(logp, values, entropy, unpadded["valid_row"], unpadded["log_probs"],
                                unpadded["advantages"], unpadded["returns"], unpadded["values"],
                                float(self.clip_coef), float(self.vf_coef), float(self.ent_coef))

@@ -27,7 +27,7 @@
 // fwd_kernel's, so the states have agx_lstm_forward's bits at T = 1 (W_hh
 // register residency is a sequence optimisation: one step reads it once).
 //
-// Dense layers: one 16 x 16 output tile per wave and pass, one accumulator
+// Dense layers (recurrent_dense.h): one 16 x 16 output tile per wave and pass, one accumulator
 // from the bias over k ascending, four 16-deep steps' operands requested ahead
 // of their MFMAs; columns past the width are written as zeros, which is the
 // padding the next layer's A operand needs.  LayerNorm / activation are row
@@ -41,96 +41,13 @@
 #include "agx_common.h"
 #include "gauss_head.h"
 #include "lstm_gates.h"
+#include "recurrent_dense.h"
 #include "rollout.h"
 
 namespace agx {
 namespace {
 
-using lstm::f32x4;
-
-constexpr int kRT = 512;  // threads
-constexpr int kRW = 8;    // waves
 constexpr int kLdsCap = 160 * 1024;
-
-// acc[row][unit] += sum_k arow[k] * wrow[k], k < K ascending.  arow: this lane's row of an LDS tile zero-padded
-// to K16 = the 16-rounded K; wrow: this lane's unit row of W [out][K].  VEC: 16-byte weight loads (K % 4 == 0,
-// W 16-byte aligned), else 4-byte loads; the same k order and bits either way.
-template <bool VEC>
-__device__ __forceinline__ f32x4 chain_row(int K, int q, f32x4 acc, const float *arow, const float *wrow) {
-    const int K16 = (K + 15) & ~15;
-#pragma unroll 1
-    for (int kc = 0; kc < K; kc += 64) {
-        f32x4 a[4], w[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int k = kc + 16 * s + 4 * q;
-            a[s] = *reinterpret_cast<const f32x4 *>(arow + min(k, K16 - 4));
-            if (VEC) {
-                w[s] = *reinterpret_cast<const f32x4 *>(wrow + min(k, K - 4));
-                if (k >= K) w[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = wrow[min(k + j, K - 1)];
-                    w[s][j] = k + j < K ? v : 0.f;
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (kc + 16 * s < K) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc = MFMA(a[s][j], w[s][j], acc);
-            }
-    }
-    return acc;
-}
-
-// Y [16][ldy] = X [16][ldx] W^T + b over the 16-rounded width of F, zeros in the columns past F
-__device__ __forceinline__ void dense(const float *X, int ldx, int K, const float *W, const float *b, int F, float *Y,
-                                      int ldy) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = lane & 15, q = lane >> 4;
-    const bool vec = (K & 3) == 0 && lstm::aligned16(W);
-    for (int tile = wave; tile < ((F + 15) >> 4); tile += kRW) {
-        const int unit = tile * 16 + r, uu = min(unit, F - 1);
-        const float bv = b[uu];
-        f32x4 acc = {bv, bv, bv, bv};
-        const float *wrow = W + (int64_t)uu * K;
-        acc = vec ? chain_row<true>(K, q, acc, X + r * ldx, wrow) : chain_row<false>(K, q, acc, X + r * ldx, wrow);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + unit] = unit < F ? acc[i] : 0.f;
-    }
-}
-
-// LayerNorm (affine lnw / lnb, eps 1e-5; null: none) and the activation over the F columns of every row of
-// Y [16][ld] in place: waves 0 .. 3, 16 lanes per row.  The loops run to the 16-rounded width, so the row
-// reductions see whole DPP rows.
-__device__ __forceinline__ void row_pass(float *Y, int ld, int F, const float *lnw, const float *lnb, int act) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (wave >= 4 || (!lnw && act == AGX_RECURRENT_ACT_NONE)) return;
-    const int sub = lane & 15, F16 = (F + 15) & ~15;
-    float *y = Y + (4 * wave + (lane >> 4)) * ld;
-    float mean = 0.f, rstd = 1.f;
-    if (lnw) {
-        float s = 0.f;
-        for (int j = sub; j < F16; j += 16) s = j < F ? s + y[j] : s;
-        mean = row_sum(s) * (1.f / (float)F);
-        float vs = 0.f;
-        for (int j = sub; j < F16; j += 16) {
-            const float d = y[j] - mean;
-            vs = j < F ? vs + d * d : vs;
-        }
-        rstd = 1.f / sqrtf(row_sum(vs) / (float)F + 1e-5f);
-    }
-    for (int j = sub; j < F; j += 16) {
-        float x = y[j];
-        if (lnw) x = (x - mean) * rstd * lnw[j] + lnb[j];
-        if (act == AGX_RECURRENT_ACT_RELU) x = relu(x);
-        if (act == AGX_RECURRENT_ACT_TANH) x = tanhf(x);
-        y[j] = x;
-    }
-}
 
 // The categorical step of the 16 rows of logits Y [16][ld]: graph_rollout.hip's graph_sample, the action as a float
 __device__ __forceinline__ void categorical_step(const agx_recurrent_step &s, const float *Y, int ld, int b0) {

@@ -971,6 +971,19 @@ def _recurrent_net(net, head, n_out: int):
     return enc, found, out, code, layers
 
 
+def _fill_recurrent_dense(d: RecurrentNet, plan) -> None:
+    """The output Linear and the head of one network's descriptor over the live parameters."""
+    _, _, out, code, layers = plan
+    d.out_w, d.out_b, d.latent, d.out_act = out.weight.data_ptr(), out.bias.data_ptr(), out.out_features, code
+    for j, (lin, ln, relu) in enumerate(layers):
+        e = d.head[j]
+        e.w, e.b, e.in_, e.out, e.relu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, \
+            lin.out_features, int(relu)
+        if ln is not None:
+            e.ln_w, e.ln_b = ln.weight.data_ptr(), ln.bias.data_ptr()
+    d.n_head = len(layers)
+
+
 def _fill_recurrent_net(d: RecurrentNet, plan, hidden, N: int, nxt, store):
     """The descriptor of one network over its live parameters -> (h_next, c_next), or None on a state mismatch."""
     enc, (meta, ts), out, code, layers = plan
@@ -981,14 +994,7 @@ def _fill_recurrent_net(d: RecurrentNet, plan, hidden, N: int, nxt, store):
                 or not t.is_contiguous():
             return None
     d.lstm = _lstm._desc(meta, ts)
-    d.out_w, d.out_b, d.latent, d.out_act = out.weight.data_ptr(), out.bias.data_ptr(), out.out_features, code
-    for j, (lin, ln, relu) in enumerate(layers):
-        e = d.head[j]
-        e.w, e.b, e.in_, e.out, e.relu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, \
-            lin.out_features, int(relu)
-        if ln is not None:
-            e.ln_w, e.ln_b = ln.weight.data_ptr(), ln.bias.data_ptr()
-    d.n_head = len(layers)
+    _fill_recurrent_dense(d, plan)
     h_next, c_next = nxt[0].view(L, N, H), nxt[1].view(L, N, H)
     d.h, d.c, d.h_next, d.c_next = h.data_ptr(), c.data_ptr(), h_next.data_ptr(), c_next.data_ptr()
     if store is not None:
@@ -1069,3 +1075,143 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     _lib.call("agx_ppo_act_recurrent", ctypes.byref(s), _lib.stream())
     res["hidden"] = {**nh_a, **nh_c}
     return res
+
+
+# --------------------------------------------------------------------------- #
+# The BPTT learner's heads (include/agx_recurrent_heads.h)                      #
+# --------------------------------------------------------------------------- #
+class RecurrentLinearGrad(ctypes.Structure):
+    """Mirror of ``agx_recurrent_linear_grad``."""
+
+    _fields_ = _ptr_fields("w", "b", "ln_w", "ln_b")
+
+
+class RecurrentHeads(ctypes.Structure):
+    """Mirror of ``agx_recurrent_heads``."""
+
+    _fields_ = ([("net", RecurrentNet * 2), ("h_top", ctypes.c_void_p * 2), ("H", ctypes.c_int32 * 2)] +
+                _ptr_fields("actions", "log_std", "mask") + [("R", ctypes.c_int64)] + _i32s("A", "box"))
+
+
+class RecurrentHeadsGrads(ctypes.Structure):
+    """Mirror of ``agx_recurrent_heads_grads``."""
+
+    _fields_ = (_ptr_fields("g_log_prob", "g_entropy", "g_value") +
+                [(n, ctypes.c_void_p * 2) for n in ("dh_top", "out_w", "out_b")] +
+                [("head", (RecurrentLinearGrad * RECURRENT_MAX_HEAD) * 2)] + _ptr_fields("log_std"))
+
+
+def _recurrent_heads_plan(actor, critic):
+    """(the two networks' plans, A, box, the parameter list of ``recurrent_heads_params``) or None."""
+    from .modules._hooks import hooked
+
+    space = actor.action_space
+    box = not hasattr(space, "n")
+    A = int(space.shape[0]) if box else int(space.n)
+    head = getattr(actor, "head_net", None)
+    if not 1 <= A <= RECURRENT_MAX_ACTIONS or hooked(actor, critic):
+        return None
+    pa, pc = _recurrent_net(actor, getattr(head, "_wrapped", None), A), _recurrent_net(critic, critic.head_net, 1)
+    if pa is None or pc is None:
+        return None
+    if box and (head.log_std.dtype != _f32 or not head.log_std.is_cuda or head.log_std.numel() != A):
+        return None
+    ts = []
+    for _, _, out, _, layers in (pa, pc):
+        ts += [out.weight, out.bias]
+        for lin, ln, _ in layers:
+            ts += [lin.weight, lin.bias] + ([ln.weight, ln.bias] if ln is not None else [])
+    return (pa, pc), A, box, ts + ([head.log_std] if box else [])
+
+
+def recurrent_heads_params(actor, critic):
+    """The parameters ``recurrent_heads_forward`` reads, in the order ``recurrent_heads_backward`` returns their
+    gradients: per network (actor, critic) the output Linear's weight and bias, then each head layer's weight,
+    bias and LayerNorm affine; ``log_std`` last (Box).  None where the kernels do not apply (the limits of
+    ``ppo_act_recurrent``, include/agx_recurrent.h)."""
+    found = _recurrent_heads_plan(actor, critic)
+    return None if found is None else found[3]
+
+
+def _recurrent_heads(actor, critic, h_top, actions, mask):
+    """-> (the descriptor, the two plans, the parameter list, tensors the descriptor points into) or None."""
+    found = _recurrent_heads_plan(actor, critic)
+    if found is None:
+        return None
+    plans, A, box, params = found
+    R = h_top[0].shape[0] if isinstance(h_top[0], torch.Tensor) and h_top[0].dim() == 2 else 0
+    if not 1 <= R <= _lstm._MAX_ROWS or (box and mask is not None):
+        return None
+    s = RecurrentHeads()
+    for k, (plan, h) in enumerate(zip(plans, h_top)):
+        H = plan[1][0][1]
+        if not isinstance(h, torch.Tensor) or tuple(h.shape) != (R, H) or h.dtype != _f32 or not h.is_cuda or \
+                not h.is_contiguous():
+            return None
+        _fill_recurrent_dense(s.net[k], plan)
+        s.h_top[k], s.H[k] = h.data_ptr(), H
+    if not isinstance(actions, torch.Tensor) or actions.dtype != _f32 or not actions.is_cuda or \
+            not actions.is_contiguous() or tuple(actions.shape) != ((R, A) if box else (R,)):
+        return None
+    keep = [actions]
+    if mask is not None:
+        mask = torch.as_tensor(mask)
+        mask = (mask.view(_u8) if mask.dtype == torch.bool else mask.to(_u8)).to(actions.device).reshape(R, A)
+        keep.append(mask := mask.contiguous())
+        s.mask = mask.data_ptr()
+    s.actions, s.R, s.A, s.box = actions.data_ptr(), R, A, int(box)
+    if box:
+        s.log_std = actor.head_net.log_std.data_ptr()
+    return s, plans, params, keep
+
+
+def recurrent_heads_forward(actor, critic, h_top, actions, mask=None, *, save=True):
+    """agx_recurrent_heads_forward: everything after the LSTMs of a ``StochasticActor`` / ``ValueNetwork`` pair over
+    R padded rows in one launch.  h_top: (actor's, critic's) top-layer LSTM output f32 [R, H]; actions f32 [R]
+    (Discrete, the index) or [R, A] (Box); mask uint8 / bool [R, A] or None.  -> (log_prob, entropy, value [R],
+    saved: what ``recurrent_heads_backward`` reads, None without ``save``), or None where the kernels do not
+    apply (the caller runs the torch modules)."""
+    found = _recurrent_heads(actor, critic, h_top, actions, mask)
+    if found is None:
+        return None
+    s = found[0]
+    dev = actions.device
+    out = torch.empty(3, s.R, dtype=_f32, device=dev)
+    saved = None
+    if save:
+        saved = torch.empty(_lib.load().agx_recurrent_heads_saved_bytes(ctypes.byref(s)) // 4, dtype=_f32, device=dev)
+    _lib.call("agx_recurrent_heads_forward", ctypes.byref(s), out[0].data_ptr(), out[1].data_ptr(),
+              out[2].data_ptr(), _lib.ptr(saved), _lib.stream())
+    return out[0], out[1], out[2], saved
+
+
+def recurrent_heads_backward(actor, critic, h_top, actions, mask, saved, g_log_prob, g_entropy, g_value):
+    """agx_recurrent_heads_backward on the inputs and ``saved`` of ``recurrent_heads_forward`` and the upstream
+    gradients f32 [R]: two launches.  -> (dh_top of the actor, of the critic [R, H], the gradients of
+    ``recurrent_heads_params`` in its order), or None where the kernels do not apply."""
+    found = _recurrent_heads(actor, critic, h_top, actions, mask)
+    if found is None:
+        return None
+    s, plans, params, _ = found
+    R = s.R
+    for t, n in ((g_log_prob, "g_log_prob"), (g_entropy, "g_entropy"), (g_value, "g_value")):
+        _need(t, n, _f32, (R,))
+    g = RecurrentHeadsGrads()
+    g.g_log_prob, g.g_entropy, g.g_value = g_log_prob.data_ptr(), g_entropy.data_ptr(), g_value.data_ptr()
+    dh = [torch.empty_like(h) for h in h_top]
+    grads = [torch.empty_like(t) for t in params]
+    it = iter(grads)
+    for k, (_, _, _, _, layers) in enumerate(plans):
+        g.dh_top[k], g.out_w[k], g.out_b[k] = dh[k].data_ptr(), next(it).data_ptr(), next(it).data_ptr()
+        for j, (_, ln, _) in enumerate(layers):
+            e = g.head[k][j]
+            e.w, e.b = next(it).data_ptr(), next(it).data_ptr()
+            if ln is not None:
+                e.ln_w, e.ln_b = next(it).data_ptr(), next(it).data_ptr()
+    if s.box:
+        g.log_std = next(it).data_ptr()
+    ws = torch.empty(_lib.load().agx_recurrent_heads_workspace_bytes(ctypes.byref(s)) // 4, dtype=_f32,
+                     device=actions.device)
+    _lib.call("agx_recurrent_heads_backward", ctypes.byref(s), saved.data_ptr(), ctypes.byref(g), ws.data_ptr(),
+              _lib.stream())
+    return dh[0], dh[1], grads

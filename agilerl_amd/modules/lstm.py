@@ -121,7 +121,8 @@ class EvolvableLSTM(nn.Module):
     def lstm(self) -> nn.LSTM:
         return self.model[f"{self.name}_lstm"]
 
-    def forward(self, x, hidden_state: dict[str, torch.Tensor] | None = None):
+    def lstm_output(self, x, hidden_state: dict[str, torch.Tensor] | None = None):
+        """The ``nn.LSTM``'s half of ``forward``: -> (the top layer's output, [rows, H] for 2-D input, h_n, c_n)."""
         if not isinstance(x, torch.Tensor):
             x = torch.tensor(np.asarray(x), dtype=torch.float32, device=self.device)
         x_shape = x.shape
@@ -139,6 +140,10 @@ class EvolvableLSTM(nn.Module):
         fused = lstm_sequence(self, x, h0, c0) if _faster(self) else None
         out, (h_n, c_n) = (fused[0], fused[1:]) if fused is not None else self.lstm(x, (h0, c0))
         out = out.reshape(out.shape[0] * out.shape[1], out.shape[2]) if sequence_input else out.squeeze(1)
+        return out, h_n, c_n
+
+    def forward(self, x, hidden_state: dict[str, torch.Tensor] | None = None):
+        out, h_n, c_n = self.lstm_output(x, hidden_state)
         out = self.model[f"{self.name}_lstm_output"](out)
         out = self.model[f"{self.name}_output_activation"](out)
         return out, {**hidden_state, f"{self.name}_h": h_n, f"{self.name}_c": c_n}

@@ -18,6 +18,11 @@ Discrete(4), one LSTM layer of H = 64 per encoder, max_seq_len 16 (CHUNKED), 64 
       compute_returns_and_advantages (the
       GAE launch both learners need before each learn) is outside the timed span.  One JSON line, also
       written to --out.  Not measured: kernel times (no profiler run), other shapes, AGX_LSTM=1.
+
+  python tools/bptt_time.py --heads [--out profiles/bptt_time.json]
+      learn() on the same buffer with the fused heads (AGX_RECURRENT_LEARN) off, which is the path
+      without them, and on, each with AGX_LSTM unset and AGX_LSTM=1: four settings of one agent in the same
+      alternating blocks.  Added to --out under "learn_heads"; the file's other keys are kept.
 """
 import copy
 import json
@@ -149,10 +154,63 @@ def torch_learn(ref, host):
     return total / count
 
 
-def main():
+def block(fn, before, calls):
+    """Mean seconds per call of ``calls`` calls, each between two device synchronises; ``before`` is not timed."""
     import torch
 
+    spans = []
+    for _ in range(calls):
+        if before is not None:
+            before()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        spans.append(time.perf_counter() - t0)
+    return sum(spans) / len(spans)
+
+
+def spread(v):
+    return {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)}
+
+
+HEADS = {"heads off": (None, "0"), "heads on": (None, "1"), "AGX_LSTM=1, heads off": ("1", "0"),
+         "AGX_LSTM=1, heads on": ("1", "1")}  # setting -> (AGX_LSTM, AGX_RECURRENT_LEARN)
+
+
+def heads(out_path):
+    agent = setup()
+
+    def learn(setting):
+        lstm, switch = HEADS[setting]
+        os.environ.pop("AGX_LSTM", None)
+        if lstm is not None:
+            os.environ["AGX_LSTM"] = lstm
+        os.environ["AGX_RECURRENT_LEARN"] = switch
+        return block(agent.learn, lambda: gae(agent), CALLS["learn"])
+
+    for setting in HEADS:  # warm-up of every setting
+        learn(setting)
+    times = {setting: [] for setting in HEADS}
+    for _ in range(ROUNDS):  # alternating blocks
+        for setting in HEADS:
+            times[setting].append(1e3 * learn(setting))
+    result = {}
+    if out_path and os.path.exists(out_path):
+        with open(out_path) as f:
+            result = json.load(f)
+    result["learn_heads"] = {"unit": "ms per learn()", "calls_per_block": CALLS["learn"], "blocks": ROUNDS,
+                             **{setting: spread(v) for setting, v in times.items()}}
+    print(json.dumps(result["learn_heads"]))
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
+def main():
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+    if "--heads" in sys.argv:
+        return heads(out_path)
     agent = setup()
     ref = copy.deepcopy(agent)
     ref.reinit_optimizers()
@@ -175,18 +233,6 @@ def main():
     def ref_learn():
         torch_learn(ref, host)
 
-    def block(fn, before, calls):
-        spans = []
-        for _ in range(calls):
-            if before is not None:
-                before()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            spans.append(time.perf_counter() - t0)
-        return sum(spans) / len(spans)
-
     pairs = {"prepare": ((agx_prepare, None), (ref_prepare, None)),
              "learn": ((agx_learn, lambda: gae(agent)), (ref_learn, None))}
     result = {"shape": dict(T=T, N=N, obs=OBS, actions=ACTIONS, H=H, layers=1, max_seq_len=MAX_SEQ_LEN,
@@ -199,7 +245,7 @@ def main():
         for _ in range(ROUNDS):  # alternating blocks
             for side, (fn, before) in zip(times, sides):
                 times[side].append(1e3 * block(fn, before, CALLS[name]))
-        result[name] = {s: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for s, v in times.items()}
+        result[name] = {s: spread(v) for s, v in times.items()}
     result["sequences"] = dict(S=buf.num_sequences, L=buf.max_sequence_length)
     result["not_measured"] = "kernel times (no profiler run), other shapes, AGX_LSTM=1"
     line = json.dumps(result)
