@@ -27,8 +27,10 @@ the heads, the log-prob and the entropy of both networks are one
 agx_recurrent_heads_forward launch with a two-launch backward
 (include/agx_recurrent_heads.h) wherever the limits hold.  Off by default.
 
-``share_encoders=True``, image / Dict observations, MultiDiscrete /
-MultiBinary actions and ``squash_output`` raise.
+Action spaces: Discrete, 1-D Box, 1-D MultiDiscrete and 1-D MultiBinary, each
+on both paths; the last two on a CUDA device only (on the CPU the agent keeps
+refusing them, as it did before they existed).  ``share_encoders=True``, image
+/ Dict observations and ``squash_output`` raise.
 """
 
 from __future__ import annotations
@@ -129,6 +131,9 @@ class RecurrentPPO(PPO):
         self.rollout_buffer_config = dict(rollout_buffer_config or {})
         self.max_seq_len, self.bptt_sequence_type = max_seq_len, bptt_sequence_type
         self.device = torch.device(device)
+        if (K.recurrent_head(action_space) or (0,))[0] >= K.HEAD_MULTI and self.device.type != "cuda":
+            # as before this change: off the GPU the agent is built for Discrete and Box only
+            raise NotImplementedError("agx recurrent PPO: MultiDiscrete / MultiBinary actions need a CUDA device")
         self.training = True
         self.registry = MutationRegistry(hp_config)
         self.scores, self.fitness, self.steps = [], [], [0]
@@ -150,7 +155,9 @@ class RecurrentPPO(PPO):
                                      device=self.device, recurrent=True, encoder_name="actor_encoder", **cfg)
         self.critic = ValueNetwork(observation_space, device=self.device, recurrent=True,
                                    encoder_name="critic_encoder", **critic_cfg)
-        self.discrete = hasattr(action_space, "n")
+        # the distribution: kernels.HEAD_*, and how many columns a row of stored actions has
+        self.head_kind, _, _, self.action_cols = K.recurrent_head(action_space)
+        self.discrete = self.head_kind == K.HEAD_DISCRETE
         self.reinit_optimizers()
         self.create_rollout_buffer()
 
@@ -234,6 +241,17 @@ class RecurrentPPO(PPO):
             self._act_counter += 1
         return res
 
+    def host_action(self, action: np.ndarray) -> np.ndarray:
+        """A step's actions [N, columns] as ``get_action`` returns them: int64 [N] (Discrete) or [N, K]
+        (MultiDiscrete), [N, n] of the space's dtype (MultiBinary), float32 [N, A] (Box)."""
+        if self.head_kind == K.HEAD_DISCRETE:
+            return action.reshape(action.shape[0]).astype(np.int64)
+        if self.head_kind == K.HEAD_MULTI:
+            return action.astype(np.int64)
+        if self.head_kind == K.HEAD_BERNOULLI:
+            return action.astype(self.action_space.dtype)
+        return action
+
     def evaluate_actions(self, obs, actions, hidden_state=None, action_mask=None):
         """-> (log_prob, entropy, values) of ``actions`` (ppo.py:529-565); with [layers, B, H] states and
         B * L rows of observations the rows are B sequences of L steps."""
@@ -248,17 +266,16 @@ class RecurrentPPO(PPO):
         if res is not None:  # one launch, then one read of what it returned
             host = torch.cat([res["actions"].reshape(-1), res["log_probs"], res["entropy"], res["values"]]).cpu()
             n = obs.shape[0]
-            action = host[:-3 * n].reshape(n, -1).numpy()
-            action = action[:, 0].astype(np.int64) if self.discrete else action
-            if not self.training and not self.discrete:
+            action = self.host_action(host[:-3 * n].reshape(n, -1).numpy())
+            if not self.training and self.head_kind == K.HEAD_BOX:
                 action = np.clip(action, self.action_space.low, self.action_space.high)
             log_prob, entropy, values = host[-3 * n:].reshape(3, n).numpy()
             return action, log_prob, entropy, values, res["hidden"]
         with torch.no_grad():
             action, log_prob, entropy, values, next_hidden = self._get_action_and_values(obs, action_mask,
                                                                                          hidden_state, sample=True)
-        action = action.cpu().numpy()
-        if not self.training and not self.discrete:
+        action = self.host_action(action.cpu().numpy())
+        if not self.training and self.head_kind == K.HEAD_BOX:
             action = np.clip(action, self.action_space.low, self.action_space.high)
         return action, log_prob.cpu().numpy(), entropy.cpu().numpy(), values.cpu().numpy(), next_hidden
 
@@ -282,14 +299,14 @@ class RecurrentPPO(PPO):
         if not self.fused_learn_on() or not isinstance(actions, torch.Tensor) or actions.device.type != "cuda":
             return None
         params = K.recurrent_heads_params(self.actor, self.critic)
-        if params is None or (action_mask is not None and not self.discrete):
+        if params is None or (action_mask is not None and self.head_kind == K.HEAD_BOX):
             return None
         obs = self.preprocess_observation(obs)
         h_top = [net.encoder.lstm_output(obs, hidden_state)[0] for net in (self.actor, self.critic)]
         if any(h.dim() != 2 or h.dtype != torch.float32 for h in h_top):
             return None
         actions = actions.to(torch.float32).contiguous()
-        if actions.shape != ((h_top[0].shape[0],) if self.discrete else (h_top[0].shape[0], params[-1].numel())):
+        if actions.shape != ((h_top[0].shape[0],) if self.discrete else (h_top[0].shape[0], self.action_cols)):
             return None
         return HeadsFn.apply(self.actor, self.critic, actions, action_mask, *h_top, *params)
 

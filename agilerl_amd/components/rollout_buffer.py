@@ -33,7 +33,7 @@ def _obs_shape(space) -> tuple[int, ...]:
 
 
 def _num_actions(space) -> int:
-    if hasattr(space, "n"):  # Discrete
+    if hasattr(space, "n") and not getattr(space, "shape", None):  # Discrete
         return 1
     return int(np.prod(space.shape))
 
@@ -153,9 +153,7 @@ class RolloutBuffer:
         if res is None:
             return None
         host = torch.cat([out["actions"].reshape(-1), out["log_probs"], out["values"]]).cpu().numpy()
-        action = host[:-2 * N].reshape(N, -1)
-        action = action[:, 0].astype(np.int64) if hasattr(self.action_space, "n") else action
-        return action, host[-2 * N:-N], host[-N:], res["hidden"]
+        return agent.host_action(host[:-2 * N].reshape(N, -1)), host[-2 * N:-N], host[-N:], res["hidden"]
 
     def finish_step(self, reward, done, next_obs=None, action_mask=None) -> None:
         """The host's half of a slot ``fused_step`` wrote: what the env returned, then the slot is taken."""

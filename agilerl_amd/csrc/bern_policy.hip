@@ -19,17 +19,6 @@
 namespace agx {
 namespace {
 
-// the uniform of flat index j of stream env `env`: the u of gumbel_score
-// (rollout.h), word j & 3 of the block of (env, counter ^ (j >> 2) << 56)
-__device__ __forceinline__ float bern_uniform(int j, unsigned long long env, unsigned long long seed,
-                                              unsigned long long counter) {
-    const uint4 rnd = philox(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)counter,
-                                        (unsigned)(counter >> 32) ^ ((unsigned)(j >> 2) << 24)),
-                             make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-    const unsigned w = (j & 3) == 0 ? rnd.x : (j & 3) == 1 ? rnd.y : (j & 3) == 2 ? rnd.z : rnd.w;
-    return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f);
-}
-
 // what the Bernoulli step writes besides the ActArgs' log_probs / values / entropy
 struct BernOut {
     long long *act_out;   // agent p, env r, bit j at ((p out_pstride + r) n + j)

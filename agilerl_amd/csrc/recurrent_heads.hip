@@ -12,7 +12,10 @@
 // saving form copies each tile a later layer's gradient needs to `saved` when
 // it is whole: the latent, every hidden layer's output, the pre-LayerNorm
 // output of LayerNorm layers, and the actor's masked logits (or means).  The
-// epilogue is 16 lanes per row, entries a and a + 16 per lane.
+// epilogue is 16 lanes per row, entries a and a + 16 per lane; the
+// multi-categorical and Bernoulli heads take 32 lanes per row over all 8 waves,
+// one logit per lane, with per-component segmented scans (seg_scan.h), in the
+// forward and in the backward's logit gradient alike.
 //
 // Backward rows, the same grid, two LDS slots.  The gradient of the last
 // layer's output is formed in registers from the saved logits (softmax and the
@@ -36,9 +39,12 @@
 #include "../../include/agx_recurrent_heads.h"
 
 #include "agx_common.h"
+#include "bern_head.h"
 #include "gauss_head.h"
 #include "lstm_gates.h"
+#include "multi_head_check.h"
 #include "recurrent_dense.h"
+#include "seg_scan.h"
 
 namespace agx {
 namespace {
@@ -68,6 +74,7 @@ struct RowArgs {
     const float *actions, *log_std;
     const uint8_t *mask;
     int R, A, box, slot;
+    unsigned starts;                              // the multi head (seg_scan.h)
     float *log_prob, *entropy, *value;            // forward
     float *saved;                                 // forward: written (or null); backward: read
     float *ws;                                    // backward
@@ -186,6 +193,61 @@ __device__ __forceinline__ void gauss_rows(const RowArgs &a, const float *Y, int
     }
 }
 
+// One lane's share of the K categoricals over the (masked) logit lg of lane g: the log-sum-exp of its component
+// and its own probability
+struct MultiLane {
+    float lse, p;
+};
+__device__ __forceinline__ MultiLane multi_lane(const SegLane &g, float lg) {
+    const float mx = seg_total(g, seg_scan_max(g, lg));
+    MultiLane m;
+    m.lse = mx + logf(seg_total(g, seg_scan_sum(g, g.on ? expf(lg - mx) : 0.f)));
+    m.p = g.on ? expf(lg - m.lse) : 0.f;
+    return m;
+}
+// component k's action of a live row, clamped into [0, n_k), as a flat logit index
+__device__ __forceinline__ int multi_action(const RowArgs &a, const SegLane &g, int row) {
+    const int act = (int)a.actions[(int64_t)row * __popc(a.starts) + g.k];
+    return g.first + min(max(act, 0), g.last - g.first);
+}
+
+// the multi-categorical log-prob of the given actions and the entropy over the 16 rows of logits Y [16][ld]
+__device__ __forceinline__ void multi_rows(const RowArgs &a, const float *Y, int ld, int b0, float *keep) {
+    const SegLane g = seg_lane(a.starts, a.A);
+    const int A = a.A, row = b0 + g.rl;
+    const bool live = row < a.R;
+    float lg = g.on ? Y[g.rl * ld + g.j] : -3.0e38f;
+    if (a.mask && live && g.on && !a.mask[(size_t)row * A + g.j]) lg = -1.0e8f;
+    if (keep && live && g.on) keep[(int64_t)row * A + g.j] = lg;
+    const MultiLane m = multi_lane(g, lg);
+    const float nh = seg_scan_sum(g, g.on ? m.p * logf(m.p + 1e-8f) : 0.f);
+    const float H = -row32_sum(g.on && g.j == g.last ? nh : 0.f);
+    const bool taken = live && g.on && g.j == multi_action(a, g, row);
+    const float lp = row32_sum(taken ? lg - m.lse : 0.f);
+    if (live && g.j == 0) {
+        a.entropy[row] = H;
+        a.log_prob[row] = lp;
+    }
+}
+
+// the Bernoulli log-prob of the given bits and the entropy over the 16 rows of logits Y [16][ld]
+__device__ __forceinline__ void bern_rows(const RowArgs &a, const float *Y, int ld, int b0, float *keep) {
+    const SegLane g = bit_lane(a.A);
+    const int A = a.A, row = b0 + g.rl;
+    const bool live = row < a.R;
+    float lg = g.on ? Y[g.rl * ld + g.j] : 0.f;
+    if (a.mask && live && g.on && !a.mask[(size_t)row * A + g.j]) lg = -1.0e8f;
+    if (keep && live && g.on) keep[(int64_t)row * A + g.j] = lg;
+    const BernBit b = bern_bit(lg);
+    const bool one = live && g.on && a.actions[(int64_t)row * A + g.j] != 0.f;
+    const float H = -row32_sum(g.on ? bern_neg_entropy(b) : 0.f);
+    const float lp = row32_sum(g.on ? (one ? b.lp : b.lq) : 0.f);
+    if (live && g.j == 0) {
+        a.entropy[row] = H;
+        a.log_prob[row] = lp;
+    }
+}
+
 template <bool SAVE>
 __global__ __launch_bounds__(kRT) void heads_fwd_kernel(const RowArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -227,8 +289,12 @@ __global__ __launch_bounds__(kRT) void heads_fwd_kernel(const RowArgs a) {
     if (critic) {
         const int row = b0 + threadIdx.x;
         if (threadIdx.x < 16 && row < R) a.value[row] = Y[threadIdx.x * ldY];
-    } else if (a.box) {
+    } else if (a.box == AGX_RECURRENT_HEAD_BOX) {
         gauss_rows(a, Y, ldY, b0, keep);
+    } else if (a.box == AGX_RECURRENT_HEAD_MULTI) {
+        multi_rows(a, Y, ldY, b0, keep);
+    } else if (a.box == AGX_RECURRENT_HEAD_BERNOULLI) {
+        bern_rows(a, Y, ldY, b0, keep);
     } else {
         categorical_rows(a, Y, ldY, b0, keep);
     }
@@ -278,6 +344,32 @@ __device__ __forceinline__ void head_grad_rows(const RowArgs &a, const Net &n, b
     }
     g[a0] = on0 ? v0 : 0.f;
     if (A > 16) g[a1] = on1 ? v1 : 0.f;
+}
+
+// head_grad_rows for the actor's multi-categorical and Bernoulli heads, 32 lanes per row.  With gl / ge the row's
+// upstream gradients of log_prob / entropy: multi gl ([j == off_k + a_k] - p_j) + ge p_j (t_j - sum_{i in k} p_i t_i),
+// t = -(log(p + eps) + p / (p + eps)), the inner sum one more segmented scan; Bernoulli gl (a_j - p_j) + ge dH / dl_j
+// (bern_head.h).  A masked logit gets exactly 0.
+__device__ __forceinline__ void head_grad_rows32(const RowArgs &a, const Net &n, float *G, int ld, int b0) {
+    const bool multi = a.box == AGX_RECURRENT_HEAD_MULTI;
+    const SegLane g = multi ? seg_lane(a.starts, a.A) : bit_lane(a.A);
+    const int A = a.A, row = b0 + g.rl;
+    const bool live = row < a.R, on = live && g.on;
+    const float gl = live ? a.g_lp[row] : 0.f, ge = live ? a.g_ent[row] : 0.f;
+    const float lg = on ? a.saved[n.sv_out + (int64_t)row * A + g.j] : (g.on ? 0.f : -3.0e38f);
+    float v;
+    if (multi) {
+        const MultiLane m = multi_lane(g, lg);
+        const float t = -(logf(m.p + 1e-8f) + m.p / (m.p + 1e-8f));
+        const float pt = seg_total(g, seg_scan_sum(g, g.on ? m.p * t : 0.f));
+        const bool taken = on && g.j == multi_action(a, g, row);
+        v = gl * ((taken ? 1.f : 0.f) - m.p) + ge * (m.p * (t - pt));
+    } else {
+        const BernBit b = bern_bit(g.on ? lg : 0.f);
+        v = gl * bern_dlogp(b, on && a.actions[(int64_t)row * A + g.j] != 0.f) + ge * bern_dH(b);
+    }
+    if (a.mask && on && !a.mask[(size_t)row * A + g.j]) v = 0.f;
+    if (g.j < r16(A)) G[g.rl * ld + g.j] = on ? v : 0.f;
 }
 
 // dA -> dZ of hidden head layer j over the rows of G [16][ld] in place: the ReLU mask from the layer's saved output,
@@ -345,7 +437,10 @@ __global__ __launch_bounds__(kRT) void heads_bwd_rows_kernel(const RowArgs a) {
     int side = 0;
     float *G = lds;
     int F = n.head[n.n_head - 1].out, ldG = r16(F) + 4;
-    head_grad_rows(a, n, critic, G, ldG, b0);
+    if (!critic && a.box >= AGX_RECURRENT_HEAD_MULTI)
+        head_grad_rows32(a, n, G, ldG, b0);
+    else
+        head_grad_rows(a, n, critic, G, ldG, b0);
     __syncthreads();
     for (int j = n.n_head - 1; j >= 0; --j) {
         const agx_recurrent_linear &hl = n.head[j];
@@ -515,7 +610,15 @@ int check_heads(const agx_recurrent_heads *heads, const char *who) {
     AGX_REQUIRE(s.A >= 1 && s.A <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d actions (1..%d)", who, s.A,
                 AGX_PPO_GRAPH_MAX_ACTIONS);
     AGX_REQUIRE(s.actions, "%s: actions is NULL", who);
-    AGX_REQUIRE(s.box ? (s.log_std && !s.mask) : !s.log_std, "%s: log_std goes with Box, a mask with Discrete", who);
+    AGX_REQUIRE(s.box >= AGX_RECURRENT_HEAD_DISCRETE && s.box <= AGX_RECURRENT_HEAD_BERNOULLI, "%s: head kind %d", who,
+                s.box);
+    AGX_REQUIRE(s.box == AGX_RECURRENT_HEAD_BOX ? (s.log_std && !s.mask) : !s.log_std,
+                "%s: log_std goes with Box, a mask with the other heads", who);
+    if (s.box == AGX_RECURRENT_HEAD_MULTI) {
+        const int L = head_width(s.multi, who);
+        if (L < 0) return AGX_EINVAL;
+        AGX_REQUIRE(L == s.A, "%s: nvec sums to %d, the head has %d logits", who, L, s.A);
+    }
     if (int rc = check_net(s.net[0], s.H[0], s.h_top[0], s.A, "actor", who)) return rc;
     return check_net(s.net[1], s.H[1], s.h_top[1], 1, "critic", who);
 }
@@ -576,6 +679,7 @@ RowArgs row_args(const agx_recurrent_heads &s, int64_t &saved, int64_t &ws) {
     a.R = (int)s.R;
     a.A = s.A;
     a.box = s.box;
+    a.starts = s.box == AGX_RECURRENT_HEAD_MULTI ? multi_starts(s.multi) : 0;
     const int wa = widest(a.net[0]), wc = widest(a.net[1]);
     a.slot = 16 * ((((wa > wc ? wa : wc) + 15) & ~15) + 4);
     return a;
@@ -642,7 +746,8 @@ extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, co
     const agx_recurrent_heads &s = *heads;
     const agx_recurrent_heads_grads &g = *grads;
     AGX_REQUIRE(g.g_log_prob && g.g_entropy && g.g_value, "%s: an upstream gradient is NULL", who);
-    AGX_REQUIRE(!s.box == !g.log_std, "%s: log_std's gradient goes with Box", who);
+    AGX_REQUIRE((s.box == AGX_RECURRENT_HEAD_BOX) == (g.log_std != nullptr), "%s: log_std's gradient goes with Box",
+                who);
     for (int k = 0; k < 2; ++k) {
         AGX_REQUIRE(g.dh_top[k] && g.out_w[k] && g.out_b[k], "%s: network %d: a gradient output is NULL", who, k);
         for (int j = 0; j < s.net[k].n_head; ++j) {
@@ -690,7 +795,7 @@ extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, co
                 jobs += (n.head[j].out + 63) / 64;
             }
     }
-    p.ls_job = s.box ? jobs++ : -1;
+    p.ls_job = s.box == AGX_RECURRENT_HEAD_BOX ? jobs++ : -1;
     p.n_jobs = jobs;
     p.R = (int)s.R;
     p.A = s.A;

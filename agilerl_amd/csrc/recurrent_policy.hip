@@ -36,21 +36,47 @@
 // Epilogue, 16 lanes per row, entries a and a + 16 per lane, with the
 // operation order of the categorical step of graph_rollout.hip and of
 // gauss_policy.hip's gauss_step, on rollout.h's and gauss_head.h's streams.
+// The multi-categorical and Bernoulli epilogues take all 8 waves, 32 lanes per
+// row and one logit per lane (seg_scan.h): a component is a run of lanes, and
+// its max, sum exp, entropy and Gumbel arg-max are segmented scans whose cost
+// does not depend on the number of components.
 #include "../../include/agx_recurrent.h"
 
+#include <cstddef>
+#include <cstring>
+
 #include "agx_common.h"
+#include "bern_head.h"
 #include "gauss_head.h"
 #include "lstm_gates.h"
+#include "multi_head_check.h"
 #include "recurrent_dense.h"
 #include "rollout.h"
+#include "seg_scan.h"
 
 namespace agx {
 namespace {
 
 constexpr int kLdsCap = 160 * 1024;
 
+// What the kernel takes by value: agx_recurrent_step up to `multi`, field for field, with the multi head reduced
+// to `starts` (seg_scan.h) in the place of the pad word.  1200 bytes as before the multi head, 1204 with the slot
+// width: under the 4 KB of kernel arguments (the 132-byte agx_multi_head stays on the host).
+struct StepArgs {
+    agx_recurrent_net actor, critic;
+    const float *obs, *log_std;
+    const uint8_t *reset, *mask;
+    int64_t N;
+    int32_t A, box, sample;
+    uint32_t starts;
+    uint64_t seed, counter;
+    float *actions, *log_probs, *entropy, *values, *obs_store;
+};
+static_assert(sizeof(StepArgs) == offsetof(agx_recurrent_step, multi), "StepArgs mirrors agx_recurrent_step");
+static_assert(sizeof(StepArgs) + sizeof(int) <= 4096, "the kernel arguments pass 4 KB");
+
 // The categorical step of the 16 rows of logits Y [16][ld]: graph_rollout.hip's graph_sample, the action as a float
-__device__ __forceinline__ void categorical_step(const agx_recurrent_step &s, const float *Y, int ld, int b0) {
+__device__ __forceinline__ void categorical_step(const StepArgs &s, const float *Y, int ld, int b0) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave >= 4) return;
     const int sub = lane & 15, rl = 4 * wave + (lane >> 4);
@@ -87,7 +113,7 @@ __device__ __forceinline__ void categorical_step(const agx_recurrent_step &s, co
 }
 
 // The Gaussian step of the 16 rows of means Y [16][ld]: gauss_policy.hip's gauss_step
-__device__ __forceinline__ void gauss_step(const agx_recurrent_step &s, const float *Y, int ld, int b0) {
+__device__ __forceinline__ void gauss_step(const StepArgs &s, const float *Y, int ld, int b0) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave >= 4) return;
     const int sub = lane & 15, rl = 4 * wave + (lane >> 4);
@@ -113,7 +139,54 @@ __device__ __forceinline__ void gauss_step(const agx_recurrent_step &s, const fl
     if (sub == 0 && s.log_probs) s.log_probs[row] = lp;
 }
 
-__global__ __launch_bounds__(kRT) void recurrent_step_kernel(const agx_recurrent_step s, const int slot) {
+// The multi-categorical step of the 16 rows of logits Y [16][ld]: the K categoricals of agx_multi.h, lane j of a
+// row on flat logit j.  Scores are keyed by the flat index, so one component of A choices makes categorical_step's
+// choices.
+__device__ __forceinline__ void multi_step(const StepArgs &s, const float *Y, int ld, int b0) {
+    const SegLane g = seg_lane(s.starts, s.A);
+    const int A = s.A, N = (int)s.N, row = b0 + g.rl;
+    const bool live = row < N;
+    float lg = g.on ? Y[g.rl * ld + g.j] : -3.0e38f;
+    if (s.mask && live && g.on && !s.mask[(size_t)row * A + g.j]) lg = -1.0e8f;
+    const float mx = seg_total(g, seg_scan_max(g, lg));
+    const float lse = mx + logf(seg_total(g, seg_scan_sum(g, g.on ? expf(lg - mx) : 0.f)));
+    const float p = g.on ? expf(lg - lse) : 0.f;
+    const bool tail = g.on && g.j == g.last;  // the lane that ends with its component's totals
+    const float nh = seg_scan_sum(g, g.on ? p * logf(p + 1e-8f) : 0.f);
+    const float H = -row32_sum(tail ? nh : 0.f);
+    if (live && g.j == 0 && s.entropy) s.entropy[row] = H;
+    if (!s.sample) return;  // uniform
+    const unsigned long long env = stream_env(-1, nullptr, 0, N, live ? row : 0);
+    float sc = g.on ? gumbel_score(lg, g.j, env, s.seed, s.counter) : -3.0e38f;
+    int ix = g.j;
+    seg_scan_argmax(g, sc, ix);
+    const float chosen = bperm(g.half + (tail ? ix : g.j), lg);
+    const float lp = row32_sum(tail ? chosen - lse : 0.f);
+    if (!live) return;
+    if (tail && s.actions) s.actions[(size_t)row * __popc(s.starts) + g.k] = (float)(ix - g.first);
+    if (g.j == 0 && s.log_probs) s.log_probs[row] = lp;
+}
+
+// The Bernoulli step of the 16 rows of logits Y [16][ld]: bern_policy.hip's bern_step, lane j of a row on bit j
+__device__ __forceinline__ void bern_step(const StepArgs &s, const float *Y, int ld, int b0) {
+    const SegLane g = bit_lane(s.A);
+    const int A = s.A, N = (int)s.N, row = b0 + g.rl;
+    const bool live = row < N;
+    float lg = g.on ? Y[g.rl * ld + g.j] : 0.f;
+    if (s.mask && live && g.on && !s.mask[(size_t)row * A + g.j]) lg = -1.0e8f;
+    const BernBit b = bern_bit(lg);
+    const float H = -row32_sum(g.on ? bern_neg_entropy(b) : 0.f);
+    if (live && g.j == 0 && s.entropy) s.entropy[row] = H;
+    if (!s.sample) return;  // uniform
+    const unsigned long long env = stream_env(-1, nullptr, 0, N, live ? row : 0);
+    const bool a = g.on && bern_uniform(g.j, env, s.seed, s.counter) < b.p;
+    const float lp = row32_sum(g.on ? (a ? b.lp : b.lq) : 0.f);
+    if (!live) return;
+    if (g.on && s.actions) s.actions[(size_t)row * A + g.j] = a ? 1.f : 0.f;
+    if (g.j == 0 && s.log_probs) s.log_probs[row] = lp;
+}
+
+__global__ __launch_bounds__(kRT) void recurrent_step_kernel(const StepArgs s, const int slot) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const bool critic = blockIdx.y != 0;
     const agx_recurrent_net &n = critic ? s.critic : s.actor;
@@ -215,8 +288,12 @@ __global__ __launch_bounds__(kRT) void recurrent_step_kernel(const agx_recurrent
     if (critic) {
         const int row = b0 + threadIdx.x;
         if (threadIdx.x < 16 && row < N && s.values) s.values[row] = Y[threadIdx.x * ldY];
-    } else if (s.box) {
+    } else if (s.box == AGX_RECURRENT_HEAD_BOX) {
         gauss_step(s, Y, ldY, b0);
+    } else if (s.box == AGX_RECURRENT_HEAD_MULTI) {
+        multi_step(s, Y, ldY, b0);
+    } else if (s.box == AGX_RECURRENT_HEAD_BERNOULLI) {
+        bern_step(s, Y, ldY, b0);
     } else {
         categorical_step(s, Y, ldY, b0);
     }
@@ -275,7 +352,19 @@ extern "C" int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *strea
     AGX_REQUIRE(s.A >= 1 && s.A <= AGX_PPO_GRAPH_MAX_ACTIONS, "%s: %d actions (1..%d)", who, s.A,
                 AGX_PPO_GRAPH_MAX_ACTIONS);
     AGX_REQUIRE(s.obs, "%s: obs is NULL", who);
-    AGX_REQUIRE(s.box ? (s.log_std && !s.mask) : !s.log_std, "%s: log_std goes with Box, a mask with Discrete", who);
+    AGX_REQUIRE(s.box >= AGX_RECURRENT_HEAD_DISCRETE && s.box <= AGX_RECURRENT_HEAD_BERNOULLI, "%s: head kind %d", who,
+                s.box);
+    AGX_REQUIRE(s.box == AGX_RECURRENT_HEAD_BOX ? (s.log_std && !s.mask) : !s.log_std,
+                "%s: log_std goes with Box, a mask with the other heads", who);
+    StepArgs k;
+    std::memcpy(&k, step, sizeof k);
+    k.starts = 0;
+    if (s.box == AGX_RECURRENT_HEAD_MULTI) {
+        const int L = head_width(s.multi, who);
+        if (L < 0) return AGX_EINVAL;
+        AGX_REQUIRE(L == s.A, "%s: nvec sums to %d, the head has %d logits", who, L, s.A);
+        k.starts = multi_starts(s.multi);
+    }
     if (int rc = check_net(s.actor, s.A, "actor", who)) return rc;
     if (int rc = check_net(s.critic, 1, "critic", who)) return rc;
     AGX_REQUIRE(s.actor.lstm.in == s.critic.lstm.in, "%s: the networks read observations of %d and %d floats", who,
@@ -290,6 +379,6 @@ extern "C" int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *strea
     }();
     (void)once;
     const dim3 grid((unsigned)ceil_div(s.N, 16), 2);
-    hipLaunchKernelGGL(recurrent_step_kernel, grid, dim3(kRT), bytes, as_stream(stream), s, slot);
+    hipLaunchKernelGGL(recurrent_step_kernel, grid, dim3(kRT), bytes, as_stream(stream), k, slot);
     return check_launch(who);
 }

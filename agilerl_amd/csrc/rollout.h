@@ -175,6 +175,17 @@ __device__ __forceinline__ float gumbel_score(float lg, int a, unsigned long lon
                                               unsigned long long counter) {
     return lg - gumbel_noise(a, env, seed, counter);
 }
+// The Bernoulli heads' draw (bern_policy.hip, recurrent_policy.hip): bit j is 1 iff bern_uniform < sigmoid(lg_j).
+// The uniform of flat index j of stream env `env`: the u of gumbel_score, word j & 3 of the block of
+// (env, counter ^ (j >> 2) << 56)
+__device__ __forceinline__ float bern_uniform(int j, unsigned long long env, unsigned long long seed,
+                                              unsigned long long counter) {
+    const uint4 rnd = philox(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)counter,
+                                        (unsigned)(counter >> 32) ^ ((unsigned)(j >> 2) << 24)),
+                             make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+    const unsigned w = (j & 3) == 0 ? rnd.x : (j & 3) == 1 ? rnd.y : (j & 3) == 2 ? rnd.z : rnd.w;
+    return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f);
+}
 
 // ---------------------------------------------------------------------------
 // host side

@@ -924,12 +924,40 @@ class RecurrentNet(ctypes.Structure):
 
 
 class RecurrentStep(ctypes.Structure):
-    """Mirror of ``agx_recurrent_step``."""
+    """Mirror of ``agx_recurrent_step`` up to ``multi``: the layout before the multi head was appended, which is
+    also what the kernel takes by value."""
 
     _fields_ = ([("actor", RecurrentNet), ("critic", RecurrentNet)] + _ptr_fields("obs", "log_std", "reset", "mask") +
                 [("N", ctypes.c_int64)] + _i32s("A", "box", "sample", "pad_") +
                 [("seed", ctypes.c_uint64), ("counter", ctypes.c_uint64)] +
                 _ptr_fields("actions", "log_probs", "entropy", "values", "obs_store"))
+
+
+class RecurrentStepMulti(RecurrentStep):
+    """Mirror of the whole ``agx_recurrent_step``: ``RecurrentStep`` and the ``agx_multi_head`` appended at its end
+    (offset 1200).  This is what ``agx_ppo_act_recurrent`` is given."""
+
+    _fields_ = [("multi", _lib.AgxMultiHead)]
+
+
+HEAD_DISCRETE, HEAD_BOX, HEAD_MULTI, HEAD_BERNOULLI = range(4)  # AGX_RECURRENT_HEAD_*
+
+
+def recurrent_head(space):
+    """(AGX_RECURRENT_HEAD_* kind, A: the width of the actor's head, nvec or None, the columns of a row of actions)
+    of an action space, or None for one the recurrent kernels have no head for.  MultiDiscrete and MultiBinary
+    are 1-D."""
+    nvec = getattr(space, "nvec", None)
+    if nvec is not None:
+        nvec = [int(n) for n in nvec] if len(getattr(space, "shape", ())) == 1 else []
+        return (HEAD_MULTI, sum(nvec), nvec, len(nvec)) if nvec and min(nvec) >= 1 else None
+    if type(space).__name__ == "MultiBinary":
+        return (HEAD_BERNOULLI, int(space.shape[0]), None, int(space.shape[0])) if len(space.shape) == 1 else None
+    if hasattr(space, "n"):
+        return HEAD_DISCRETE, int(space.n), None, 1
+    if hasattr(space, "low") and len(space.shape) == 1:
+        return HEAD_BOX, int(space.shape[0]), None, int(space.shape[0])
+    return None
 
 
 def _recurrent_net(net, head, n_out: int):
@@ -1014,12 +1042,15 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     slot) instead of new tensors; store_hidden {key: [N, L, H]} / store_obs [N, in]: the slot's copies of the
     states the step was taken from and of obs.  -> {"actions", "log_probs" (None without ``sample``), "entropy",
     "values", "hidden": the next states}, or None where the kernel does not apply (the caller runs the torch
-    modules): see include/agx_recurrent.h for the limits."""
+    modules): see include/agx_recurrent.h for the limits.  MultiDiscrete: mask [N, sum nvec], "actions" [N, K]
+    (each component's index); MultiBinary: mask and "actions" [N, n] (0 / 1)."""
     from .modules._hooks import hooked
 
-    space = actor.action_space
-    box = not hasattr(space, "n")
-    A = int(space.shape[0]) if box else int(space.n)
+    found = recurrent_head(actor.action_space)
+    if found is None:
+        return None
+    kind, A, nvec, cols = found
+    box = kind == HEAD_BOX
     head = getattr(actor, "head_net", None)
     if not 1 <= A <= RECURRENT_MAX_ACTIONS or hooked(actor, critic) or (box and mask is not None):
         return None
@@ -1033,7 +1064,7 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     N, dev = obs.shape[0], obs.device
     sizes = [p[1][0][2] * N * p[1][0][1] for p in (pa, pc)]  # L N H
     nxt = torch.empty(2 * sum(sizes), dtype=_f32, device=dev)
-    s = RecurrentStep()
+    s = RecurrentStepMulti()
     nh_a = _fill_recurrent_net(s.actor, pa, hidden, N, (nxt[:sizes[0]], nxt[sizes[0]:2 * sizes[0]]), store_hidden)
     nh_c = _fill_recurrent_net(s.critic, pc, hidden, N, (nxt[2 * sizes[0]:2 * sizes[0] + sizes[1]],
                                                           nxt[2 * sizes[0] + sizes[1]:]), store_hidden)
@@ -1042,7 +1073,7 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     out = out or {}
     res = {"actions": out.get("actions"), "log_probs": out.get("log_probs"), "values": out.get("values")}
     if sample and res["actions"] is None:
-        res["actions"] = torch.empty(N, A if box else 1, dtype=_f32, device=dev)
+        res["actions"] = torch.empty(N, cols, dtype=_f32, device=dev)
     small = torch.empty(3, N, dtype=_f32, device=dev)
     res["entropy"] = small[0]
     if res["values"] is None:
@@ -1050,17 +1081,19 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     if sample and res["log_probs"] is None:
         res["log_probs"] = small[2]
     if sample:
-        _need(res["actions"], "actions", _f32, (N, A if box else 1))
+        _need(res["actions"], "actions", _f32, (N, cols))
         _need(res["log_probs"], "log_probs", _f32, (N,))
         s.actions, s.log_probs = res["actions"].data_ptr(), res["log_probs"].data_ptr()
     else:
         res["actions"] = res["log_probs"] = None
     _need(res["values"], "values", _f32, (N,))
     s.entropy, s.values = res["entropy"].data_ptr(), res["values"].data_ptr()
-    s.obs, s.N, s.A, s.box, s.sample = obs.data_ptr(), N, A, int(box), int(bool(sample))
+    s.obs, s.N, s.A, s.box, s.sample = obs.data_ptr(), N, A, kind, int(bool(sample))
     s.seed, s.counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
     if box:
         s.log_std = head.log_std.data_ptr()
+    if kind == HEAD_MULTI:
+        s.multi = multi_head(nvec)
     keep = [nxt, small]
     for name, t, shape in (("mask", mask, (N, A)), ("reset", reset, (N,))):
         if t is None:
@@ -1087,10 +1120,17 @@ class RecurrentLinearGrad(ctypes.Structure):
 
 
 class RecurrentHeads(ctypes.Structure):
-    """Mirror of ``agx_recurrent_heads``."""
+    """Mirror of ``agx_recurrent_heads`` up to ``multi``: the layout before the multi head was appended."""
 
     _fields_ = ([("net", RecurrentNet * 2), ("h_top", ctypes.c_void_p * 2), ("H", ctypes.c_int32 * 2)] +
                 _ptr_fields("actions", "log_std", "mask") + [("R", ctypes.c_int64)] + _i32s("A", "box"))
+
+
+class RecurrentHeadsMulti(RecurrentHeads):
+    """Mirror of the whole ``agx_recurrent_heads``: ``RecurrentHeads`` and the ``agx_multi_head`` appended at its
+    end (offset 1152).  This is what the head kernels' entry points are given."""
+
+    _fields_ = [("multi", _lib.AgxMultiHead)]
 
 
 class RecurrentHeadsGrads(ctypes.Structure):
@@ -1102,12 +1142,14 @@ class RecurrentHeadsGrads(ctypes.Structure):
 
 
 def _recurrent_heads_plan(actor, critic):
-    """(the two networks' plans, A, box, the parameter list of ``recurrent_heads_params``) or None."""
+    """(the two networks' plans, ``recurrent_head`` of the action space, the parameter list of
+    ``recurrent_heads_params``) or None."""
     from .modules._hooks import hooked
 
-    space = actor.action_space
-    box = not hasattr(space, "n")
-    A = int(space.shape[0]) if box else int(space.n)
+    found = recurrent_head(actor.action_space)
+    if found is None:
+        return None
+    A, box = found[1], found[0] == HEAD_BOX
     head = getattr(actor, "head_net", None)
     if not 1 <= A <= RECURRENT_MAX_ACTIONS or hooked(actor, critic):
         return None
@@ -1121,7 +1163,7 @@ def _recurrent_heads_plan(actor, critic):
         ts += [out.weight, out.bias]
         for lin, ln, _ in layers:
             ts += [lin.weight, lin.bias] + ([ln.weight, ln.bias] if ln is not None else [])
-    return (pa, pc), A, box, ts + ([head.log_std] if box else [])
+    return (pa, pc), found, ts + ([head.log_std] if box else [])
 
 
 def recurrent_heads_params(actor, critic):
@@ -1130,7 +1172,7 @@ def recurrent_heads_params(actor, critic):
     bias and LayerNorm affine; ``log_std`` last (Box).  None where the kernels do not apply (the limits of
     ``ppo_act_recurrent``, include/agx_recurrent.h)."""
     found = _recurrent_heads_plan(actor, critic)
-    return None if found is None else found[3]
+    return None if found is None else found[2]
 
 
 def _recurrent_heads(actor, critic, h_top, actions, mask):
@@ -1138,11 +1180,12 @@ def _recurrent_heads(actor, critic, h_top, actions, mask):
     found = _recurrent_heads_plan(actor, critic)
     if found is None:
         return None
-    plans, A, box, params = found
+    plans, (kind, A, nvec, cols), params = found
+    box = kind == HEAD_BOX
     R = h_top[0].shape[0] if isinstance(h_top[0], torch.Tensor) and h_top[0].dim() == 2 else 0
     if not 1 <= R <= _lstm._MAX_ROWS or (box and mask is not None):
         return None
-    s = RecurrentHeads()
+    s = RecurrentHeadsMulti()
     for k, (plan, h) in enumerate(zip(plans, h_top)):
         H = plan[1][0][1]
         if not isinstance(h, torch.Tensor) or tuple(h.shape) != (R, H) or h.dtype != _f32 or not h.is_cuda or \
@@ -1151,7 +1194,7 @@ def _recurrent_heads(actor, critic, h_top, actions, mask):
         _fill_recurrent_dense(s.net[k], plan)
         s.h_top[k], s.H[k] = h.data_ptr(), H
     if not isinstance(actions, torch.Tensor) or actions.dtype != _f32 or not actions.is_cuda or \
-            not actions.is_contiguous() or tuple(actions.shape) != ((R, A) if box else (R,)):
+            not actions.is_contiguous() or tuple(actions.shape) != ((R,) if kind == HEAD_DISCRETE else (R, cols)):
         return None
     keep = [actions]
     if mask is not None:
@@ -1159,16 +1202,19 @@ def _recurrent_heads(actor, critic, h_top, actions, mask):
         mask = (mask.view(_u8) if mask.dtype == torch.bool else mask.to(_u8)).to(actions.device).reshape(R, A)
         keep.append(mask := mask.contiguous())
         s.mask = mask.data_ptr()
-    s.actions, s.R, s.A, s.box = actions.data_ptr(), R, A, int(box)
+    s.actions, s.R, s.A, s.box = actions.data_ptr(), R, A, kind
     if box:
         s.log_std = actor.head_net.log_std.data_ptr()
+    if kind == HEAD_MULTI:
+        s.multi = multi_head(nvec)
     return s, plans, params, keep
 
 
 def recurrent_heads_forward(actor, critic, h_top, actions, mask=None, *, save=True):
     """agx_recurrent_heads_forward: everything after the LSTMs of a ``StochasticActor`` / ``ValueNetwork`` pair over
     R padded rows in one launch.  h_top: (actor's, critic's) top-layer LSTM output f32 [R, H]; actions f32 [R]
-    (Discrete, the index) or [R, A] (Box); mask uint8 / bool [R, A] or None.  -> (log_prob, entropy, value [R],
+    (Discrete, the index), [R, A] (Box), [R, K] (MultiDiscrete, each component's index) or [R, n] (MultiBinary);
+    mask uint8 / bool [R, A] or None, A the width of the actor's head.  -> (log_prob, entropy, value [R],
     saved: what ``recurrent_heads_backward`` reads, None without ``save``), or None where the kernels do not
     apply (the caller runs the torch modules)."""
     found = _recurrent_heads(actor, critic, h_top, actions, mask)
@@ -1208,7 +1254,7 @@ def recurrent_heads_backward(actor, critic, h_top, actions, mask, saved, g_log_p
             e.w, e.b = next(it).data_ptr(), next(it).data_ptr()
             if ln is not None:
                 e.ln_w, e.ln_b = next(it).data_ptr(), next(it).data_ptr()
-    if s.box:
+    if s.box == HEAD_BOX:
         g.log_std = next(it).data_ptr()
     ws = torch.empty(_lib.load().agx_recurrent_heads_workspace_bytes(ctypes.byref(s)) // 4, dtype=_f32,
                      device=actions.device)

@@ -71,14 +71,18 @@ class DeterministicActor(EvolvableNetwork):
 
 
 class EvolvableDistribution(torch.nn.Module):
-    """The head of a ``StochasticActor`` (agilerl/networks/distributions.py:110-342) for Discrete and Box
-    action spaces: the MLP as ``_wrapped`` and, for Box, the learned ``log_std`` [1, A] (the reference's
-    state-dict names).  ``forward`` keeps the masked logits for ``log_prob``; sampling is torch ops."""
+    """The head of a ``StochasticActor`` (agilerl/networks/distributions.py:110-342) for Discrete, Box,
+    MultiDiscrete and MultiBinary action spaces: the MLP as ``_wrapped`` and, for Box, the learned ``log_std``
+    [1, A] (the reference's state-dict names).  ``forward`` keeps the masked logits for ``log_prob``; sampling
+    is torch ops.  ``discrete`` is every space but Box; ``nvec`` (MultiDiscrete) / ``binary`` (MultiBinary) name the two factored heads: K
+    categoricals over slices of the logits (actions [.., K]) and n Bernoullis (actions [.., n] of 0 / 1)."""
 
     def __init__(self, action_space, network, action_std_init: float = 0.0, device="cpu") -> None:
         super().__init__()
         self._wrapped, self.action_space, self.device = network, action_space, device
-        self.discrete = hasattr(action_space, "n")
+        self.nvec = [int(n) for n in action_space.nvec] if hasattr(action_space, "nvec") else None
+        self.binary = type(action_space).__name__ == "MultiBinary"
+        self.discrete = hasattr(action_space, "n") or self.nvec is not None  # a head of logits: no log_std
         self.logits = None
         if not self.discrete:
             self.log_std = torch.nn.Parameter(torch.ones(1, flatdim(action_space), device=device) * action_std_init)
@@ -97,24 +101,37 @@ class EvolvableDistribution(torch.nn.Module):
         return new
 
     def log_prob(self, action: torch.Tensor) -> torch.Tensor:
-        from ..population.nets import categorical, gaussian
+        from ..population.nets import bernoulli_head, categorical, gaussian, multi_categorical
 
         if self.logits is None:
             raise ValueError("Distribution not initialized. Call forward first.")
+        if self.nvec is not None:
+            return multi_categorical(self.logits, self.nvec, action.long().reshape(-1, len(self.nvec)))[0]
+        if self.binary:
+            return bernoulli_head(self.logits, action.reshape(self.logits.shape))[0]
         if self.discrete:
             return categorical(self.logits)[0].gather(-1, action.long().reshape(-1, 1)).squeeze(-1)
         return gaussian(self.logits, self.log_std, action)[0]
 
     def forward(self, latent: torch.Tensor, action_mask=None, sample: bool = True):
         """-> (action, log_prob, entropy); action and log_prob are None without ``sample``."""
-        from ..population.nets import categorical, gaussian
+        from ..population.nets import bernoulli_head, categorical, gaussian, multi_categorical
 
         logits = self._wrapped(latent)
         if action_mask is not None:  # distributions.py:16-28: illegal logits -> -1e8
             mask = torch.as_tensor(action_mask, device=logits.device).bool().view(logits.shape)
             logits = torch.where(mask, logits, torch.full_like(logits, -1e8))
         self.logits = logits
-        if self.discrete:
+        if self.nvec is not None:
+            parts = logits.split(self.nvec, dim=-1)
+            first = torch.zeros(*logits.shape[:-1], len(self.nvec), dtype=torch.long, device=logits.device)
+            entropy = multi_categorical(logits, self.nvec, first)[1]
+            action = torch.stack([torch.multinomial(torch.softmax(p, dim=-1), 1).squeeze(-1) for p in parts],
+                                 -1) if sample else None
+        elif self.binary:
+            entropy = bernoulli_head(logits, logits)[1]
+            action = torch.bernoulli(torch.sigmoid(logits)) if sample else None
+        elif self.discrete:
             entropy = categorical(logits)[1]
             action = torch.multinomial(torch.softmax(logits, dim=-1), 1).squeeze(-1) if sample else None
         else:
@@ -124,9 +141,10 @@ class EvolvableDistribution(torch.nn.Module):
 
 
 class StochasticActor(EvolvableNetwork):
-    """``StochasticActor`` (agilerl/networks/actors.py:214-425) over Discrete (categorical logits) and 1-D Box
-    (mean, learned log_std) action spaces, for recurrent PPO: an encoder, the MLP head "actor" and its
-    distribution.  ``squash_output`` is not supported."""
+    """``StochasticActor`` (agilerl/networks/actors.py:214-425) over Discrete (categorical logits), 1-D Box
+    (mean, learned log_std), 1-D MultiDiscrete (sum nvec logits, one categorical per component) and 1-D
+    MultiBinary (one Bernoulli logit per bit) action spaces, for recurrent PPO: an encoder, the MLP head "actor"
+    and its distribution.  ``squash_output`` is not supported."""
 
     def __init__(self, observation_space, action_space, encoder_cls=None, encoder_config=None, head_config=None,
                  action_std_init: float = 0.0, squash_output: bool = False, min_latent_dim: int = 8,
@@ -138,18 +156,18 @@ class StochasticActor(EvolvableNetwork):
                          random_seed=random_seed, encoder_name=encoder_name)
         if squash_output:
             raise NotImplementedError("agx StochasticActor: squash_output=True is not supported")
-        if not hasattr(action_space, "n") and (hasattr(action_space, "nvec") or not hasattr(action_space, "low")
-                                               or len(action_space.shape) != 1):
-            raise NotImplementedError("agx StochasticActor: Discrete and 1-D Box action spaces")
-        if type(action_space).__name__ == "MultiBinary":
-            raise NotImplementedError("agx StochasticActor: Discrete and 1-D Box action spaces")
+        multi, binary = hasattr(action_space, "nvec"), type(action_space).__name__ == "MultiBinary"
+        if (multi or binary or not hasattr(action_space, "n")) and (
+                len(action_space.shape) != 1 or not (multi or binary or hasattr(action_space, "low"))):
+            raise NotImplementedError("agx StochasticActor: Discrete and 1-D Box, MultiDiscrete and MultiBinary "
+                                      "action spaces")
         head_config = as_config(head_config)
         if head_config is None:
             head_config = mlp_net_config([32], output_activation=None)
         else:
             head_config["output_activation"] = None
         self.action_std_init, self.squash_output, self.output_activation = action_std_init, False, None
-        self.output_size = flatdim(action_space)
+        self.output_size = int(sum(action_space.nvec)) if multi else flatdim(action_space)
         self.head_net = EvolvableDistribution(action_space,
                                               self.create_mlp(self.latent_dim, self.output_size, "actor", head_config),
                                               action_std_init=action_std_init, device=device)

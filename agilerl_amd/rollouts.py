@@ -49,7 +49,7 @@ def collect_rollouts_recurrent(agent, env, n_steps: int | None = None, last_obs=
     n_steps = n_steps or -(agent.learn_step // -agent.num_envs)
     buf = agent.rollout_buffer
     buf.reset()
-    box = not hasattr(agent.action_space, "n")
+    box = hasattr(agent.action_space, "low")
     completed = []
     term = np.zeros(agent.num_envs, dtype=bool)
     fused = agent.fused_step_on()

@@ -9,6 +9,11 @@
  *                 head     = Linear [LayerNorm] ReLU ... Linear
  *   Discrete:     masked logits, log-softmax, entropy, Gumbel-max sample
  *   Box:          mean + exp(log_std) * eps, Gaussian log-prob and entropy
+ *   MultiDiscrete: K categoricals over slices of the A = sum nvec masked logits
+ *                 (agx_multi.h): per-component log-softmax, entropy and
+ *                 Gumbel-max sample; log-prob and entropy summed over k
+ *   MultiBinary:  A independent Bernoullis over the masked logits
+ *                 (agx_bernoulli.h)
  *
  * Grid (ceil(N / 16), 2): a workgroup owns a 16-env row tile of one network
  * (y = 0 the actor, y = 1 the critic).  The tiles of every layer stay in LDS,
@@ -21,7 +26,10 @@
  * The samples are the Philox streams of agx_ppo_act (Discrete: Gumbel-max,
  * word a & 3 of the block of (env, counter ^ (a >> 2) << 56)) and of
  * agx_ppo_act_gauss_graph (Box: Box-Muller per dimension), keyed by the env's
- * row index, `seed` and `counter`.
+ * row index, `seed` and `counter`.  MultiDiscrete scores flat logit j as
+ * Discrete scores action j and takes each component's first maximum, so
+ * nvec = (A) makes Discrete's choices; MultiBinary's bit j is u_j < sigmoid(lg_j)
+ * with the u_j of that score (agx_ppo_act_bern_graph's rule).
  *
  * Binding: agilerl_amd/kernels.py ppo_act_recurrent. */
 #ifndef AGX_RECURRENT_H
@@ -29,12 +37,19 @@
 
 #include "agx_graph.h"
 #include "agx_lstm.h"
+#include "agx_multi.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
 #define AGX_RECURRENT_MAX_HEAD 4 /* head Linear layers: up to 3 hidden and the output */
+
+/* the actor's distribution: the values of `box` */
+#define AGX_RECURRENT_HEAD_DISCRETE 0
+#define AGX_RECURRENT_HEAD_BOX 1
+#define AGX_RECURRENT_HEAD_MULTI 2     /* multi-categorical (MultiDiscrete) */
+#define AGX_RECURRENT_HEAD_BERNOULLI 3 /* MultiBinary */
 
 #define AGX_RECURRENT_ACT_NONE 0
 #define AGX_RECURRENT_ACT_RELU 1
@@ -68,16 +83,20 @@ typedef struct agx_recurrent_step {
     const float *obs;        /* [N][in] */
     const float *log_std;    /* [A], Box only */
     const uint8_t *reset;    /* [N] or NULL: 1 = the row starts from the zero state (and stores it) */
-    const uint8_t *mask;     /* [N][A] or NULL, Discrete only: 1 = legal; illegal logits become -1e8 */
+    const uint8_t *mask;     /* [N][A] or NULL, not with Box: 1 = legal; illegal logits become -1e8 */
     int64_t N;
-    int32_t A;               /* Discrete: actions; Box: dimensions; 1 .. AGX_PPO_GRAPH_MAX_ACTIONS */
-    int32_t box;             /* 0: Discrete, 1: Box */
+    int32_t A;               /* Discrete: actions; Box: dimensions; multi: sum nvec; Bernoulli: bits;
+                                1 .. AGX_PPO_GRAPH_MAX_ACTIONS */
+    int32_t box;             /* AGX_RECURRENT_HEAD_* */
     int32_t sample;          /* 0: no draw, `actions` and `log_probs` are not written */
     int32_t pad_;
     uint64_t seed, counter;
-    float *actions;          /* Discrete [N] (the index as a float), Box [N][A] */
+    float *actions;          /* Discrete [N] (the index as a float), Box [N][A], multi [N][K] (component k's
+                                index in [0, n_k) as a float), Bernoulli [N][A] (0 / 1) */
     float *log_probs, *entropy, *values; /* [N] */
     float *obs_store;        /* [N][in] or NULL: a copy of obs (the rollout slot) */
+    agx_multi_head multi;    /* AGX_RECURRENT_HEAD_MULTI only: K >= 1 components, every n_k >= 1, sum n_k == A.
+                                The host reduces it to one word for the kernel (bit j: logit j starts a component) */
 } agx_recurrent_step;
 
 /* One launch on `stream`; nothing is synchronised.  AGX_EINVAL (agx_last_error

@@ -6,7 +6,10 @@
  *                 head   = Linear [LayerNorm] ReLU ... Linear
  *   actor:        masked logits -> log_prob of the given action, entropy
  *                 (Discrete: log-softmax, H = -sum p log(p + 1e-8);
- *                  Box: the diagonal Gaussian of gauss_head.h with log_std)
+ *                  Box: the diagonal Gaussian of gauss_head.h with log_std;
+ *                  multi-categorical: the K categoricals of agx_multi.h over
+ *                  slices of the A = sum nvec logits, summed over k;
+ *                  Bernoulli: the A independent bits of agx_bernoulli.h)
  *   critic:       value
  *
  * A network is an agx_recurrent_net (agx_recurrent.h) with the limits of
@@ -47,12 +50,16 @@ typedef struct agx_recurrent_heads {
     agx_recurrent_net net[2]; /* net[0].head ends in A outputs, net[1].head in 1 */
     const float *h_top[2];   /* [R][H[k]]: the top LSTM layer's output at every padded row */
     int32_t H[2];            /* a multiple of 16 in [16, AGX_LSTM_MAX_HIDDEN] */
-    const float *actions;    /* Discrete [R] (the index as a float), Box [R][A] */
+    const float *actions;    /* Discrete [R] (the index as a float), Box [R][A], multi [R][K] (component k's index
+                                as a float; one outside [0, n_k) is clamped into it), Bernoulli [R][A] (anything
+                                but 0 counts as 1) */
     const float *log_std;    /* [A], Box only */
-    const uint8_t *mask;     /* [R][A] or NULL, Discrete only: 1 = legal; illegal logits become -1e8 */
+    const uint8_t *mask;     /* [R][A] or NULL, not with Box: 1 = legal; illegal logits become -1e8 and get a
+                                gradient of exactly 0 */
     int64_t R;               /* 1 .. 2^24 */
-    int32_t A;               /* 1 .. AGX_PPO_GRAPH_MAX_ACTIONS */
-    int32_t box;             /* 0: Discrete, 1: Box */
+    int32_t A;               /* 1 .. AGX_PPO_GRAPH_MAX_ACTIONS: actions, dimensions, sum nvec or bits */
+    int32_t box;             /* AGX_RECURRENT_HEAD_* (agx_recurrent.h) */
+    agx_multi_head multi;    /* AGX_RECURRENT_HEAD_MULTI only, as in agx_recurrent_step */
 } agx_recurrent_heads;
 
 /* The backward's upstream gradients and outputs.  Every output is overwritten. */

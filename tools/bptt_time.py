@@ -23,6 +23,9 @@ Discrete(4), one LSTM layer of H = 64 per encoder, max_seq_len 16 (CHUNKED), 64 
       learn() on the same buffer with the fused heads (AGX_RECURRENT_LEARN) off, which is the path
       without them, and on, each with AGX_LSTM unset and AGX_LSTM=1: four settings of one agent in the same
       alternating blocks.  Added to --out under "learn_heads"; the file's other keys are kept.
+  python tools/bptt_time.py --heads --space NAME [--out FILE]
+      the same on another action space (SPACES: Discrete of 6 / 32 logits, MultiDiscrete([3, 3]) / ([2] * 16),
+      MultiBinary(4) / (32)), under "learn_heads_NAME".
 """
 import copy
 import json
@@ -38,21 +41,31 @@ CALLS = {"prepare": int(os.environ.get("PREPARE_CALLS", 100)), "learn": int(os.e
 ROUNDS = int(os.environ.get("ROUNDS", 5))
 
 
-def setup():
+SPACES = {"discrete6": ("Discrete", 6), "multidiscrete3x3": ("MultiDiscrete", [3, 3]), "discrete32": ("Discrete", 32),
+          "multidiscrete2x16": ("MultiDiscrete", [2] * 16), "multibinary4": ("MultiBinary", 4),
+          "multibinary32": ("MultiBinary", 32)}
+
+
+def setup(space=None):
     import numpy as np
     import torch
 
+    from agilerl_amd import envs
     from agilerl_amd.algorithms.ppo import PPO
-    from agilerl_amd.envs import Box, Discrete
+    from agilerl_amd.envs import Box
 
+    kind, arg = SPACES[space] if space else ("Discrete", ACTIONS)
+    # the exclusive upper bounds of a step's random actions: [] (Discrete), [K] or [n]
+    high = torch.tensor([2] * arg if kind == "MultiBinary" else arg)
     torch.manual_seed(0)
-    agent = PPO(Box(-np.inf, np.inf, (OBS,)), Discrete(ACTIONS), recurrent=True, share_encoders=False, num_envs=N,
+    agent = PPO(Box(-np.inf, np.inf, (OBS,)), getattr(envs, kind)(arg), recurrent=True, share_encoders=False, num_envs=N,
                 learn_step=T * N, max_seq_len=MAX_SEQ_LEN, batch_size=BATCH, update_epochs=EPOCHS,
                 net_config={"encoder_config": {"hidden_state_size": H, "num_layers": 1}})
     buf, g = agent.rollout_buffer, torch.Generator().manual_seed(1)
     hidden = agent.get_initial_hidden_state(N)
     for _ in range(T):
-        buf.add(obs=torch.randn(N, OBS, generator=g), action=torch.randint(0, ACTIONS, (N,), generator=g),
+        action = (torch.rand(N, *high.shape, generator=g) * high).long()
+        buf.add(obs=torch.randn(N, OBS, generator=g), action=action,
                 reward=torch.randn(N, generator=g), done=torch.rand(N, generator=g) < 0.03,
                 value=torch.randn(N, generator=g), log_prob=-torch.rand(N, generator=g) - 0.5,
                 hidden_state={k: 0.1 * torch.randn(v.shape, generator=g) for k, v in hidden.items()})
@@ -178,8 +191,8 @@ HEADS = {"heads off": (None, "0"), "heads on": (None, "1"), "AGX_LSTM=1, heads o
          "AGX_LSTM=1, heads on": ("1", "1")}  # setting -> (AGX_LSTM, AGX_RECURRENT_LEARN)
 
 
-def heads(out_path):
-    agent = setup()
+def heads(out_path, space=None):
+    agent = setup(space)
 
     def learn(setting):
         lstm, switch = HEADS[setting]
@@ -199,9 +212,10 @@ def heads(out_path):
     if out_path and os.path.exists(out_path):
         with open(out_path) as f:
             result = json.load(f)
-    result["learn_heads"] = {"unit": "ms per learn()", "calls_per_block": CALLS["learn"], "blocks": ROUNDS,
+    key = "learn_heads" + (f"_{space}" if space else "")
+    result[key] = {"unit": "ms per learn()", "calls_per_block": CALLS["learn"], "blocks": ROUNDS,
                              **{setting: spread(v) for setting, v in times.items()}}
-    print(json.dumps(result["learn_heads"]))
+    print(key, json.dumps(result[key]))
     if out_path:
         with open(out_path, "w") as f:
             f.write(json.dumps(result, indent=1) + "\n")
@@ -210,7 +224,7 @@ def heads(out_path):
 def main():
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     if "--heads" in sys.argv:
-        return heads(out_path)
+        return heads(out_path, sys.argv[sys.argv.index("--space") + 1] if "--space" in sys.argv else None)
     agent = setup()
     ref = copy.deepcopy(agent)
     ref.reinit_optimizers()

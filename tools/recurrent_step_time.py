@@ -8,9 +8,12 @@ blocks of CALLS calls) and one ``collect_rollouts_recurrent`` of T = 128 steps
 on a SyntheticVecEnv (ms per rollout, the bootstrap value and GAE included).
 After a warm-up, ROUNDS rounds alternate fused and torch.  Median and min-max
 of the blocks.  Shapes: N in 64 / 128, obs 8, H in 64 / 128, L in 1 / 2,
-default heads, Discrete(4) and Box(6).
+default heads, Discrete(4) and Box(6).  ``--spaces`` times N = 64, H = 64, L = 1
+over MultiDiscrete([3, 3]), MultiDiscrete([2] * 16), MultiBinary(4) and
+MultiBinary(32), each beside the Discrete space of the same logit count.
 
   python tools/recurrent_step_time.py [--out FILE]    (default profiles/recurrent_step_time.json)
+  python tools/recurrent_step_time.py --spaces [--out FILE]    (default profiles/recurrent_step_spaces.json)
 """
 import json
 import os
@@ -29,7 +32,12 @@ def _stats(v, digits):
     return [round(sorted(v)[len(v) // 2], digits), round(min(v), digits), round(max(v), digits)]
 
 
-def time_cell(N, H, L, box):
+SPACES = {"discrete6": dict(n_actions=6), "multidiscrete3x3": dict(nvec=[3, 3]), "discrete32": dict(n_actions=32),
+          "multidiscrete2x16": dict(nvec=[2] * 16), "discrete4": dict(n_actions=4), "multibinary4": dict(n_binary=4),
+          "multibinary32": dict(n_binary=32)}
+
+
+def time_cell(N, H, L, env_kw):
     import numpy as np
     import torch
 
@@ -38,7 +46,7 @@ def time_cell(N, H, L, box):
     from agilerl_amd.rollouts import collect_rollouts_recurrent
 
     def make(fused):
-        env = SyntheticVecEnv(N, obs_dim=8, n_actions=4, p_done=1 / 50, seed=3, action_dim=6 if box else None)
+        env = SyntheticVecEnv(N, obs_dim=8, p_done=1 / 50, seed=3, **env_kw)
         torch.manual_seed(N + H + L)
         agent = PPO(env.single_observation_space, env.single_action_space, recurrent=True, share_encoders=False,
                     num_envs=N, learn_step=T * N, fused_step=fused,
@@ -82,16 +90,18 @@ if __name__ == "__main__":
 
     assert torch.cuda.is_available(), "tools/recurrent_step_time.py measures on the GPU only"
     os.environ.pop("AGX_RECURRENT_STEP", None)
+    spaces = "--spaces" in sys.argv
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
-        os.path.join(ROOT, "profiles", "recurrent_step_time.json")
+        os.path.join(ROOT, "profiles", "recurrent_step_spaces.json" if spaces else "recurrent_step_time.json")
     result = {"calls_per_block": CALLS, "rounds": ROUNDS, "unit": "median, min, max (host wall-clock)",
               "fused": "fused_step=True", "torch": "the switch off (the parent commit's path)", "cells": {}}
-    for box in (False, True):
-        for N in NS:
-            for H in HS:
-                for L in LS:
-                    result["cells"][f"{'box6' if box else 'discrete4'}_N{N}_H{H}_L{L}"] = time_cell(N, H, L, box)
-                    with open(out_path, "w") as f:  # after every cell: a run cut short keeps what it measured
-                        json.dump(result, f, indent=1)
-                        f.write("\n")
+    cells = [(f"{name}_N64_H64_L1", 64, 64, 1, kw) for name, kw in SPACES.items()] if spaces else \
+        [(f"{name}_N{N}_H{H}_L{L}", N, H, L, kw) for name, kw in (("discrete4", dict(n_actions=4)),
+                                                                  ("box6", dict(action_dim=6)))
+         for N in NS for H in HS for L in LS]
+    for name, N, H, L, kw in cells:
+        result["cells"][name] = time_cell(N, H, L, kw)
+        with open(out_path, "w") as f:  # after every cell: a run cut short keeps what it measured
+            json.dump(result, f, indent=1)
+            f.write("\n")
     print(json.dumps(result))
