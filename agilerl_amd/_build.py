@@ -33,8 +33,9 @@ _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # lstm.hip: the same flag for the same reasons; its resource report is in DESIGN 4.13.  recurrent_policy.hip
 # shares lstm.hip's gate chains (csrc/lstm_gates.h) and must produce their bits: the same flag.
 # recurrent_heads.hip shares recurrent_policy.hip's dense layers (csrc/recurrent_dense.h): the same flag.
+# lstm_split.hip is lstm.hip's per-step form and must produce its bits: the same flag.
 EXTRA_CFLAGS = {"simba.hip": _NO_PACKED_FP32, "lstm.hip": _NO_PACKED_FP32, "recurrent_policy.hip": _NO_PACKED_FP32,
-                "recurrent_heads.hip": _NO_PACKED_FP32}
+                "recurrent_heads.hip": _NO_PACKED_FP32, "lstm_split.hip": _NO_PACKED_FP32}
 
 
 def _needs(obj: str, src: str, deps: list[str]) -> bool:

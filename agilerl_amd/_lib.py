@@ -175,6 +175,10 @@ SIGNATURES = {
     "agx_lstm_workspace_bytes": (_SZ, [_P, _I, _I]),
     "agx_lstm_forward": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "agx_lstm_backward": (_INT, [_P, _P, _P, _P, _I, _I] + [_P] * 10),
+    "agx_lstm_choose_plan": (_INT, [_P, _I, _I, _P]),
+    "agx_lstm_split_workspace_bytes": (_SZ, [_P, _I, _I, _INT]),
+    "agx_lstm_forward_split": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "agx_lstm_backward_split": (_INT, [_P, _P, _P, _P, _I, _I] + [_P] * 10),
     # include/agx_bptt.h: truncated BPTT for recurrent PPO (gather arguments: kernels.py BpttGatherArgs)
     "agx_bptt_capacity": (_I, [_I, _I]),
     "agx_bptt_plan_workspace_bytes": (_SZ, [_I]),

@@ -45,45 +45,6 @@ namespace lstm {
 constexpr int kThreads = 512;
 constexpr int kWaves = 8;
 
-// A wave-uniform value the optimiser cannot see through: addresses formed from it are computed where they are used
-// instead of being carried through the step loop as one induction pointer per store (which spilled).
-__device__ __forceinline__ int64_t opaque(int64_t v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-
-__device__ __forceinline__ int opaque_lane(int v) {  // the same for a per-lane value
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-// acc[row][col] += sum_k arow[k] * wcol[k * ldw], k < K (K % 16 == 0): W read down a column, four steps' operands
-// ahead of their MFMAs.
-__device__ __forceinline__ f32x4 chain_col(int K, int q, f32x4 acc, const float *arow, const float *wcol, int ldw) {
-#pragma unroll 1
-    for (int kc = 0; kc < K; kc += 64) {
-        f32x4 a[4];
-        float w[16];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int k = kc + 16 * s + 4 * q, kk = min(k, K - 4);
-            a[s] = *reinterpret_cast<const f32x4 *>(arow + kk);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float v = wcol[(int64_t)(kk + j) * ldw];
-                w[4 * s + j] = k < K ? v : 0.f;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (kc + 16 * s < K) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc = MFMA(a[s][j], w[4 * s + j], acc);
-            }
-    }
-    return acc;
-}
-
 // ---------------------------------------------------------------------------
 struct FwdArgs {
     agx_lstm_desc d;
@@ -92,9 +53,6 @@ struct FwdArgs {
     int B;
     int64_t T;
 };
-
-// `saved`, per layer l at l * 6 * N * H floats: gates [N][4H], c [N][H], h [N][H] (below the top layer)
-__host__ __device__ inline int64_t saved_layer(int64_t N, int H, int l) { return (int64_t)l * 6 * N * H; }
 
 // NT: unit tiles per wave; KS > 0: W_hh in registers, H <= 16 * KS (NT == 1)
 template <int NT, int KS, bool SAVE>
@@ -495,10 +453,8 @@ static void allow_lds() {
     (void)once;
 }
 
-}  // namespace lstm
-
 // ---------------------------------------------------------------------------
-static int check_dims(const agx_lstm_desc *d, int64_t B, int64_t T, const char *who) {
+int check_dims(const agx_lstm_desc *d, int64_t B, int64_t T, const char *who) {
     AGX_REQUIRE(d, "%s: descriptor is NULL", who);
     AGX_REQUIRE(d->L >= 1 && d->L <= AGX_LSTM_MAX_LAYERS, "%s: %d layers outside [1, %d]", who, d->L,
                 AGX_LSTM_MAX_LAYERS);
@@ -512,7 +468,7 @@ static int check_dims(const agx_lstm_desc *d, int64_t B, int64_t T, const char *
     return AGX_OK;
 }
 
-static int check_desc(const agx_lstm_desc *d, int64_t B, int64_t T, bool backward, const char *who) {
+int check_desc(const agx_lstm_desc *d, int64_t B, int64_t T, bool backward, const char *who) {
     if (int rc = check_dims(d, B, T, who)) return rc;
     for (int l = 0; l < d->L; ++l) {
         const agx_lstm_layer &p = d->layer[l];
@@ -522,6 +478,27 @@ static int check_desc(const agx_lstm_desc *d, int64_t B, int64_t T, bool backwar
     }
     return AGX_OK;
 }
+
+int launch_dw_dx(const agx_lstm_layer &p, const float *dG, const float *xin, const float *hout, const float *h0, float *dX,
+                 int K, int H, int64_t T, int64_t N, hipStream_t s, const char *who) {
+    allow_lds();
+    const dim3 block(kThreads);
+    DwArgs wa{dG, xin, hout, h0, p.g_w_ih, p.g_w_hh, p.g_b_ih, p.g_b_hh, K, H, T, N};
+    const int tiles = (K + 15) / 16 + H / 16 + 1;
+    hipLaunchKernelGGL(dw_kernel, dim3(4 * H / 16, (unsigned)ceil_div(tiles, kWaves)), block, 0, s, wa);
+    if (int rc = check_launch(who)) return rc;
+    if (dX) {
+        DxArgs xa{dG, p.w_ih, dX, K, H, N};
+        hipLaunchKernelGGL(dx_kernel, dim3((unsigned)ceil_div(N, 16)), block, scan_lds(H), s, xa);
+        if (int rc = check_launch(who)) return rc;
+    }
+    return AGX_OK;
+}
+
+}  // namespace lstm
+
+using lstm::check_desc;
+using lstm::check_dims;
 
 extern "C" size_t agx_lstm_saved_bytes(const agx_lstm_desc *d, int64_t B, int64_t T) {
     if (check_dims(d, B, T, "agx_lstm_saved_bytes")) return 0;
@@ -569,7 +546,6 @@ extern "C" int agx_lstm_backward(const agx_lstm_desc *d, const float *x, const f
     const float *sv = static_cast<const float *>(saved);
     float *dG = static_cast<float *>(workspace), *dY = dG + 4 * N * H;
     hipStream_t s = as_stream(stream);
-    const dim3 block(lstm::kThreads);
     for (int l = L - 1; l >= 0; --l) {
         const agx_lstm_layer &p = d->layer[l];
         const float *svl = sv + lstm::saved_layer(N, H, l);
@@ -581,20 +557,11 @@ extern "C" int agx_lstm_backward(const agx_lstm_desc *d, const float *x, const f
                           gh0 ? gh0 + l * BH : nullptr, gc0 ? gc0 + l * BH : nullptr, (int)B, H, T};
         const dim3 sgrid((unsigned)ceil_div(B, 16));
         const size_t slds = lstm::scan_lds(H);
-#define AGX_LSTM_SCAN(NT, KS, unused) hipLaunchKernelGGL((lstm::bwd_scan_kernel<NT, KS>), sgrid, block, slds, s, sa)
+#define AGX_LSTM_SCAN(NT, KS, unused) hipLaunchKernelGGL((lstm::bwd_scan_kernel<NT, KS>), sgrid, dim3(lstm::kThreads), slds, s, sa)
         AGX_LSTM_WIDTHS(AGX_LSTM_SCAN, 0);
 #undef AGX_LSTM_SCAN
         if (int rc = check_launch(who)) return rc;
-        lstm::DwArgs wa{dG, xin, hout, h0 + l * BH, p.g_w_ih, p.g_w_hh, p.g_b_ih, p.g_b_hh, K, H, T, N};
-        const int tiles = (K + 15) / 16 + H / 16 + 1;
-        hipLaunchKernelGGL(lstm::dw_kernel, dim3(4 * H / 16, (unsigned)ceil_div(tiles, lstm::kWaves)), block, 0, s, wa);
-        if (int rc = check_launch(who)) return rc;
-        float *dX = l == 0 ? gx : dY;
-        if (dX) {
-            lstm::DxArgs xa{dG, p.w_ih, dX, K, H, N};
-            hipLaunchKernelGGL(lstm::dx_kernel, dim3((unsigned)ceil_div(N, 16)), block, slds, s, xa);
-            if (int rc = check_launch(who)) return rc;
-        }
+        if (int rc = lstm::launch_dw_dx(p, dG, xin, hout, h0 + l * BH, l == 0 ? gx : dY, K, H, T, N, s, who)) return rc;
     }
     return AGX_OK;
 }

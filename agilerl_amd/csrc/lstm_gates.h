@@ -1,14 +1,17 @@
-// The LSTM gate chains shared by the sequence kernels (lstm.hip) and the fused
-// recurrent policy step (recurrent_policy.hip): the MFMA macro, the sigmoid,
-// the staging of a step's input tile and the four gates' accumulation over an
-// LDS row and a weight row.  Both files accumulate every gate as bias, then k
-// ascending over the input, then k ascending over h with these functions, so a
-// step taken by either has the other's bits.
+// The LSTM gate chains shared by the sequence kernels (lstm.hip), their split
+// per-step form (lstm_split.hip) and the fused recurrent policy step
+// (recurrent_policy.hip): the MFMA macro, the sigmoid, the staging of a step's
+// input tile, the four gates' accumulation over an LDS row and a weight row,
+// and the backward's single-accumulator chain down a weight column.  All files
+// accumulate every gate as bias, then k ascending over the input, then k
+// ascending over h with these functions, so a step taken by any has the
+// others' bits.
 #pragma once
 
 #include <cstdint>
 
 #include "agx_common.h"
+#include "../../include/agx_lstm.h"
 
 namespace agx {
 
@@ -84,6 +87,55 @@ __device__ __forceinline__ void gates_any(int K, int q, f32x4 (&acc)[4], const f
             for (int g = 0; g < 4; ++g) acc[g] = MFMA(a[j], w[g][j], acc[g]);
     }
 }
+
+// A wave-uniform value the optimiser cannot see through: addresses formed from it are computed where they are used
+// instead of being carried through the step loop as one induction pointer per store (which spilled).
+__device__ __forceinline__ int64_t opaque(int64_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+__device__ __forceinline__ int opaque_lane(int v) {  // the same for a per-lane value
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// acc[row][col] += sum_k arow[k] * wcol[k * ldw], k < K (K % 16 == 0): W read down a column, four steps' operands
+// ahead of their MFMAs.
+__device__ __forceinline__ f32x4 chain_col(int K, int q, f32x4 acc, const float *arow, const float *wcol, int ldw) {
+#pragma unroll 1
+    for (int kc = 0; kc < K; kc += 64) {
+        f32x4 a[4];
+        float w[16];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = kc + 16 * s + 4 * q, kk = min(k, K - 4);
+            a[s] = *reinterpret_cast<const f32x4 *>(arow + kk);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = wcol[(int64_t)(kk + j) * ldw];
+                w[4 * s + j] = k < K ? v : 0.f;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (kc + 16 * s < K) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = MFMA(a[s][j], w[4 * s + j], acc);
+            }
+    }
+    return acc;
+}
+
+// `saved`, per layer l at l * 6 * N * H floats: gates [N][4H], c [N][H], h [N][H] (below the top layer)
+__host__ __device__ inline int64_t saved_layer(int64_t N, int H, int l) { return (int64_t)l * 6 * N * H; }
+
+// lstm.hip's host side, shared with lstm_split.hip: the descriptor checks (no HIP call) and the two launches of a
+// layer's backward that run over all N rows (dw_kernel, then dx_kernel when dX is wanted).
+int check_dims(const agx_lstm_desc *d, int64_t B, int64_t T, const char *who);
+int check_desc(const agx_lstm_desc *d, int64_t B, int64_t T, bool backward, const char *who);
+int launch_dw_dx(const agx_lstm_layer &p, const float *dG, const float *xin, const float *hout, const float *h0, float *dX,
+                 int K, int H, int64_t T, int64_t N, hipStream_t s, const char *who);
 
 }  // namespace lstm
 

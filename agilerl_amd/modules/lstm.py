@@ -10,7 +10,12 @@ parameters stay the ``nn.LSTM``'s own tensors.
 
 ``lstm_sequence(module, x, h0, c0)`` runs the stack on the fused kernels: x
 [B, T, in], h0 / c0 [L, B, H] -> (y [B, T, H], h_n, c_n), one launch forward
-(no-grad: nothing stored but the outputs) and three per layer backward.  It
+(no-grad: nothing stored but the outputs) and three per layer backward.  That
+is the ``"whole"`` plan; ``plan="split"`` runs the same arithmetic as one
+launch per time step with every layer split by hidden unit across the device
+(csrc/lstm_split.hip: agx_lstm_forward_split / _backward_split), bit for bit
+the same results.  ``plan=None`` takes AGX_LSTM_PLAN=whole|split if set, else
+agx_lstm_choose_plan's measured choice (split for wide layers).  It
 applies to contiguous f32 CUDA tensors, 1..4 layers, H a multiple of 16 in
 [16, 512], input sizes 1..512, zero inter-layer dropout or eval mode, modules
 without hooks; anything else returns None and the torch module runs.  A
@@ -246,19 +251,26 @@ class LstmFn(torch.autograd.Function):
     """(x [B, T, in], h0, c0 [L, B, H], the nn.LSTM's parameters...) -> (y [B, T, H], h_n, c_n)."""
 
     @staticmethod
-    def forward(ctx, meta, x, h0, c0, *ts):
+    def forward(ctx, meta, split, x, h0, c0, *ts):
         x, h0, c0 = x.contiguous(), h0.contiguous(), c0.contiguous()
         (B, T, _), (_, H, L) = x.shape, meta
         y = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
         h_n, c_n = torch.empty_like(h0), torch.empty_like(c0)
         d = _desc(meta, ts)
-        saved = None
+        ctx.set_materialize_grads(False)  # an output without a cotangent reaches the backward as None, not zeros
+        saved = ws = None
         if any(ctx.needs_input_grad):
             n = _lib.load().agx_lstm_saved_bytes(ctypes.byref(d), B, T)
             saved = torch.empty(n // 4, dtype=torch.float32, device=x.device)
-        _lib.call("agx_lstm_forward", ctypes.byref(d), x.data_ptr(), h0.data_ptr(), c0.data_ptr(), B, T, y.data_ptr(),
-                  h_n.data_ptr(), c_n.data_ptr(), _lib.ptr(saved), _lib.stream())
-        ctx.meta = meta
+        args = (ctypes.byref(d), x.data_ptr(), h0.data_ptr(), c0.data_ptr(), B, T, y.data_ptr(), h_n.data_ptr(),
+                c_n.data_ptr(), _lib.ptr(saved))
+        if split:  # one workspace, of the backward's size when a backward will follow, serves both
+            nws = _lib.load().agx_lstm_split_workspace_bytes(ctypes.byref(d), B, T, int(saved is not None))
+            ws = torch.empty(nws // 4, dtype=torch.float32, device=x.device)
+            _lib.call("agx_lstm_forward_split", *args, ws.data_ptr(), _lib.stream())
+        else:
+            _lib.call("agx_lstm_forward", *args, _lib.stream())
+        ctx.meta, ctx.ws = meta, ws
         if saved is not None:
             ctx.save_for_backward(x, h0, c0, y, saved, *ts)
         return y, h_n, c_n
@@ -272,20 +284,38 @@ class LstmFn(torch.autograd.Function):
         gh_n = None if gh_n is None else gh_n.to(torch.float32).contiguous()
         gc_n = None if gc_n is None else gc_n.to(torch.float32).contiguous()
         grads = [torch.empty_like(t) for t in ts]
-        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        gh0 = torch.empty_like(h0) if ctx.needs_input_grad[2] else None
-        gc0 = torch.empty_like(c0) if ctx.needs_input_grad[3] else None
+        gx = torch.empty_like(x) if ctx.needs_input_grad[2] else None
+        gh0 = torch.empty_like(h0) if ctx.needs_input_grad[3] else None
+        gc0 = torch.empty_like(c0) if ctx.needs_input_grad[4] else None
         d = _desc(ctx.meta, ts, grads)
-        nws = _lib.load().agx_lstm_workspace_bytes(ctypes.byref(d), B, T)
-        ws = torch.empty(nws // 4, dtype=torch.float32, device=x.device)
-        _lib.call("agx_lstm_backward", ctypes.byref(d), x.data_ptr(), h0.data_ptr(), c0.data_ptr(), B, T, y.data_ptr(),
-                  saved.data_ptr(), gy.data_ptr(), _lib.ptr(gh_n), _lib.ptr(gc_n), _lib.ptr(gx), _lib.ptr(gh0),
-                  _lib.ptr(gc0), ws.data_ptr(), _lib.stream())
-        return (None, gx, gh0, gc0, *[g if ctx.needs_input_grad[4 + i] else None for i, g in enumerate(grads)])
+        ws = ctx.ws  # the split forward's, sized for its backward
+        if ws is None:
+            nws = _lib.load().agx_lstm_workspace_bytes(ctypes.byref(d), B, T)
+            ws = torch.empty(nws // 4, dtype=torch.float32, device=x.device)
+        _lib.call("agx_lstm_backward_split" if ctx.ws is not None else "agx_lstm_backward", ctypes.byref(d),
+                  x.data_ptr(), h0.data_ptr(), c0.data_ptr(), B, T, y.data_ptr(), saved.data_ptr(), gy.data_ptr(),
+                  _lib.ptr(gh_n), _lib.ptr(gc_n), _lib.ptr(gx), _lib.ptr(gh0), _lib.ptr(gc0), ws.data_ptr(),
+                  _lib.stream())
+        return (None, None, gx, gh0, gc0,
+                *[g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads)])
 
 
-def lstm_sequence(module: EvolvableLSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
-    """``module.lstm(x, (h0, c0))`` on the fused kernels as (y, h_n, c_n), or None where they do not apply."""
+def choose_plan(meta, B: int, T: int) -> str:
+    """agx_lstm_choose_plan's form for (in, H, L) at B sequences of T steps: "whole" or "split"."""
+    d, split = AgxLstmDesc(), ctypes.c_int32(0)
+    d.in_, d.H, d.L = meta
+    lib = _lib.load(require_gpu=False)
+    _lib.check(lib.agx_lstm_choose_plan(ctypes.byref(d), B, T, ctypes.byref(split)), "agx_lstm_choose_plan")
+    return "split" if split.value else "whole"
+
+
+def lstm_sequence(module: EvolvableLSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor,
+                  plan: str | None = None):
+    """``module.lstm(x, (h0, c0))`` on the fused kernels as (y, h_n, c_n), or None where they do not apply.
+    ``plan``: "whole", "split" or None (AGX_LSTM_PLAN, else the library's choice); the results do not depend on it."""
+    plan = plan or os.environ.get("AGX_LSTM_PLAN") or None
+    if plan not in (None, "whole", "split"):
+        raise ValueError(f"lstm_sequence: plan {plan!r} is neither 'whole' nor 'split'")
     if not enabled() or not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
                                 for t in (x, h0, c0)):
         return None
@@ -297,4 +327,6 @@ def lstm_sequence(module: EvolvableLSTM, x: torch.Tensor, h0: torch.Tensor, c0: 
     if (x.dim() != 3 or x.shape[2] != n_in or min(x.shape[:2]) < 1 or x.shape[0] * x.shape[1] > _MAX_ROWS or
             tuple(h0.shape) != (L, x.shape[0], H) or tuple(c0.shape) != (L, x.shape[0], H)):
         return None
-    return LstmFn.apply(meta, x, h0, c0, *ts)
+    if plan is None:
+        plan = choose_plan(meta, x.shape[0], x.shape[1])
+    return LstmFn.apply(meta, plan == "split", x, h0, c0, *ts)

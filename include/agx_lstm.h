@@ -68,6 +68,40 @@ int agx_lstm_backward(const agx_lstm_desc *desc, const float *x, const float *h0
                       const float *y, const void *saved, const float *gy, const float *gh_n, const float *gc_n,
                       float *gx, float *gh0, float *gc0, void *workspace, void *stream);
 
+/* ---- The split form (csrc/lstm_split.hip) ---------------------------------
+ * A layer split by hidden unit across the device, one launch per time step
+ * (wave-tasks of 16 units x 16 rows, grouped by unit tile so that a slice of
+ * W_hh is staged through LDS once per workgroup and step), the input half of
+ * the gates hoisted into one device-wide projection per layer.  Nothing waits
+ * on another workgroup, no atomics, no sum is split, and every element takes
+ * the whole kernels' chain: the results have agx_lstm_forward's and
+ * agx_lstm_backward's bits.  It serves every descriptor they serve; `saved`
+ * has the same layout, so a split forward may be followed by either backward
+ * and the other way round.  T + 1 launches per layer forward, at most T + 3
+ * backward; no host synchronisation, no allocation, capturable. */
+
+/* Which form is faster for (desc, B, T): *split = 1 from the width at which
+ * tools/lstm_time.py measured the split form clear of the whole one in every
+ * sequence cell, 0 below it (always 0 for H <= 128).  Host only, no HIP call. */
+int agx_lstm_choose_plan(const agx_lstm_desc *desc, int64_t B, int64_t T, int32_t *split);
+
+/* Bytes of the split form's workspace, N = B * T.  Forward (backward == 0):
+ * the projection [N][4H] of the layer at hand, 16 N H (used when saved ==
+ * NULL; with `saved` the projection lies in its gate region).  Backward: the
+ * whole backward's workspace and the cell gradient [B][H]:
+ * 4 (N H (L > 1 ? 5 : 4) + B H), which is no less than the forward's, so one
+ * buffer of that size serves both.  0 for a descriptor outside the limits. */
+size_t agx_lstm_split_workspace_bytes(const agx_lstm_desc *desc, int64_t B, int64_t T, int backward);
+
+/* agx_lstm_forward's arguments and the workspace (never NULL). */
+int agx_lstm_forward_split(const agx_lstm_desc *desc, const float *x, const float *h0, const float *c0, int64_t B,
+                           int64_t T, float *y, float *h_n, float *c_n, void *saved, void *workspace, void *stream);
+
+/* agx_lstm_backward's arguments; the workspace has the split form's size. */
+int agx_lstm_backward_split(const agx_lstm_desc *desc, const float *x, const float *h0, const float *c0, int64_t B,
+                            int64_t T, const float *y, const void *saved, const float *gy, const float *gh_n,
+                            const float *gc_n, float *gx, float *gh0, float *gc0, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

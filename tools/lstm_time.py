@@ -1,20 +1,25 @@
 """EvolvableLSTM's nn.LSTM on one GPU: the fused sequence kernels (AGX_LSTM=1)
-against torch's nn.LSTM (AGX_LSTM=0), in one process.
+in their whole-sequence form (``fused``) and their split per-step form
+(``split``, csrc/lstm_split.hip) against torch's nn.LSTM (AGX_LSTM=0), in one
+process.
 
 Three modes per cell: ``step`` (no-grad, T = 1, B = 128: the rollout's call),
 ``fwd`` (no-grad sequence) and ``fwdbwd`` (forward, then autograd.grad down to
-x, h0, c0 and every parameter).  The fused variant is captured once and
-replayed.  torch's nn.LSTM cannot be captured here (its hipBLASLt calls
+x, h0, c0 and every parameter).  The fused and split variants are captured
+once and replayed.  torch's nn.LSTM cannot be captured here (its hipBLASLt calls
 refuse a capturing stream and the process dies), so it is called eagerly
 and its figures include the host's launch work: they are an upper bound on
 torch's device time, and no automatic bound of EvolvableLSTM.forward is taken
-from them.  After a warm-up, ROUNDS rounds alternate fused and torch, each a
-block of REPLAYS calls between two device events.  Median and min-max of the
-blocks, in microseconds per call.  Grid: H in 64 / 128 / 256 / 512 x L in 1 / 2, and
-for the sequence modes T in 16 / 64 x B in 32 / 128; input size 8.
+from them.  After a warm-up, ROUNDS rounds alternate fused, split and torch,
+each a block of REPLAYS calls between two device events.  Median and min-max
+of the blocks, in microseconds per call.  Grid: H in 64 / 128 / 144 / 256 / 512
+x L in 1 / 2, and for the sequence modes T in 16 / 64 x B in 32 / 128; input
+size 8.
 
 A cell's ``fused_clear`` is true when the fused maximum lies below torch's
-(eager) minimum.
+(eager) minimum, its ``split_clear`` when the split maximum lies below the
+fused minimum: agx_lstm_choose_plan returns split for the widths at which that
+holds in every sequence cell (``split_clear_widths`` in the result).
 
   python tools/lstm_time.py [--out FILE]    (default profiles/lstm_time.json)
 """
@@ -25,7 +30,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-HS, LS, TS, BS = (64, 128, 256, 512), (1, 2), (16, 64), (32, 128)
+HS, LS, TS, BS = (64, 128, 144, 256, 512), (1, 2), (16, 64), (32, 128)
 REPLAYS = int(os.environ.get("REPLAYS", 20))
 ROUNDS = int(os.environ.get("ROUNDS", 5))
 WARMUP = 5
@@ -75,10 +80,10 @@ def time_cell(H, L, B, T, grad):
     x, h0, c0 = (torch.randn(*s, device="cuda").requires_grad_(grad) for s in ((B, T, 8), (L, B, H), (L, B, H)))
     gy = torch.randn(B, T, H, device="cuda")
 
-    def run(fused):
+    def run(plan):
         with torch.set_grad_enabled(grad):
-            if fused:
-                y, h_n, c_n = lstm_sequence(net, x, h0, c0)
+            if plan:
+                y, h_n, c_n = lstm_sequence(net, x, h0, c0, plan=plan)
             else:
                 y, (h_n, c_n) = net.lstm(x, (h0, c0))
             if not grad:
@@ -86,9 +91,11 @@ def time_cell(H, L, B, T, grad):
             return torch.autograd.grad([(y * gy).sum() + h_n.sum() + c_n.sum()], [x, h0, c0] + params)
 
     for _ in range(WARMUP):
-        run(False)
-    res = _blocks({"fused": _capture(lambda: run(True)).replay, "torch": lambda: run(False)})
+        run(None)
+    res = _blocks({"fused": _capture(lambda: run("whole")).replay, "split": _capture(lambda: run("split")).replay,
+                   "torch": lambda: run(None)})
     res["fused_clear"] = res["fused"][2] < res["torch"][1]
+    res["split_clear"] = res["split"][2] < res["fused"][1]
     return res
 
 
@@ -102,9 +109,13 @@ if __name__ == "__main__":
     cells = [("step", H, L, 128, 1) for H in HS for L in LS]
     cells += [(mode, H, L, B, T) for mode in ("fwd", "fwdbwd") for H in HS for L in LS for T in TS for B in BS]
     result = {"replays_per_block": REPLAYS, "rounds": ROUNDS, "unit": "us: median, min, max",
-              "fused": "captured graph replay", "torch": "eager calls", "cells": {}}
+              "fused": "captured graph replay", "split": "captured graph replay", "torch": "eager calls",
+              "cells": {}}
     for mode, H, L, B, T in cells:
         result["cells"][f"{mode}_H{H}_L{L}_B{B}_T{T}"] = time_cell(H, L, B, T, mode == "fwdbwd")
+        seq = {H: [c["split_clear"] for k, c in result["cells"].items() if f"_H{H}_" in k and k[:4] != "step"]
+               for H in HS}
+        result["split_clear_widths"] = [H for H in HS if seq[H] and all(seq[H])]
         with open(out_path, "w") as f:  # after every cell: a run cut short keeps what it measured
             json.dump(result, f, indent=1)
             f.write("\n")
