@@ -193,6 +193,12 @@ SIGNATURES = {
     "agx_recurrent_heads_workspace_bytes": (_SZ, [_P]),
     "agx_recurrent_heads_forward": (_INT, [_P, _P, _P, _P, _P, _P]),
     "agx_recurrent_heads_backward": (_INT, [_P, _P, _P, _P, _P]),
+    # the shared-encoder forms of both (share_encoders=True), on the same descriptors
+    "agx_ppo_act_recurrent_shared": (_INT, [_P, _P]),
+    "agx_recurrent_heads_saved_bytes_shared": (_SZ, [_P]),
+    "agx_recurrent_heads_workspace_bytes_shared": (_SZ, [_P]),
+    "agx_recurrent_heads_forward_shared": (_INT, [_P, _P, _P, _P, _P, _P]),
+    "agx_recurrent_heads_backward_shared": (_INT, [_P, _P, _P, _P, _P]),
     "agx_conv2d_forward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _INT, _P, _P]),
     "agx_conv2d_wgrad_workspace_bytes": (_SZ, [_P]),
     "agx_conv2d_backward": (_INT, [_P, _P, _INT, _F, _F, _P, _P, _P, _P, _P, _P, _INT, _P, _P]),

@@ -26,7 +26,8 @@ LayerNorm on, shared encoder.  ``get_action`` / ``learn`` / ``test`` keep the
 reference's signatures and return types; squashed Box outputs and custom
 ``actor_network`` objects raise NotImplementedError (outside the hot path);
 ``recurrent=True`` builds the per-agent BPTT agent of
-algorithms/ppo_recurrent.py.  ``get_action(obs, action_mask)``
+algorithms/ppo_recurrent.py, with separate encoders or, on a CUDA device, the
+reference's default shared one.  ``get_action(obs, action_mask)``
 applies the reference's legal-action masks (logits of illegal actions ->
 -1e8, ppo.py:529-565); ``target_kl`` stops an agent's epochs early exactly
 as ppo.py:917-918 does, inside the fused learner.

@@ -29,8 +29,20 @@ agx_recurrent_heads_forward launch with a two-launch backward
 
 Action spaces: Discrete, 1-D Box, 1-D MultiDiscrete and 1-D MultiBinary, each
 on both paths; the last two on a CUDA device only (on the CPU the agent keeps
-refusing them, as it did before they existed).  ``share_encoders=True``, image
-/ Dict observations and ``squash_output`` raise.
+refusing them, as it did before they existed).  Image / Dict observations and
+``squash_output`` raise.
+
+``share_encoders=True`` (the reference's default, CUDA only; the CPU keeps
+refusing it): both networks are built on ``shared_encoder``, the actor's encoder
+is the live one and the critic's head reads the actor's latent
+(ppo.py:430-442), so a step and a minibatch run one LSTM, the hidden state is
+the ``shared_encoder_h`` / ``_c`` pair, and the encoder's gradient carries the
+value loss's share.  The critic's own encoder is a non-trainable copy that is
+never run: synced from the actor's at construction, after ``learn()`` and after
+``load_state_dict``, so ``state_dict()`` has the reference's keys.  With the
+switches on, the step is agx_ppo_act_recurrent_shared and the heads are
+agx_recurrent_heads_forward_shared / _backward_shared: one workgroup per row
+tile runs both heads off the one latent.
 """
 
 from __future__ import annotations
@@ -76,7 +88,8 @@ class HeadsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, actor, critic, actions, mask, h_actor, h_critic, *params):
-        h_top = (h_actor.detach().contiguous(), h_critic.detach().contiguous())
+        # h_critic is None for a pair that shares one encoder: one h_top, and one dh_top on the way back
+        h_top = tuple(h.detach().contiguous() for h in (h_actor, h_critic) if h is not None)
         logp, entropy, value, saved = K.recurrent_heads_forward(actor, critic, h_top, actions, mask)
         ctx.nets, ctx.mask = (actor, critic), mask
         ctx.save_for_backward(*h_top, actions, saved)
@@ -85,11 +98,11 @@ class HeadsFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_logp, g_entropy, g_value):
-        h_actor, h_critic, actions, saved = ctx.saved_tensors
-        ups = [torch.zeros(h_actor.shape[0], device=h_actor.device) if g is None else g.float().contiguous()
+        *h_top, actions, saved = ctx.saved_tensors
+        ups = [torch.zeros(h_top[0].shape[0], device=h_top[0].device) if g is None else g.float().contiguous()
                for g in (g_logp, g_entropy, g_value)]
-        dh_actor, dh_critic, grads = K.recurrent_heads_backward(*ctx.nets, (h_actor, h_critic), actions, ctx.mask,
-                                                                saved, *ups)
+        dh_actor, dh_critic, grads = K.recurrent_heads_backward(*ctx.nets, tuple(h_top), actions, ctx.mask, saved,
+                                                                *ups)
         return (None, None, None, None, dh_actor, dh_critic, *grads)
 
 
@@ -113,8 +126,9 @@ class RecurrentPPO(PPO):
             raise ValueError("use_rollout_buffer must be True if recurrent=True.")
         if actor_network is not None or critic_network is not None:
             raise NotImplementedError("custom actor/critic modules: use net_config networks")
-        if share_encoders:
-            raise NotImplementedError("agx recurrent PPO builds separate actor and critic encoders: pass "
+        if share_encoders and torch.device(device).type != "cuda":
+            # as before the shared form existed: off the GPU the agent is built with separate encoders only
+            raise NotImplementedError("agx recurrent PPO: share_encoders=True needs a CUDA device; on the CPU pass "
                                       "share_encoders=False")
         assert isinstance(batch_size, int) and batch_size >= 1, "Batch size must be an integer greater than or equal to one."
         assert lr > 0, "Learning rate must be greater than zero."
@@ -127,7 +141,8 @@ class RecurrentPPO(PPO):
         self.gamma, self.gae_lambda = gamma, gae_lambda
         self.action_std_init, self.clip_coef, self.ent_coef, self.vf_coef = action_std_init, clip_coef, ent_coef, vf_coef
         self.max_grad_norm, self.target_kl, self.update_epochs = max_grad_norm, target_kl, update_epochs
-        self.num_envs, self.share_encoders, self.recurrent, self.use_rollout_buffer = num_envs, False, True, True
+        self.num_envs, self.share_encoders, self.recurrent = num_envs, bool(share_encoders), True
+        self.use_rollout_buffer = True
         self.rollout_buffer_config = dict(rollout_buffer_config or {})
         self.max_seq_len, self.bptt_sequence_type = max_seq_len, bptt_sequence_type
         self.device = torch.device(device)
@@ -151,10 +166,16 @@ class RecurrentPPO(PPO):
         else:
             critic_head = mlp_net_config([16])
         critic_cfg["head_config"] = critic_head
+        names = ("shared_encoder",) * 2 if self.share_encoders else ("actor_encoder", "critic_encoder")  # ppo.py:308-316
         self.actor = StochasticActor(observation_space, action_space, action_std_init=action_std_init,
-                                     device=self.device, recurrent=True, encoder_name="actor_encoder", **cfg)
+                                     device=self.device, recurrent=True, encoder_name=names[0], **cfg)
         self.critic = ValueNetwork(observation_space, device=self.device, recurrent=True,
-                                   encoder_name="critic_encoder", **critic_cfg)
+                                   encoder_name=names[1], **critic_cfg)
+        if self.share_encoders:
+            # The actor's encoder is the live one.  The critic's is a copy that is never run: it takes no gradient,
+            # is not in the optimiser, and is there so that state_dict() has the reference's keys.
+            self.critic.encoder.requires_grad_(False)
+            self.sync_shared_encoder()
         # the distribution: kernels.HEAD_*, and how many columns a row of stored actions has
         self.head_kind, _, _, self.action_cols = K.recurrent_head(action_space)
         self.discrete = self.head_kind == K.HEAD_DISCRETE
@@ -163,7 +184,15 @@ class RecurrentPPO(PPO):
 
     # ---- the pieces of the reference's agent ----------------------------------
     def reinit_optimizers(self, optimizer=None) -> None:
-        self.optimizer = torch.optim.Adam(list(self.actor.parameters()) + list(self.critic.parameters()), lr=self.lr)
+        params = list(self.actor.parameters()) + [p for p in self.critic.parameters() if p.requires_grad]
+        self.optimizer = torch.optim.Adam(params, lr=self.lr)
+
+    @torch.no_grad()
+    def sync_shared_encoder(self) -> None:
+        """share_encoders: the critic's encoder entries take the actor's values (after every change of those)."""
+        if self.share_encoders:
+            for dst, src in zip(self.critic.encoder.state_dict().values(), self.actor.encoder.state_dict().values()):
+                dst.copy_(src)
 
     def create_rollout_buffer(self) -> None:
         """ppo.py:360-378."""
@@ -177,6 +206,9 @@ class RecurrentPPO(PPO):
                                             **self.rollout_buffer_config)
 
     def get_initial_hidden_state(self, num_envs: int = 1) -> dict[str, torch.Tensor]:
+        """ppo.py:519-525: with a shared encoder the actor's state is the only one."""
+        if self.share_encoders:
+            return self.actor.initialize_hidden_state(batch_size=num_envs)
         return {**self.actor.initialize_hidden_state(batch_size=num_envs),
                 **self.critic.initialize_hidden_state(batch_size=num_envs)}
 
@@ -197,6 +229,7 @@ class RecurrentPPO(PPO):
         for net in ("actor", "critic"):
             getattr(self, net).load_state_dict({k[len(net) + 1:]: v for k, v in state_dict.items()
                                                 if k.startswith(net + ".")}, strict=strict)
+        self.sync_shared_encoder()
 
     def save_checkpoint(self, path: str) -> None:
         raise NotImplementedError("agx recurrent PPO: checkpoints are not written yet (state_dict / load_state_dict)")
@@ -211,9 +244,14 @@ class RecurrentPPO(PPO):
         return obs.to(self.device, torch.float32).reshape(-1, *self.observation_space.shape)
 
     def _get_action_and_values(self, obs, action_mask=None, hidden_state=None, *, sample: bool = True):
-        """ppo.py:400-492 with separate encoders: the actor and the critic take the states of their own keys."""
+        """ppo.py:400-492.  Separate encoders: the actor and the critic take the states of their own keys.  A shared
+        encoder (ppo.py:430-442): the critic's head reads the actor's latent."""
         if hidden_state is None:
             raise ValueError("recurrent PPO acts on a hidden state (get_initial_hidden_state)")
+        if self.share_encoders:
+            latent, next_hidden = self.actor.extract_features(obs, hidden_state=hidden_state)
+            action, log_prob, entropy = self.actor.forward_head(latent, action_mask=action_mask, sample=sample)
+            return action, log_prob, entropy, self.critic.forward_head(latent).squeeze(-1), next_hidden
         actor_h = {k: v for k, v in hidden_state.items() if k.startswith("actor_encoder")}
         critic_h = {k: v for k, v in hidden_state.items() if k.startswith("critic_encoder")}
         latent, next_actor = self.actor.extract_features(obs, hidden_state=actor_h)
@@ -302,9 +340,11 @@ class RecurrentPPO(PPO):
         if params is None or (action_mask is not None and self.head_kind == K.HEAD_BOX):
             return None
         obs = self.preprocess_observation(obs)
-        h_top = [net.encoder.lstm_output(obs, hidden_state)[0] for net in (self.actor, self.critic)]
+        h_top = [net.encoder.lstm_output(obs, hidden_state)[0]
+                 for net in ((self.actor,) if self.share_encoders else (self.actor, self.critic))]
         if any(h.dim() != 2 or h.dtype != torch.float32 for h in h_top):
             return None
+        h_top += [None] * (2 - len(h_top))  # a shared encoder: one LSTM run, no h_top of the critic's
         actions = actions.to(torch.float32).contiguous()
         if actions.shape != ((h_top[0].shape[0],) if self.discrete else (h_top[0].shape[0], self.action_cols)):
             return None
@@ -354,6 +394,7 @@ class RecurrentPPO(PPO):
             if self.target_kl is not None and epoch_kl and (np.mean(epoch_kl) > self.target_kl
                                                             or last_kl > self.target_kl):
                 break
+        self.sync_shared_encoder()
         return mean_loss / max(1e-8, updates)
 
     # ---- evaluation ---------------------------------------------------------------

@@ -53,29 +53,70 @@ __device__ __forceinline__ f32x4 chain_row(int K, int q, f32x4 acc, const float 
     return acc;
 }
 
+// One 16 x 16 output tile of y = x W^T + b, this wave's: the bias, then k ascending
+__device__ __forceinline__ void dense_tile(int tile, const float *X, int ldx, int K, const float *W, const float *b,
+                                           int F, float *Y, int ldy) {
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const bool vec = (K & 3) == 0 && lstm::aligned16(W);
+    const int unit = tile * 16 + r, uu = min(unit, F - 1);
+    const float bv = b[uu];
+    f32x4 acc = {bv, bv, bv, bv};
+    const float *wrow = W + (int64_t)uu * K;
+    acc = vec ? chain_row<true>(K, q, acc, X + r * ldx, wrow) : chain_row<false>(K, q, acc, X + r * ldx, wrow);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + unit] = unit < F ? acc[i] : 0.f;
+}
+
 // Y [16][ldy] = X [16][ldx] W^T + b over the 16-rounded width of F, zeros in the columns past F
 __device__ __forceinline__ void dense(const float *X, int ldx, int K, const float *W, const float *b, int F, float *Y,
                                       int ldy) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = lane & 15, q = lane >> 4;
-    const bool vec = (K & 3) == 0 && lstm::aligned16(W);
-    for (int tile = wave; tile < ((F + 15) >> 4); tile += kRW) {
-        const int unit = tile * 16 + r, uu = min(unit, F - 1);
-        const float bv = b[uu];
-        f32x4 acc = {bv, bv, bv, bv};
-        const float *wrow = W + (int64_t)uu * K;
-        acc = vec ? chain_row<true>(K, q, acc, X + r * ldx, wrow) : chain_row<false>(K, q, acc, X + r * ldx, wrow);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + unit] = unit < F ? acc[i] : 0.f;
+    const int wave = threadIdx.x >> 6;
+    for (int tile = wave; tile < ((F + 15) >> 4); tile += kRW) dense_tile(tile, X, ldx, K, W, b, F, Y, ldy);
+}
+
+// One side of a pair of dense layers that advance together (the two heads over a shared latent): where its input
+// and output tiles lie; `on`: the side still has a layer at this depth.
+struct DenseSide {
+    const float *X;
+    float *Y;
+    int ldx, ldy;
+    bool on;
+
+    // the next layer reads what the last one wrote and writes `to`
+    __device__ __forceinline__ void advance(float *to, int out) {
+        X = Y;
+        ldx = ldy;
+        Y = to;
+        ldy = ((out + 15) & ~15) + 4;
+    }
+};
+
+// `dense` of both sides' layers la and lc as one tile list, side a's tiles first: the 8 waves share the list, so a
+// depth of the pair costs the barriers of one layer.  A tile is still one wave's chain, with the bits `dense`
+// gives it.
+__device__ __forceinline__ void dense_pair(const agx_recurrent_linear &la, const DenseSide &a,
+                                           const agx_recurrent_linear &lc, const DenseSide &c) {
+    const int wave = threadIdx.x >> 6;
+    const int ta = a.on ? (la.out + 15) >> 4 : 0, tc = c.on ? (lc.out + 15) >> 4 : 0;
+    for (int tile = wave; tile < ta + tc; tile += kRW) {
+        if (tile < ta)
+            dense_tile(tile, a.X, a.ldx, la.in, la.w, la.b, la.out, a.Y, a.ldy);
+        else
+            dense_tile(tile - ta, c.X, c.ldx, lc.in, lc.w, lc.b, lc.out, c.Y, c.ldy);
     }
 }
 
+// the row passes of both sides' layers at once: side a on waves 0 .. 3, side c on waves 4 .. 7
+__device__ __forceinline__ void row_pass_pair(const agx_recurrent_linear &la, const DenseSide &a,
+                                              const agx_recurrent_linear &lc, const DenseSide &c);
+
 // LayerNorm (affine lnw / lnb, eps 1e-5; null: none) and the activation over the F columns of every row of
 // Y [16][ld] in place: waves 0 .. 3, 16 lanes per row.  The loops run to the 16-rounded width, so the row
-// reductions see whole DPP rows.
-__device__ __forceinline__ void row_pass(float *Y, int ld, int F, const float *lnw, const float *lnb, int act) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (wave >= 4 || (!lnw && act == AGX_RECURRENT_ACT_NONE)) return;
+// reductions see whole DPP rows.  w0 = 4 puts the pass on waves 4 .. 7, beside another tile's pass on waves 0 .. 3.
+__device__ __forceinline__ void row_pass(float *Y, int ld, int F, const float *lnw, const float *lnb, int act,
+                                         int w0 = 0) {
+    const int wave = (int)(threadIdx.x >> 6) - w0, lane = threadIdx.x & 63;
+    if (wave < 0 || wave >= 4 || (!lnw && act == AGX_RECURRENT_ACT_NONE)) return;
     const int sub = lane & 15, F16 = (F + 15) & ~15;
     float *y = Y + (4 * wave + (lane >> 4)) * ld;
     float mean = 0.f, rstd = 1.f;
@@ -97,6 +138,13 @@ __device__ __forceinline__ void row_pass(float *Y, int ld, int F, const float *l
         if (act == AGX_RECURRENT_ACT_TANH) x = tanhf(x);
         y[j] = x;
     }
+}
+
+__device__ __forceinline__ void row_pass_pair(const agx_recurrent_linear &la, const DenseSide &a,
+                                              const agx_recurrent_linear &lc, const DenseSide &c) {
+    if (a.on) row_pass(a.Y, a.ldy, la.out, la.ln_w, la.ln_b, la.relu ? AGX_RECURRENT_ACT_RELU : AGX_RECURRENT_ACT_NONE);
+    if (c.on)
+        row_pass(c.Y, c.ldy, lc.out, lc.ln_w, lc.ln_b, lc.relu ? AGX_RECURRENT_ACT_RELU : AGX_RECURRENT_ACT_NONE, 4);
 }
 
 }  // namespace agx

@@ -36,6 +36,10 @@
 // saved input, or 1 for the bias tile), or 64 columns of a LayerNorm's affine
 // gradients, or log_std's gradient: column sums over rows ascending.  No sum
 // is split across waves.
+//
+// The shared-encoder forms (agx_recurrent_heads_*_shared) run the forward and the backward rows on a grid of
+// (ceil(R / 16), 1): one workgroup takes both heads off one latent tile and back to it (the kernels' own comments),
+// and the parameter pass has one output Linear in its job list.
 #include "../../include/agx_recurrent_heads.h"
 
 #include "agx_common.h"
@@ -120,17 +124,27 @@ __device__ __forceinline__ f32x4 chain_colk(int K, int q, f32x4 acc, const float
     return acc;
 }
 
+// one 16 x 16 tile of Y = G W, this wave's
+__device__ __forceinline__ void dense_t_tile(int tile, const float *G, int ldg, int F, const float *W, int K, float *Y,
+                                             int ldy) {
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const int col = tile * 16 + r;
+    const f32x4 acc = chain_colk(F, q, f32x4{0.f, 0.f, 0.f, 0.f}, G + r * ldg, W + min(col, K - 1), K);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + col] = col < K ? acc[i] : 0.f;
+}
+
 // Y [16][ldy] = G [16][ldg] W over the 16-rounded width of K, W [F][K]; zeros in the columns past K
 __device__ __forceinline__ void dense_t(const float *G, int ldg, int F, const float *W, int K, float *Y, int ldy) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = lane & 15, q = lane >> 4;
-    for (int tile = wave; tile < ((K + 15) >> 4); tile += kRW) {
-        const int col = tile * 16 + r;
-        const f32x4 acc = chain_colk(F, q, f32x4{0.f, 0.f, 0.f, 0.f}, G + r * ldg, W + min(col, K - 1), K);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + col] = col < K ? acc[i] : 0.f;
-    }
+    const int wave = threadIdx.x >> 6;
+    for (int tile = wave; tile < ((K + 15) >> 4); tile += kRW) dense_t_tile(tile, G, ldg, F, W, K, Y, ldy);
 }
+
+// One head's place in the shared-encoder kernels' walk: the tile at hand and its row stride
+struct Walk {
+    float *G;
+    int ld;
+};
 
 // ---------------------------------------------------------------------------
 // forward
@@ -248,6 +262,23 @@ __device__ __forceinline__ void bern_rows(const RowArgs &a, const float *Y, int 
     }
 }
 
+// the actor's distribution over the 16 rows of its head's output Y [16][ld]
+__device__ __forceinline__ void actor_rows(const RowArgs &a, const float *Y, int ld, int b0, float *keep) {
+    if (a.box == AGX_RECURRENT_HEAD_BOX)
+        gauss_rows(a, Y, ld, b0, keep);
+    else if (a.box == AGX_RECURRENT_HEAD_MULTI)
+        multi_rows(a, Y, ld, b0, keep);
+    else if (a.box == AGX_RECURRENT_HEAD_BERNOULLI)
+        bern_rows(a, Y, ld, b0, keep);
+    else
+        categorical_rows(a, Y, ld, b0, keep);
+}
+
+__device__ __forceinline__ void value_rows(const RowArgs &a, const float *Y, int ld, int b0) {
+    const int row = b0 + threadIdx.x;
+    if (threadIdx.x < 16 && row < a.R) a.value[row] = Y[threadIdx.x * ld];
+}
+
 template <bool SAVE>
 __global__ __launch_bounds__(kRT) void heads_fwd_kernel(const RowArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -285,19 +316,54 @@ __global__ __launch_bounds__(kRT) void heads_fwd_kernel(const RowArgs a) {
         __syncthreads();
         if (SAVE && j < n.n_head - 1) store_rows(Y, ldY, F, a.saved + n.sv_act[j], R, b0);
     }
-    float *keep = SAVE ? a.saved + n.sv_out : nullptr;
-    if (critic) {
-        const int row = b0 + threadIdx.x;
-        if (threadIdx.x < 16 && row < R) a.value[row] = Y[threadIdx.x * ldY];
-    } else if (a.box == AGX_RECURRENT_HEAD_BOX) {
-        gauss_rows(a, Y, ldY, b0, keep);
-    } else if (a.box == AGX_RECURRENT_HEAD_MULTI) {
-        multi_rows(a, Y, ldY, b0, keep);
-    } else if (a.box == AGX_RECURRENT_HEAD_BERNOULLI) {
-        bern_rows(a, Y, ldY, b0, keep);
-    } else {
-        categorical_rows(a, Y, ldY, b0, keep);
+    if (critic)
+        value_rows(a, Y, ldY, b0);
+    else
+        actor_rows(a, Y, ldY, b0, SAVE ? a.saved + n.sv_out : nullptr);
+}
+
+// The shared-encoder forward (agx_recurrent_heads_forward_shared), grid (ceil(R / 16), 1): net[0]'s output Linear
+// once per row tile, then both heads off the one latent tile.  Four LDS slots: the h_top tile in slot 2, the latent
+// in slot 0, the actor's head on between slots 1 and 0 as above, the critic's between slots 2 and 3 (h_top is dead
+// once the latent is whole).  Depth j of both heads is one tile list over the 8 waves (dense_pair) and one row
+// pass (actor: waves 0 .. 3, critic: 4 .. 7); the actor's depth 1 overwrites the latent after the barrier that ends
+// depth 0, where the critic has read it and the saving form has stored it.
+template <bool SAVE>
+__global__ __launch_bounds__(kRT) void heads_fwd_shared_kernel(const RowArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Net &na = a.net[0], &nc = a.net[1];
+    const int R = a.R, H = na.H, ldh = H + 4;
+    const int b0 = blockIdx.x * 16;
+    float *xs = lds + 2 * a.slot;
+
+    lstm::stage_step(xs, ldh, na.h_top, R, 1, 0, H, H, b0);
+    __syncthreads();
+    const int ldl = r16(na.latent) + 4;
+    dense(xs, ldh, H, na.out_w, na.out_b, na.latent, lds, ldl);
+    __syncthreads();
+    row_pass(lds, ldl, na.latent, nullptr, nullptr, na.out_act);
+    __syncthreads();
+    if (SAVE) store_rows(lds, ldl, na.latent, a.saved + na.sv_lat, R, b0);
+    DenseSide sa{nullptr, lds, 0, ldl, true}, sc{nullptr, lds, 0, ldl, true};
+    for (int j = 0; j < (na.n_head > nc.n_head ? na.n_head : nc.n_head); ++j) {
+        const agx_recurrent_linear &la = na.head[min(j, na.n_head - 1)], &lc = nc.head[min(j, nc.n_head - 1)];
+        sa.on = j < na.n_head;
+        sc.on = j < nc.n_head;
+        if (sa.on) sa.advance(lds + ((j + 1) & 1) * a.slot, la.out);
+        if (sc.on) sc.advance(lds + (2 + (j & 1)) * a.slot, lc.out);
+        dense_pair(la, sa, lc, sc);
+        __syncthreads();
+        const bool pa = SAVE && sa.on && la.ln_w, pc = SAVE && sc.on && lc.ln_w;
+        if (pa) store_rows(sa.Y, sa.ldy, la.out, a.saved + na.sv_pre[j], R, b0);
+        if (pc) store_rows(sc.Y, sc.ldy, lc.out, a.saved + nc.sv_pre[j], R, b0);
+        if (pa || pc) __syncthreads();  // the row pass works in place
+        row_pass_pair(la, sa, lc, sc);
+        __syncthreads();
+        if (SAVE && j < na.n_head - 1) store_rows(sa.Y, sa.ldy, la.out, a.saved + na.sv_act[j], R, b0);
+        if (SAVE && j < nc.n_head - 1) store_rows(sc.Y, sc.ldy, lc.out, a.saved + nc.sv_act[j], R, b0);
     }
+    value_rows(a, sc.Y, sc.ldy, b0);
+    actor_rows(a, sa.Y, sa.ldy, b0, SAVE ? a.saved + na.sv_out : nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -373,10 +439,11 @@ __device__ __forceinline__ void head_grad_rows32(const RowArgs &a, const Net &n,
 }
 
 // dA -> dZ of hidden head layer j over the rows of G [16][ld] in place: the ReLU mask from the layer's saved output,
-// then the LayerNorm backward (16 lanes per row; the row statistics as row_pass takes them)
-__device__ __forceinline__ void hidden_grad_rows(const RowArgs &a, const Net &n, int j, float *G, int ld, int b0) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (wave >= 4) return;
+// then the LayerNorm backward (16 lanes per row; the row statistics as row_pass takes them), on waves w0 .. w0 + 3
+__device__ __forceinline__ void hidden_grad_rows(const RowArgs &a, const Net &n, int j, float *G, int ld, int b0,
+                                                 int w0 = 0) {
+    const int wave = (int)(threadIdx.x >> 6) - w0, lane = threadIdx.x & 63;
+    if (wave < 0 || wave >= 4) return;
     const agx_recurrent_linear &hl = n.head[j];
     const int sub = lane & 15, rl = 4 * wave + (lane >> 4);
     const int F = hl.out, F16 = r16(F), row = b0 + rl;
@@ -481,6 +548,78 @@ __global__ __launch_bounds__(kRT) void heads_bwd_rows_kernel(const RowArgs a) {
     }
 }
 
+// The shared-encoder backward rows (agx_recurrent_heads_backward_shared), grid (ceil(R / 16), 1): one workgroup
+// walks both heads back to the latent, the actor between slots 0 and 1, the critic between slots 2 and 3.  Step t
+// takes the actor's layer n_a - 1 - t and the critic's n_c - 1 - t: the two row passes side by side (waves 0 .. 3
+// and 4 .. 7) and the two dX = dZ W as one tile list over the 8 waves.  A head that has reached the latent keeps
+// its dX where it is.  Then dLatent = dX_actor + dX_critic, in that order, the output activation's backward once,
+// one dZ_out to the workspace and one dh_top = dZ_out W_out.
+__global__ __launch_bounds__(kRT) void heads_bwd_rows_shared_kernel(const RowArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Net &na = a.net[0], &nc = a.net[1];
+    const int R = a.R, H = na.H;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = lane & 15, q = lane >> 4;
+    const int b0 = blockIdx.x * 16;
+    Walk wa{lds, r16(a.A) + 4}, wc{lds + 2 * a.slot, 16 + 4};
+    if (a.box >= AGX_RECURRENT_HEAD_MULTI)
+        head_grad_rows32(a, na, wa.G, wa.ld, b0);
+    else
+        head_grad_rows(a, na, false, wa.G, wa.ld, b0);
+    head_grad_rows(a, nc, true, wc.G, wc.ld, b0);
+    __syncthreads();
+    for (int t = 0; t < (na.n_head > nc.n_head ? na.n_head : nc.n_head); ++t) {
+        const int ja = na.n_head - 1 - t, jc = nc.n_head - 1 - t;
+        const bool ra = ja >= 0 && t > 0, rc = jc >= 0 && t > 0;  // hidden layers: dA -> dZ first
+        if (ra) hidden_grad_rows(a, na, ja, wa.G, wa.ld, b0);
+        if (rc) hidden_grad_rows(a, nc, jc, wc.G, wc.ld, b0, 4);
+        if (ra || rc) __syncthreads();
+        const bool oa = ja >= 0, oc = jc >= 0;
+        const agx_recurrent_linear &la = na.head[max(ja, 0)], &lc = nc.head[max(jc, 0)];
+        if (oa) store_rows(wa.G, wa.ld, la.out, a.ws + na.ws_dz[ja], R, b0);
+        if (oc) store_rows(wc.G, wc.ld, lc.out, a.ws + nc.ws_dz[jc], R, b0);
+        float *Xa = lds + ((t + 1) & 1) * a.slot, *Xc = lds + (2 + ((t + 1) & 1)) * a.slot;
+        const int ta = oa ? (la.in + 15) >> 4 : 0, tc = oc ? (lc.in + 15) >> 4 : 0;
+        for (int tile = wave; tile < ta + tc; tile += kRW) {
+            if (tile < ta)
+                dense_t_tile(tile, wa.G, wa.ld, la.out, la.w, la.in, Xa, r16(la.in) + 4);
+            else
+                dense_t_tile(tile - ta, wc.G, wc.ld, lc.out, lc.w, lc.in, Xc, r16(lc.in) + 4);
+        }
+        __syncthreads();
+        if (oa) wa = Walk{Xa, r16(la.in) + 4};
+        if (oc) wc = Walk{Xc, r16(lc.in) + 4};
+    }
+    // dLatent, the latent's activation, then the output Linear
+    const int F = na.latent;
+    float *G = wa.G;
+    const int ldG = wa.ld;
+    if (wave < 4) {
+        const int rl = 4 * wave + q, row = b0 + rl;
+        const float *lat = a.saved + na.sv_lat + (int64_t)(row < R ? row : 0) * F;
+        for (int k = r; k < F; k += 16) {
+            const float g = G[rl * ldG + k] + wc.G[rl * wc.ld + k];
+            float dz = g;
+            if (na.out_act != AGX_RECURRENT_ACT_NONE) {
+                const float y = row < R ? lat[k] : 0.f;
+                dz = na.out_act == AGX_RECURRENT_ACT_RELU ? (y > 0.f ? g : 0.f) : g * (1.f - y * y);
+            }
+            G[rl * ldG + k] = dz;
+        }
+    }
+    __syncthreads();
+    store_rows(G, ldG, F, a.ws + na.ws_dzo, R, b0);
+    for (int tile = wave; tile < (H >> 4); tile += kRW) {
+        const int col = tile * 16 + r;
+        const f32x4 acc = chain_colk(F, q, f32x4{0.f, 0.f, 0.f, 0.f}, G + r * ldG, na.out_w + col, H);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = b0 + 4 * q + i;
+            if (row < R) a.dh_top[0][(int64_t)row * H + col] = acc[i];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // backward, parameters
 
@@ -579,17 +718,10 @@ __global__ __launch_bounds__(kRT) void heads_bwd_params_kernel(const ParamArgs a
 // ---------------------------------------------------------------------------
 // host
 
-int check_net(const agx_recurrent_net &n, int H, const float *h_top, int out, const char *name, const char *who) {
-    AGX_REQUIRE(H >= 16 && H <= AGX_LSTM_MAX_HIDDEN && H % 16 == 0,
-                "%s: %s: hidden size %d is not a multiple of 16 in [16, %d]", who, name, H, AGX_LSTM_MAX_HIDDEN);
-    AGX_REQUIRE(h_top && n.out_w && n.out_b, "%s: %s: h_top or the output Linear is NULL", who, name);
-    AGX_REQUIRE(n.latent >= 1 && n.latent <= AGX_PPO_GRAPH_MAX_WIDTH, "%s: %s: latent %d outside [1, %d]", who, name,
-                n.latent, AGX_PPO_GRAPH_MAX_WIDTH);
-    AGX_REQUIRE(n.out_act >= AGX_RECURRENT_ACT_NONE && n.out_act <= AGX_RECURRENT_ACT_TANH,
-                "%s: %s: output activation %d", who, name, n.out_act);
+// the head of n over a latent of `width` floats
+int check_head(const agx_recurrent_net &n, int width, int out, const char *name, const char *who) {
     AGX_REQUIRE(n.n_head >= 2 && n.n_head <= AGX_RECURRENT_MAX_HEAD, "%s: %s: %d head layers outside [2, %d]", who,
                 name, n.n_head, AGX_RECURRENT_MAX_HEAD);
-    int width = n.latent;
     for (int j = 0; j < n.n_head; ++j) {
         const agx_recurrent_linear &h = n.head[j];
         const bool last = j == n.n_head - 1;
@@ -603,7 +735,19 @@ int check_net(const agx_recurrent_net &n, int H, const float *h_top, int out, co
     return AGX_OK;
 }
 
-int check_heads(const agx_recurrent_heads *heads, const char *who) {
+int check_net(const agx_recurrent_net &n, int H, const float *h_top, int out, const char *name, const char *who) {
+    AGX_REQUIRE(H >= 16 && H <= AGX_LSTM_MAX_HIDDEN && H % 16 == 0,
+                "%s: %s: hidden size %d is not a multiple of 16 in [16, %d]", who, name, H, AGX_LSTM_MAX_HIDDEN);
+    AGX_REQUIRE(h_top && n.out_w && n.out_b, "%s: %s: h_top or the output Linear is NULL", who, name);
+    AGX_REQUIRE(n.latent >= 1 && n.latent <= AGX_PPO_GRAPH_MAX_WIDTH, "%s: %s: latent %d outside [1, %d]", who, name,
+                n.latent, AGX_PPO_GRAPH_MAX_WIDTH);
+    AGX_REQUIRE(n.out_act >= AGX_RECURRENT_ACT_NONE && n.out_act <= AGX_RECURRENT_ACT_TANH,
+                "%s: %s: output activation %d", who, name, n.out_act);
+    return check_head(n, n.latent, out, name, who);
+}
+
+// shared: net[1] gives its head only, over net[0]'s latent
+int check_heads(const agx_recurrent_heads *heads, const char *who, bool shared) {
     AGX_REQUIRE(heads, "%s: heads is NULL", who);
     const agx_recurrent_heads &s = *heads;
     AGX_REQUIRE(s.R >= 1 && s.R <= (1 << 24), "%s: R %lld outside [1, 2^24]", who, (long long)s.R);
@@ -620,27 +764,32 @@ int check_heads(const agx_recurrent_heads *heads, const char *who) {
         AGX_REQUIRE(L == s.A, "%s: nvec sums to %d, the head has %d logits", who, L, s.A);
     }
     if (int rc = check_net(s.net[0], s.H[0], s.h_top[0], s.A, "actor", who)) return rc;
+    if (shared) return check_head(s.net[1], s.net[0].latent, 1, "critic", who);
     return check_net(s.net[1], s.H[1], s.h_top[1], 1, "critic", who);
 }
 
-// The networks as the kernels read them and the sizes of `saved` and of the workspace, in floats
-void plan(const agx_recurrent_heads &s, Net (&net)[2], int64_t &saved, int64_t &ws) {
+// The networks as the kernels read them and the sizes of `saved` and of the workspace, in floats.  shared: the
+// critic's Net is its head over the actor's output Linear, latent and dZ_out, which are kept once.
+void plan(const agx_recurrent_heads &s, Net (&net)[2], int64_t &saved, int64_t &ws, bool shared) {
     saved = ws = 0;
     const int64_t R = s.R;
     for (int k = 0; k < 2; ++k) {
-        const agx_recurrent_net &d = s.net[k];
+        const bool own = k == 0 || !shared;  // the network has an output Linear of its own
+        const agx_recurrent_net &d = s.net[k], &e = s.net[own ? k : 0];
         Net &n = net[k];
-        n.h_top = s.h_top[k];
-        n.out_w = d.out_w;
-        n.out_b = d.out_b;
-        n.H = s.H[k];
-        n.latent = d.latent;
-        n.out_act = d.out_act;
+        n.h_top = s.h_top[own ? k : 0];
+        n.out_w = e.out_w;
+        n.out_b = e.out_b;
+        n.H = s.H[own ? k : 0];
+        n.latent = e.latent;
+        n.out_act = e.out_act;
         n.n_head = d.n_head;
-        n.sv_lat = saved;
-        saved += R * d.latent;
-        n.ws_dzo = ws;
-        ws += R * d.latent;
+        n.sv_lat = own ? saved : net[0].sv_lat;
+        n.ws_dzo = own ? ws : net[0].ws_dzo;
+        if (own) {
+            saved += R * d.latent;
+            ws += R * d.latent;
+        }
         for (int j = 0; j < AGX_RECURRENT_MAX_HEAD; ++j) {
             const bool on = j < d.n_head;
             n.head[j] = on ? d.head[j] : agx_recurrent_linear{};
@@ -670,9 +819,9 @@ int widest(const Net &n) {
     return w;
 }
 
-RowArgs row_args(const agx_recurrent_heads &s, int64_t &saved, int64_t &ws) {
+RowArgs row_args(const agx_recurrent_heads &s, int64_t &saved, int64_t &ws, bool shared) {
     RowArgs a{};
-    plan(s, a.net, saved, ws);
+    plan(s, a.net, saved, ws, shared);
     a.actions = s.actions;
     a.log_std = s.log_std;
     a.mask = s.mask;
@@ -693,55 +842,52 @@ void allow_lds() {
                                   kLdsCap);
         (void)hipFuncSetAttribute((const void *)heads_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   kLdsCap);
+        (void)hipFuncSetAttribute((const void *)heads_fwd_shared_kernel<false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap);
+        (void)hipFuncSetAttribute((const void *)heads_fwd_shared_kernel<true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap);
+        (void)hipFuncSetAttribute((const void *)heads_bwd_rows_shared_kernel,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap);
         return true;
     }();
     (void)once;
 }
 
-}  // namespace
-}  // namespace agx
-
-using namespace agx;
-
-extern "C" size_t agx_recurrent_heads_saved_bytes(const agx_recurrent_heads *heads) {
-    if (check_heads(heads, "agx_recurrent_heads_saved_bytes")) return 0;
+size_t plan_bytes(const agx_recurrent_heads *heads, bool shared, bool workspace, const char *who) {
+    if (check_heads(heads, who, shared)) return 0;
     int64_t saved, ws;
-    (void)row_args(*heads, saved, ws);
-    return (size_t)saved * sizeof(float);
+    (void)row_args(*heads, saved, ws, shared);
+    return (size_t)(workspace ? ws : saved) * sizeof(float);
 }
 
-extern "C" size_t agx_recurrent_heads_workspace_bytes(const agx_recurrent_heads *heads) {
-    if (check_heads(heads, "agx_recurrent_heads_workspace_bytes")) return 0;
-    int64_t saved, ws;
-    (void)row_args(*heads, saved, ws);
-    return (size_t)ws * sizeof(float);
-}
-
-extern "C" int agx_recurrent_heads_forward(const agx_recurrent_heads *heads, float *log_prob, float *entropy,
-                                           float *value, void *saved, void *stream) {
-    const char *who = "agx_recurrent_heads_forward";
-    if (int rc = check_heads(heads, who)) return rc;
+int heads_forward(const agx_recurrent_heads *heads, float *log_prob, float *entropy, float *value, void *saved,
+                  void *stream, bool shared, const char *who) {
+    if (int rc = check_heads(heads, who, shared)) return rc;
     AGX_REQUIRE(log_prob && entropy && value, "%s: an output is NULL", who);
     int64_t nsaved, nws;
-    RowArgs a = row_args(*heads, nsaved, nws);
+    RowArgs a = row_args(*heads, nsaved, nws, shared);
     a.log_prob = log_prob;
     a.entropy = entropy;
     a.value = value;
     a.saved = static_cast<float *>(saved);
     allow_lds();
-    const dim3 grid((unsigned)ceil_div(heads->R, 16), 2);
-    const size_t bytes = (size_t)3 * a.slot * sizeof(float);  // at most 3 * 16 * 516 * 4 = 97 KB
-    if (saved)
+    const dim3 grid((unsigned)ceil_div(heads->R, 16), shared ? 1 : 2);
+    // 3 slots, at most 3 * 16 * 516 * 4 = 97 KB; shared: 4 slots, at most 129 KB
+    const size_t bytes = (size_t)(shared ? 4 : 3) * a.slot * sizeof(float);
+    if (shared && saved)
+        hipLaunchKernelGGL(heads_fwd_shared_kernel<true>, grid, dim3(kRT), bytes, as_stream(stream), a);
+    else if (shared)
+        hipLaunchKernelGGL(heads_fwd_shared_kernel<false>, grid, dim3(kRT), bytes, as_stream(stream), a);
+    else if (saved)
         hipLaunchKernelGGL(heads_fwd_kernel<true>, grid, dim3(kRT), bytes, as_stream(stream), a);
     else
         hipLaunchKernelGGL(heads_fwd_kernel<false>, grid, dim3(kRT), bytes, as_stream(stream), a);
     return check_launch(who);
 }
 
-extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, const void *saved,
-                                            const agx_recurrent_heads_grads *grads, void *workspace, void *stream) {
-    const char *who = "agx_recurrent_heads_backward";
-    if (int rc = check_heads(heads, who)) return rc;
+int heads_backward(const agx_recurrent_heads *heads, const void *saved, const agx_recurrent_heads_grads *grads,
+                   void *workspace, void *stream, bool shared, const char *who) {
+    if (int rc = check_heads(heads, who, shared)) return rc;
     AGX_REQUIRE(saved && grads && workspace, "%s: saved, grads or the workspace is NULL", who);
     const agx_recurrent_heads &s = *heads;
     const agx_recurrent_heads_grads &g = *grads;
@@ -749,7 +895,8 @@ extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, co
     AGX_REQUIRE((s.box == AGX_RECURRENT_HEAD_BOX) == (g.log_std != nullptr), "%s: log_std's gradient goes with Box",
                 who);
     for (int k = 0; k < 2; ++k) {
-        AGX_REQUIRE(g.dh_top[k] && g.out_w[k] && g.out_b[k], "%s: network %d: a gradient output is NULL", who, k);
+        AGX_REQUIRE((shared && k == 1) || (g.dh_top[k] && g.out_w[k] && g.out_b[k]),
+                    "%s: network %d: a gradient output is NULL", who, k);
         for (int j = 0; j < s.net[k].n_head; ++j) {
             const agx_recurrent_linear_grad &o = g.head[k][j];
             AGX_REQUIRE(o.w && o.b && (!s.net[k].head[j].ln_w || (o.ln_w && o.ln_b)),
@@ -757,7 +904,7 @@ extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, co
         }
     }
     int64_t nsaved, nws;
-    RowArgs a = row_args(s, nsaved, nws);
+    RowArgs a = row_args(s, nsaved, nws, shared);
     float *sv = const_cast<float *>(static_cast<const float *>(saved)), *ws = static_cast<float *>(workspace);
     a.saved = sv;
     a.ws = ws;
@@ -765,19 +912,26 @@ extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, co
     a.g_ent = g.g_entropy;
     a.g_val = g.g_value;
     a.dh_top[0] = g.dh_top[0];
-    a.dh_top[1] = g.dh_top[1];
+    a.dh_top[1] = shared ? nullptr : g.dh_top[1];
     allow_lds();
-    const dim3 grid((unsigned)ceil_div(s.R, 16), 2);
-    hipLaunchKernelGGL(heads_bwd_rows_kernel, grid, dim3(kRT), (size_t)2 * a.slot * sizeof(float), as_stream(stream), a);
+    const dim3 grid((unsigned)ceil_div(s.R, 16), shared ? 1 : 2);
+    if (shared)
+        hipLaunchKernelGGL(heads_bwd_rows_shared_kernel, grid, dim3(kRT), (size_t)4 * a.slot * sizeof(float),
+                           as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(heads_bwd_rows_kernel, grid, dim3(kRT), (size_t)2 * a.slot * sizeof(float),
+                           as_stream(stream), a);
     if (int rc = check_launch(who)) return rc;
 
     ParamArgs p{};
     int jobs = 0;
     for (int k = 0; k < 2; ++k) {
         const Net &n = a.net[k];
-        ParamLayer &o = p.layer[p.n_layers++];
-        o = ParamLayer{ws + n.ws_dzo, n.h_top, g.out_w[k], g.out_b[k], n.H, n.latent, jobs, (n.H + 15) / 16 + 1};
-        jobs += ((n.latent + 15) / 16) * o.ct;
+        if (k == 0 || !shared) {  // shared: one output Linear, its dZ the sum of both heads' shares
+            ParamLayer &o = p.layer[p.n_layers++];
+            o = ParamLayer{ws + n.ws_dzo, n.h_top, g.out_w[k], g.out_b[k], n.H, n.latent, jobs, (n.H + 15) / 16 + 1};
+            jobs += ((n.latent + 15) / 16) * o.ct;
+        }
         for (int j = 0; j < n.n_head; ++j) {
             const agx_recurrent_linear &hl = n.head[j];
             ParamLayer &l = p.layer[p.n_layers++];
@@ -807,4 +961,46 @@ extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, co
     p.g_log_std = g.log_std;
     hipLaunchKernelGGL(heads_bwd_params_kernel, dim3((unsigned)ceil_div(jobs, kRW)), dim3(kRT), 0, as_stream(stream), p);
     return check_launch(who);
+}
+
+}  // namespace
+}  // namespace agx
+
+using namespace agx;
+
+extern "C" size_t agx_recurrent_heads_saved_bytes(const agx_recurrent_heads *heads) {
+    return plan_bytes(heads, false, false, "agx_recurrent_heads_saved_bytes");
+}
+
+extern "C" size_t agx_recurrent_heads_workspace_bytes(const agx_recurrent_heads *heads) {
+    return plan_bytes(heads, false, true, "agx_recurrent_heads_workspace_bytes");
+}
+
+extern "C" int agx_recurrent_heads_forward(const agx_recurrent_heads *heads, float *log_prob, float *entropy,
+                                           float *value, void *saved, void *stream) {
+    return heads_forward(heads, log_prob, entropy, value, saved, stream, false, "agx_recurrent_heads_forward");
+}
+
+extern "C" int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, const void *saved,
+                                            const agx_recurrent_heads_grads *grads, void *workspace, void *stream) {
+    return heads_backward(heads, saved, grads, workspace, stream, false, "agx_recurrent_heads_backward");
+}
+
+extern "C" size_t agx_recurrent_heads_saved_bytes_shared(const agx_recurrent_heads *heads) {
+    return plan_bytes(heads, true, false, "agx_recurrent_heads_saved_bytes_shared");
+}
+
+extern "C" size_t agx_recurrent_heads_workspace_bytes_shared(const agx_recurrent_heads *heads) {
+    return plan_bytes(heads, true, true, "agx_recurrent_heads_workspace_bytes_shared");
+}
+
+extern "C" int agx_recurrent_heads_forward_shared(const agx_recurrent_heads *heads, float *log_prob, float *entropy,
+                                                  float *value, void *saved, void *stream) {
+    return heads_forward(heads, log_prob, entropy, value, saved, stream, true, "agx_recurrent_heads_forward_shared");
+}
+
+extern "C" int agx_recurrent_heads_backward_shared(const agx_recurrent_heads *heads, const void *saved,
+                                                   const agx_recurrent_heads_grads *grads, void *workspace,
+                                                   void *stream) {
+    return heads_backward(heads, saved, grads, workspace, stream, true, "agx_recurrent_heads_backward_shared");
 }

@@ -40,6 +40,9 @@
 // row and one logit per lane (seg_scan.h): a component is a run of lanes, and
 // its max, sum exp, entropy and Gumbel arg-max are segmented scans whose cost
 // does not depend on the number of components.
+//
+// The shared-encoder form (agx_ppo_act_recurrent_shared, recurrent_step_shared_kernel below) runs a grid of
+// (ceil(N / 16), 1): the same LSTM and output Linear once per row tile, then both heads in that workgroup.
 #include "../../include/agx_recurrent.h"
 
 #include <cstddef>
@@ -186,15 +189,14 @@ __device__ __forceinline__ void bern_step(const StepArgs &s, const float *Y, int
     if (g.j == 0 && s.log_probs) s.log_probs[row] = lp;
 }
 
-__global__ __launch_bounds__(kRT) void recurrent_step_kernel(const StepArgs s, const int slot) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const bool critic = blockIdx.y != 0;
-    const agx_recurrent_net &n = critic ? s.critic : s.actor;
+// The LSTM of network n at T = 1 over env rows b0 .. b0 + 15: h' of the top layer ends in slot 2 + ((L - 1) & 1),
+// whole, and slots 0 and 1 are free.  `keep_obs`: this workgroup also writes the rollout slot's copy of obs.
+__device__ __forceinline__ void lstm_step(const StepArgs &s, const agx_recurrent_net &n, float *lds, int slot, int b0,
+                                          bool keep_obs) {
     const int N = (int)s.N, H = n.lstm.H, L = n.lstm.L, in = n.lstm.in;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane & 15, q = lane >> 4;
     const int sr = threadIdx.x >> 5, sc = threadIdx.x & 31;  // staging: 32 threads per row
-    const int b0 = blockIdx.x * 16;
     const int in16 = (in + 15) & ~15, ldx = in16 + 4, ldh = H + 4;
     float *xs = lds, *hs = lds + slot;
     const int srow = b0 + sr;
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(kRT) void recurrent_step_kernel(const StepArgs s, c
     const bool skeep = slive && !(s.reset && s.reset[srow]);  // the row carries its state into the step
 
     lstm::stage_step(xs, ldx, s.obs, N, 1, 0, in, in16, b0);
-    if (!critic && s.obs_store && slive)
+    if (keep_obs && s.obs_store && slive)
         for (int k = sc; k < in; k += 32) s.obs_store[(int64_t)srow * in + k] = s.obs[(int64_t)srow * in + k];
 
     for (int l = 0; l < L; ++l) {
@@ -262,6 +264,32 @@ __global__ __launch_bounds__(kRT) void recurrent_step_kernel(const StepArgs s, c
         }
         __syncthreads();  // h' is whole, and hs is free for the next layer's h_prev
     }
+}
+
+// the actor's distribution over the 16 rows of its head's output Y [16][ld]
+__device__ __forceinline__ void actor_step(const StepArgs &s, const float *Y, int ld, int b0) {
+    if (s.box == AGX_RECURRENT_HEAD_BOX)
+        gauss_step(s, Y, ld, b0);
+    else if (s.box == AGX_RECURRENT_HEAD_MULTI)
+        multi_step(s, Y, ld, b0);
+    else if (s.box == AGX_RECURRENT_HEAD_BERNOULLI)
+        bern_step(s, Y, ld, b0);
+    else
+        categorical_step(s, Y, ld, b0);
+}
+
+__device__ __forceinline__ void value_store(const StepArgs &s, const float *Y, int ld, int b0) {
+    const int row = b0 + threadIdx.x;
+    if (threadIdx.x < 16 && row < (int)s.N && s.values) s.values[row] = Y[threadIdx.x * ld];
+}
+
+__global__ __launch_bounds__(kRT) void recurrent_step_kernel(const StepArgs s, const int slot) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const bool critic = blockIdx.y != 0;
+    const agx_recurrent_net &n = critic ? s.critic : s.actor;
+    const int H = n.lstm.H, L = n.lstm.L, ldh = H + 4;
+    const int b0 = blockIdx.x * 16;
+    lstm_step(s, n, lds, slot, b0, !critic);
 
     // the encoder's output Linear and activation, then the head: slots 0 and 1 in turn
     const float *X = lds + (2 + ((L - 1) & 1)) * slot;
@@ -285,19 +313,49 @@ __global__ __launch_bounds__(kRT) void recurrent_step_kernel(const StepArgs s, c
         row_pass(Y, ldY, F, hl.ln_w, hl.ln_b, hl.relu ? AGX_RECURRENT_ACT_RELU : AGX_RECURRENT_ACT_NONE);
         __syncthreads();
     }
-    if (critic) {
-        const int row = b0 + threadIdx.x;
-        if (threadIdx.x < 16 && row < N && s.values) s.values[row] = Y[threadIdx.x * ldY];
-    } else if (s.box == AGX_RECURRENT_HEAD_BOX) {
-        gauss_step(s, Y, ldY, b0);
-    } else if (s.box == AGX_RECURRENT_HEAD_MULTI) {
-        multi_step(s, Y, ldY, b0);
-    } else if (s.box == AGX_RECURRENT_HEAD_BERNOULLI) {
-        bern_step(s, Y, ldY, b0);
-    } else {
-        categorical_step(s, Y, ldY, b0);
-    }
+    if (critic)
+        value_store(s, Y, ldY, b0);
+    else
+        actor_step(s, Y, ldY, b0);
 }
+
+// The shared-encoder step (agx_ppo_act_recurrent_shared), grid (ceil(N / 16), 1): the LSTM and the output Linear
+// of s.actor once per row tile, then both heads in this workgroup off the one latent tile.  The latent lands in
+// slot 0; by then the LSTM's slots 2 and 3 are dead, so the actor's head goes on between slots 1 and 0 as in the
+// kernel above while the critic's takes slots 2 and 3, and no fifth slot is needed at any shape.  Depth j of both
+// heads is one tile list over the 8 waves (dense_pair) and one row pass (actor: waves 0 .. 3, critic: 4 .. 7)
+// between one pair of barriers; the actor's depth 1 overwrites the latent only after the barrier that ends
+// depth 0, where the critic has read it.  A head that has run out of layers keeps its output where it is.
+__global__ __launch_bounds__(kRT) void recurrent_step_shared_kernel(const StepArgs s, const int slot) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const agx_recurrent_net &n = s.actor;
+    const int H = n.lstm.H, L = n.lstm.L;
+    const int b0 = blockIdx.x * 16;
+    lstm_step(s, n, lds, slot, b0, true);
+
+    const int ldl = ((n.latent + 15) & ~15) + 4;
+    dense(lds + (2 + ((L - 1) & 1)) * slot, H + 4, H, n.out_w, n.out_b, n.latent, lds, ldl);
+    __syncthreads();
+    row_pass(lds, ldl, n.latent, nullptr, nullptr, n.out_act);
+    __syncthreads();
+    DenseSide a{nullptr, lds, 0, ldl, true}, c{nullptr, lds, 0, ldl, true};
+    const int na = n.n_head, nc = s.critic.n_head;
+    for (int j = 0; j < (na > nc ? na : nc); ++j) {
+        const agx_recurrent_linear &la = n.head[min(j, na - 1)], &lc = s.critic.head[min(j, nc - 1)];
+        a.on = j < na;
+        c.on = j < nc;
+        if (a.on) a.advance(lds + ((j + 1) & 1) * slot, la.out);
+        if (c.on) c.advance(lds + (2 + (j & 1)) * slot, lc.out);
+        dense_pair(la, a, lc, c);
+        __syncthreads();
+        row_pass_pair(la, a, lc, c);
+        __syncthreads();
+    }
+    value_store(s, c.Y, c.ldy, b0);
+    actor_step(s, a.Y, a.ldy, b0);
+}
+
+int check_head(const agx_recurrent_net &n, int width, int out, const char *name, const char *who);
 
 int check_net(const agx_recurrent_net &n, int out, const char *name, const char *who) {
     const agx_lstm_desc &d = n.lstm;
@@ -316,9 +374,13 @@ int check_net(const agx_recurrent_net &n, int out, const char *name, const char 
                 n.latent, AGX_PPO_GRAPH_MAX_WIDTH);
     AGX_REQUIRE(n.out_act >= AGX_RECURRENT_ACT_NONE && n.out_act <= AGX_RECURRENT_ACT_TANH,
                 "%s: %s: output activation %d", who, name, n.out_act);
+    return check_head(n, n.latent, out, name, who);
+}
+
+// the head of n over a latent of `width` floats
+int check_head(const agx_recurrent_net &n, int width, int out, const char *name, const char *who) {
     AGX_REQUIRE(n.n_head >= 2 && n.n_head <= AGX_RECURRENT_MAX_HEAD, "%s: %s: %d head layers outside [2, %d]", who,
                 name, n.n_head, AGX_RECURRENT_MAX_HEAD);
-    int width = n.latent;
     for (int j = 0; j < n.n_head; ++j) {
         const agx_recurrent_linear &h = n.head[j];
         const bool last = j == n.n_head - 1;
@@ -344,8 +406,8 @@ int widest(const agx_recurrent_net &n) {
 
 using namespace agx;
 
-extern "C" int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *stream) {
-    const char *who = "agx_ppo_act_recurrent";
+// Both entry points: `shared` takes the encoder of s.actor for both heads and reads the critic's head only
+static int act_recurrent(const agx_recurrent_step *step, void *stream, bool shared, const char *who) {
     AGX_REQUIRE(step, "%s: step is NULL", who);
     const agx_recurrent_step &s = *step;
     AGX_REQUIRE(s.N >= 1 && s.N <= (1 << 24), "%s: N %lld outside [1, 2^24]", who, (long long)s.N);
@@ -366,19 +428,39 @@ extern "C" int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *strea
         k.starts = multi_starts(s.multi);
     }
     if (int rc = check_net(s.actor, s.A, "actor", who)) return rc;
-    if (int rc = check_net(s.critic, 1, "critic", who)) return rc;
-    AGX_REQUIRE(s.actor.lstm.in == s.critic.lstm.in, "%s: the networks read observations of %d and %d floats", who,
-                s.actor.lstm.in, s.critic.lstm.in);
-    const int wa = widest(s.actor), wc = widest(s.critic);
+    int wc = 0;
+    if (shared) {
+        if (int rc = check_head(s.critic, s.actor.latent, 1, "critic", who)) return rc;
+        for (int j = 0; j < s.critic.n_head; ++j) wc = s.critic.head[j].out > wc ? s.critic.head[j].out : wc;
+    } else {
+        if (int rc = check_net(s.critic, 1, "critic", who)) return rc;
+        AGX_REQUIRE(s.actor.lstm.in == s.critic.lstm.in, "%s: the networks read observations of %d and %d floats",
+                    who, s.actor.lstm.in, s.critic.lstm.in);
+        wc = widest(s.critic);
+    }
+    const int wa = widest(s.actor);
     const int slot = 16 * ((((wa > wc ? wa : wc) + 15) & ~15) + 4);
     const size_t bytes = (size_t)4 * slot * sizeof(float);  // at most 4 * 16 * 516 * 4 = 129 KB
     static const bool once = [] {
         (void)hipFuncSetAttribute((const void *)recurrent_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   kLdsCap);
+        (void)hipFuncSetAttribute((const void *)recurrent_step_shared_kernel,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap);
         return true;
     }();
     (void)once;
-    const dim3 grid((unsigned)ceil_div(s.N, 16), 2);
-    hipLaunchKernelGGL(recurrent_step_kernel, grid, dim3(kRT), bytes, as_stream(stream), k, slot);
+    const dim3 grid((unsigned)ceil_div(s.N, 16), shared ? 1 : 2);
+    if (shared)
+        hipLaunchKernelGGL(recurrent_step_shared_kernel, grid, dim3(kRT), bytes, as_stream(stream), k, slot);
+    else
+        hipLaunchKernelGGL(recurrent_step_kernel, grid, dim3(kRT), bytes, as_stream(stream), k, slot);
     return check_launch(who);
+}
+
+extern "C" int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *stream) {
+    return act_recurrent(step, stream, false, "agx_ppo_act_recurrent");
+}
+
+extern "C" int agx_ppo_act_recurrent_shared(const agx_recurrent_step *step, void *stream) {
+    return act_recurrent(step, stream, true, "agx_ppo_act_recurrent_shared");
 }

@@ -1043,7 +1043,11 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     states the step was taken from and of obs.  -> {"actions", "log_probs" (None without ``sample``), "entropy",
     "values", "hidden": the next states}, or None where the kernel does not apply (the caller runs the torch
     modules): see include/agx_recurrent.h for the limits.  MultiDiscrete: mask [N, sum nvec], "actions" [N, K]
-    (each component's index); MultiBinary: mask and "actions" [N, n] (0 / 1)."""
+    (each component's index); MultiBinary: mask and "actions" [N, n] (0 / 1).
+
+    A pair whose encoders are named alike, with one pair of states in ``hidden``, shares one encoder
+    (``share_encoders``): the launch is agx_ppo_act_recurrent_shared, which runs the actor's encoder once and both
+    heads on its latent; the critic's own encoder is not read."""
     from .modules._hooks import hooked
 
     found = recurrent_head(actor.action_space)
@@ -1062,12 +1066,18 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     if box and (head.log_std.dtype != _f32 or not head.log_std.is_cuda or head.log_std.numel() != A):
         return None
     N, dev = obs.shape[0], obs.device
-    sizes = [p[1][0][2] * N * p[1][0][1] for p in (pa, pc)]  # L N H
+    # one encoder for both networks (share_encoders): the encoders are named alike and there is one pair of states
+    shared = pa[0].name == pc[0].name and len(hidden) == 2
+    sizes = [p[1][0][2] * N * p[1][0][1] for p in ((pa,) if shared else (pa, pc))]  # L N H
     nxt = torch.empty(2 * sum(sizes), dtype=_f32, device=dev)
     s = RecurrentStepMulti()
     nh_a = _fill_recurrent_net(s.actor, pa, hidden, N, (nxt[:sizes[0]], nxt[sizes[0]:2 * sizes[0]]), store_hidden)
-    nh_c = _fill_recurrent_net(s.critic, pc, hidden, N, (nxt[2 * sizes[0]:2 * sizes[0] + sizes[1]],
-                                                          nxt[2 * sizes[0] + sizes[1]:]), store_hidden)
+    if shared:  # the critic gives its head; the kernel runs it on the actor's latent
+        _fill_recurrent_dense(s.critic, pc)
+        nh_c = {} if pc[2].out_features == pa[2].out_features else None
+    else:
+        nh_c = _fill_recurrent_net(s.critic, pc, hidden, N, (nxt[2 * sizes[0]:2 * sizes[0] + sizes[1]],
+                                                              nxt[2 * sizes[0] + sizes[1]:]), store_hidden)
     if nh_a is None or nh_c is None:
         return None
     out = out or {}
@@ -1105,7 +1115,7 @@ def ppo_act_recurrent(actor, critic, obs, hidden, *, sample=True, seed=0, counte
     if store_obs is not None:
         _need(store_obs, "store_obs", _f32, tuple(obs.shape))
         s.obs_store = store_obs.data_ptr()
-    _lib.call("agx_ppo_act_recurrent", ctypes.byref(s), _lib.stream())
+    _lib.call("agx_ppo_act_recurrent_shared" if shared else "agx_ppo_act_recurrent", ctypes.byref(s), _lib.stream())
     res["hidden"] = {**nh_a, **nh_c}
     return res
 
@@ -1158,19 +1168,23 @@ def _recurrent_heads_plan(actor, critic):
         return None
     if box and (head.log_std.dtype != _f32 or not head.log_std.is_cuda or head.log_std.numel() != A):
         return None
+    shared = pa[0].name == pc[0].name  # share_encoders: one output Linear, the actor's
+    if shared and pc[2].out_features != pa[2].out_features:
+        return None
     ts = []
-    for _, _, out, _, layers in (pa, pc):
-        ts += [out.weight, out.bias]
+    for k, (_, _, out, _, layers) in enumerate((pa, pc)):
+        ts += [] if shared and k == 1 else [out.weight, out.bias]
         for lin, ln, _ in layers:
             ts += [lin.weight, lin.bias] + ([ln.weight, ln.bias] if ln is not None else [])
-    return (pa, pc), found, ts + ([head.log_std] if box else [])
+    return (pa, pc), found, ts + ([head.log_std] if box else []), shared
 
 
 def recurrent_heads_params(actor, critic):
     """The parameters ``recurrent_heads_forward`` reads, in the order ``recurrent_heads_backward`` returns their
     gradients: per network (actor, critic) the output Linear's weight and bias, then each head layer's weight,
-    bias and LayerNorm affine; ``log_std`` last (Box).  None where the kernels do not apply (the limits of
-    ``ppo_act_recurrent``, include/agx_recurrent.h)."""
+    bias and LayerNorm affine; ``log_std`` last (Box).  A pair that shares one encoder (encoders named alike) has
+    one output Linear, the actor's: the critic's is not in the list.  None where the kernels do not apply (the
+    limits of ``ppo_act_recurrent``, include/agx_recurrent.h)."""
     found = _recurrent_heads_plan(actor, critic)
     return None if found is None else found[2]
 
@@ -1180,18 +1194,20 @@ def _recurrent_heads(actor, critic, h_top, actions, mask):
     found = _recurrent_heads_plan(actor, critic)
     if found is None:
         return None
-    plans, (kind, A, nvec, cols), params = found
+    plans, (kind, A, nvec, cols), params, shared = found
     box = kind == HEAD_BOX
     R = h_top[0].shape[0] if isinstance(h_top[0], torch.Tensor) and h_top[0].dim() == 2 else 0
-    if not 1 <= R <= _lstm._MAX_ROWS or (box and mask is not None):
+    if not 1 <= R <= _lstm._MAX_ROWS or (box and mask is not None) or len(h_top) != (1 if shared else 2):
         return None
     s = RecurrentHeadsMulti()
-    for k, (plan, h) in enumerate(zip(plans, h_top)):
-        H = plan[1][0][1]
+    for k, plan in enumerate(plans):
+        _fill_recurrent_dense(s.net[k], plan)
+        if shared and k == 1:  # the critic's head reads the actor's latent
+            break
+        h, H = h_top[k], plan[1][0][1]
         if not isinstance(h, torch.Tensor) or tuple(h.shape) != (R, H) or h.dtype != _f32 or not h.is_cuda or \
                 not h.is_contiguous():
             return None
-        _fill_recurrent_dense(s.net[k], plan)
         s.h_top[k], s.H[k] = h.data_ptr(), H
     if not isinstance(actions, torch.Tensor) or actions.dtype != _f32 or not actions.is_cuda or \
             not actions.is_contiguous() or tuple(actions.shape) != ((R,) if kind == HEAD_DISCRETE else (R, cols)):
@@ -1207,7 +1223,7 @@ def _recurrent_heads(actor, critic, h_top, actions, mask):
         s.log_std = actor.head_net.log_std.data_ptr()
     if kind == HEAD_MULTI:
         s.multi = multi_head(nvec)
-    return s, plans, params, keep
+    return s, plans, params, keep, "_shared" if shared else ""
 
 
 def recurrent_heads_forward(actor, critic, h_top, actions, mask=None, *, save=True):
@@ -1216,17 +1232,19 @@ def recurrent_heads_forward(actor, critic, h_top, actions, mask=None, *, save=Tr
     (Discrete, the index), [R, A] (Box), [R, K] (MultiDiscrete, each component's index) or [R, n] (MultiBinary);
     mask uint8 / bool [R, A] or None, A the width of the actor's head.  -> (log_prob, entropy, value [R],
     saved: what ``recurrent_heads_backward`` reads, None without ``save``), or None where the kernels do not
-    apply (the caller runs the torch modules)."""
+    apply (the caller runs the torch modules).  A pair that shares one encoder takes h_top = (the one output,)
+    and agx_recurrent_heads_forward_shared."""
     found = _recurrent_heads(actor, critic, h_top, actions, mask)
     if found is None:
         return None
-    s = found[0]
+    s, form = found[0], found[4]
     dev = actions.device
     out = torch.empty(3, s.R, dtype=_f32, device=dev)
     saved = None
     if save:
-        saved = torch.empty(_lib.load().agx_recurrent_heads_saved_bytes(ctypes.byref(s)) // 4, dtype=_f32, device=dev)
-    _lib.call("agx_recurrent_heads_forward", ctypes.byref(s), out[0].data_ptr(), out[1].data_ptr(),
+        nbytes = getattr(_lib.load(), "agx_recurrent_heads_saved_bytes" + form)(ctypes.byref(s))
+        saved = torch.empty(nbytes // 4, dtype=_f32, device=dev)
+    _lib.call("agx_recurrent_heads_forward" + form, ctypes.byref(s), out[0].data_ptr(), out[1].data_ptr(),
               out[2].data_ptr(), _lib.ptr(saved), _lib.stream())
     return out[0], out[1], out[2], saved
 
@@ -1234,11 +1252,12 @@ def recurrent_heads_forward(actor, critic, h_top, actions, mask=None, *, save=Tr
 def recurrent_heads_backward(actor, critic, h_top, actions, mask, saved, g_log_prob, g_entropy, g_value):
     """agx_recurrent_heads_backward on the inputs and ``saved`` of ``recurrent_heads_forward`` and the upstream
     gradients f32 [R]: two launches.  -> (dh_top of the actor, of the critic [R, H], the gradients of
-    ``recurrent_heads_params`` in its order), or None where the kernels do not apply."""
+    ``recurrent_heads_params`` in its order), or None where the kernels do not apply.  A pair that shares one
+    encoder has one dh_top, with both heads' shares; the critic's is None."""
     found = _recurrent_heads(actor, critic, h_top, actions, mask)
     if found is None:
         return None
-    s, plans, params, _ = found
+    s, plans, params, _, form = found
     R = s.R
     for t, n in ((g_log_prob, "g_log_prob"), (g_entropy, "g_entropy"), (g_value, "g_value")):
         _need(t, n, _f32, (R,))
@@ -1248,7 +1267,8 @@ def recurrent_heads_backward(actor, critic, h_top, actions, mask, saved, g_log_p
     grads = [torch.empty_like(t) for t in params]
     it = iter(grads)
     for k, (_, _, _, _, layers) in enumerate(plans):
-        g.dh_top[k], g.out_w[k], g.out_b[k] = dh[k].data_ptr(), next(it).data_ptr(), next(it).data_ptr()
+        if k < len(dh):  # a network with an output Linear of its own
+            g.dh_top[k], g.out_w[k], g.out_b[k] = dh[k].data_ptr(), next(it).data_ptr(), next(it).data_ptr()
         for j, (_, ln, _) in enumerate(layers):
             e = g.head[k][j]
             e.w, e.b = next(it).data_ptr(), next(it).data_ptr()
@@ -1256,8 +1276,8 @@ def recurrent_heads_backward(actor, critic, h_top, actions, mask, saved, g_log_p
                 e.ln_w, e.ln_b = next(it).data_ptr(), next(it).data_ptr()
     if s.box == HEAD_BOX:
         g.log_std = next(it).data_ptr()
-    ws = torch.empty(_lib.load().agx_recurrent_heads_workspace_bytes(ctypes.byref(s)) // 4, dtype=_f32,
-                     device=actions.device)
-    _lib.call("agx_recurrent_heads_backward", ctypes.byref(s), saved.data_ptr(), ctypes.byref(g), ws.data_ptr(),
-              _lib.stream())
-    return dh[0], dh[1], grads
+    nbytes = getattr(_lib.load(), "agx_recurrent_heads_workspace_bytes" + form)(ctypes.byref(s))
+    ws = torch.empty(nbytes // 4, dtype=_f32, device=actions.device)
+    _lib.call("agx_recurrent_heads_backward" + form, ctypes.byref(s), saved.data_ptr(), ctypes.byref(g),
+              ws.data_ptr(), _lib.stream())
+    return dh[0], dh[1] if len(dh) == 2 else None, grads

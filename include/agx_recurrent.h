@@ -103,6 +103,15 @@ typedef struct agx_recurrent_step {
  * says why) for shapes outside the limits. */
 int agx_ppo_act_recurrent(const agx_recurrent_step *step, void *stream);
 
+/* The same step for an agent whose networks share one encoder (`share_encoders`): step->actor is the shared
+ * encoder with the actor's head; of step->critic only `head` and `n_head` are read, and its first layer's `in`
+ * must be actor.latent.  The critic's lstm, out_*, latent, states and stores are ignored.  Grid (ceil(N / 16), 1):
+ * a workgroup runs the LSTM and the output Linear once per row tile and then both heads off the one latent tile in
+ * LDS, depth by depth as one tile list over its 8 waves.  Every output tile is the same single-wave chain as in
+ * agx_ppo_act_recurrent, so actions, log-probs, entropy and next states have the bits that entry gives on the same
+ * actor, and the values the bits it gives for a critic whose encoder is a copy of the actor's. */
+int agx_ppo_act_recurrent_shared(const agx_recurrent_step *step, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

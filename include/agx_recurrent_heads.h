@@ -85,6 +85,23 @@ int agx_recurrent_heads_forward(const agx_recurrent_heads *heads, float *log_pro
 int agx_recurrent_heads_backward(const agx_recurrent_heads *heads, const void *saved,
                                  const agx_recurrent_heads_grads *grads, void *workspace, void *stream);
 
+/* The same four entry points for an agent whose networks share one encoder (`share_encoders`), on the same
+ * structs: h_top[0], H[0] and net[0].out_* are the shared ones, of net[1] only the head is read (its first
+ * layer's `in` must be net[0].latent); h_top[1], H[1], dh_top[1], out_w[1] and out_b[1] are ignored.
+ *
+ * Forward, grid (ceil(R / 16), 1): one latent per row tile, saved once, then both heads in that workgroup as one
+ * tile list per depth; log_prob, entropy and value have the bits of agx_recurrent_heads_forward for a critic whose
+ * output Linear is a copy of the actor's on the same h_top.  Backward rows, the same grid: one workgroup walks both
+ * heads back to the latent, forms dLatent = dX_actor + dX_critic in LDS in that order, applies the output
+ * activation's backward once and writes one dZ_out and one dh_top[0] = dZ_out W_out.  Backward params: the same
+ * one-wave jobs over one output Linear ([dW_out | db_out] from the summed dZ_out) and the two heads. */
+size_t agx_recurrent_heads_saved_bytes_shared(const agx_recurrent_heads *heads);
+size_t agx_recurrent_heads_workspace_bytes_shared(const agx_recurrent_heads *heads);
+int agx_recurrent_heads_forward_shared(const agx_recurrent_heads *heads, float *log_prob, float *entropy,
+                                       float *value, void *saved, void *stream);
+int agx_recurrent_heads_backward_shared(const agx_recurrent_heads *heads, const void *saved,
+                                        const agx_recurrent_heads_grads *grads, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,10 @@ Discrete(4), one LSTM layer of H = 64 per encoder, max_seq_len 16 (CHUNKED), 64 
   python tools/bptt_time.py --heads --space NAME [--out FILE]
       the same on another action space (SPACES: Discrete of 6 / 32 logits, MultiDiscrete([3, 3]) / ([2] * 16),
       MultiBinary(4) / (32)), under "learn_heads_NAME".
+  python tools/bptt_time.py --heads --shared [--out profiles/bptt_time.json]
+      the same four settings on a shared-encoder agent (``share_encoders=True``) and, for information,
+      the two heads-on settings on a separate-encoder agent of the same shape in the same alternating blocks, under
+      "learn_heads_shared".
 """
 import copy
 import json
@@ -46,7 +50,7 @@ SPACES = {"discrete6": ("Discrete", 6), "multidiscrete3x3": ("MultiDiscrete", [3
           "multibinary32": ("MultiBinary", 32)}
 
 
-def setup(space=None):
+def setup(space=None, shared=False):
     import numpy as np
     import torch
 
@@ -58,7 +62,7 @@ def setup(space=None):
     # the exclusive upper bounds of a step's random actions: [] (Discrete), [K] or [n]
     high = torch.tensor([2] * arg if kind == "MultiBinary" else arg)
     torch.manual_seed(0)
-    agent = PPO(Box(-np.inf, np.inf, (OBS,)), getattr(envs, kind)(arg), recurrent=True, share_encoders=False, num_envs=N,
+    agent = PPO(Box(-np.inf, np.inf, (OBS,)), getattr(envs, kind)(arg), recurrent=True, share_encoders=shared, num_envs=N,
                 learn_step=T * N, max_seq_len=MAX_SEQ_LEN, batch_size=BATCH, update_epochs=EPOCHS,
                 net_config={"encoder_config": {"hidden_state_size": H, "num_layers": 1}})
     buf, g = agent.rollout_buffer, torch.Generator().manual_seed(1)
@@ -191,28 +195,32 @@ HEADS = {"heads off": (None, "0"), "heads on": (None, "1"), "AGX_LSTM=1, heads o
          "AGX_LSTM=1, heads on": ("1", "1")}  # setting -> (AGX_LSTM, AGX_RECURRENT_LEARN)
 
 
-def heads(out_path, space=None):
-    agent = setup(space)
+def heads(out_path, space=None, shared=False):
+    agents = dict.fromkeys(HEADS, setup(space, shared))
+    if shared:
+        sep = setup(space)
+        agents.update({"separate encoders, " + s: sep for s in HEADS if s.endswith("heads on")})
 
     def learn(setting):
-        lstm, switch = HEADS[setting]
+        agent = agents[setting]
+        lstm, switch = HEADS[setting.replace("separate encoders, ", "")]
         os.environ.pop("AGX_LSTM", None)
         if lstm is not None:
             os.environ["AGX_LSTM"] = lstm
         os.environ["AGX_RECURRENT_LEARN"] = switch
         return block(agent.learn, lambda: gae(agent), CALLS["learn"])
 
-    for setting in HEADS:  # warm-up of every setting
+    for setting in agents:  # warm-up of every setting
         learn(setting)
-    times = {setting: [] for setting in HEADS}
+    times = {setting: [] for setting in agents}
     for _ in range(ROUNDS):  # alternating blocks
-        for setting in HEADS:
+        for setting in agents:
             times[setting].append(1e3 * learn(setting))
     result = {}
     if out_path and os.path.exists(out_path):
         with open(out_path) as f:
             result = json.load(f)
-    key = "learn_heads" + (f"_{space}" if space else "")
+    key = "learn_heads" + (f"_{space}" if space else "") + ("_shared" if shared else "")
     result[key] = {"unit": "ms per learn()", "calls_per_block": CALLS["learn"], "blocks": ROUNDS,
                              **{setting: spread(v) for setting, v in times.items()}}
     print(key, json.dumps(result[key]))
@@ -224,7 +232,8 @@ def heads(out_path, space=None):
 def main():
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     if "--heads" in sys.argv:
-        return heads(out_path, sys.argv[sys.argv.index("--space") + 1] if "--space" in sys.argv else None)
+        return heads(out_path, sys.argv[sys.argv.index("--space") + 1] if "--space" in sys.argv else None,
+                     "--shared" in sys.argv)
     agent = setup()
     ref = copy.deepcopy(agent)
     ref.reinit_optimizers()

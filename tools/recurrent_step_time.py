@@ -14,6 +14,10 @@ MultiBinary(32), each beside the Discrete space of the same logit count.
 
   python tools/recurrent_step_time.py [--out FILE]    (default profiles/recurrent_step_time.json)
   python tools/recurrent_step_time.py --spaces [--out FILE]    (default profiles/recurrent_step_spaces.json)
+  python tools/recurrent_step_time.py --shared [--out FILE]
+      the same shapes and method for a shared-encoder agent (``share_encoders=True``): its fused step
+      (agx_ppo_act_recurrent_shared) against its torch modules, and beside them, for information, the fused step
+      of a separate-encoder agent of the same shape.  Added to --out under "cells_shared"; other keys are kept.
 """
 import json
 import os
@@ -37,7 +41,7 @@ SPACES = {"discrete6": dict(n_actions=6), "multidiscrete3x3": dict(nvec=[3, 3]),
           "multibinary32": dict(n_binary=32)}
 
 
-def time_cell(N, H, L, env_kw):
+def time_cell(N, H, L, env_kw, shared=False):
     import numpy as np
     import torch
 
@@ -45,15 +49,17 @@ def time_cell(N, H, L, env_kw):
     from agilerl_amd.envs import SyntheticVecEnv
     from agilerl_amd.rollouts import collect_rollouts_recurrent
 
-    def make(fused):
+    def make(fused, share=shared):
         env = SyntheticVecEnv(N, obs_dim=8, p_done=1 / 50, seed=3, **env_kw)
         torch.manual_seed(N + H + L)
-        agent = PPO(env.single_observation_space, env.single_action_space, recurrent=True, share_encoders=False,
+        agent = PPO(env.single_observation_space, env.single_action_space, recurrent=True, share_encoders=share,
                     num_envs=N, learn_step=T * N, fused_step=fused,
                     net_config={"encoder_config": {"hidden_state_size": H, "num_layers": L}})
         return agent, env
 
     variants = {"fused": make(True), "torch": make(False)}
+    if shared:
+        variants["separate_fused"] = make(True, False)
     obs = np.random.default_rng(0).standard_normal((N, 8)).astype(np.float32)
 
     def act(agent):
@@ -93,14 +99,23 @@ if __name__ == "__main__":
     spaces = "--spaces" in sys.argv
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
         os.path.join(ROOT, "profiles", "recurrent_step_spaces.json" if spaces else "recurrent_step_time.json")
+    shared = "--shared" in sys.argv
     result = {"calls_per_block": CALLS, "rounds": ROUNDS, "unit": "median, min, max (host wall-clock)",
               "fused": "fused_step=True", "torch": "the switch off (the parent commit's path)", "cells": {}}
     cells = [(f"{name}_N64_H64_L1", 64, 64, 1, kw) for name, kw in SPACES.items()] if spaces else \
         [(f"{name}_N{N}_H{H}_L{L}", N, H, L, kw) for name, kw in (("discrete4", dict(n_actions=4)),
                                                                   ("box6", dict(action_dim=6)))
          for N in NS for H in HS for L in LS]
+    key = "cells"
+    if shared:  # beside what the file holds
+        key, kept = "cells_shared", result
+        with open(out_path) as f:
+            result = json.load(f)
+        result[key] = {"fused": "share_encoders=True, fused_step=True", "torch": "share_encoders=True, the switch off",
+                       "separate_fused": "share_encoders=False, fused_step=True (for information)",
+                       **{k: kept[k] for k in ("calls_per_block", "rounds", "unit")}}
     for name, N, H, L, kw in cells:
-        result["cells"][name] = time_cell(N, H, L, kw)
+        result[key][name] = time_cell(N, H, L, kw, shared)
         with open(out_path, "w") as f:  # after every cell: a run cut short keeps what it measured
             json.dump(result, f, indent=1)
             f.write("\n")
